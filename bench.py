@@ -3,10 +3,13 @@
 
 N = 1: a "step" is one pass of lzs_compress_batch_device over one batch of independent 64 KiB
 blocks already resident in HBM (BASELINE.json configs[1]: 1 GiB = 16384 blocks of
-enwik-style ASCII text).  After the timed region EVERY block is compared with the reference C
-compressor on the host cores (which is also the cpu_baseline), and the config-5 job below is run
-once more at world size 1 (`config5_world1`), so that the scaling curve's first point has the same
-fields as the others.
+enwik-style ASCII text).  A plain run sets up, warms up, times the steps and prints the line
+(`value`, `ms_per_step`, and the roofline of the timed launches).  With --full, after the timed
+region EVERY block is also compared with the reference C compressor on the host cores (which is
+also the cpu_baseline), the other two classes are measured and checked the same way, and the
+config-5 job below is run once more at world size 1 (`config5_world1`), so that the scaling
+curve's first point has the same fields as the others.  --dump-outputs DIR writes what the last
+timed step computed to DIR/*.npy (dump_outputs below), for comparing two builds output for output.
 
 N > 1 (BASELINE.json configs[4]): 131072 blocks (8 GiB) per GPU --
 64 GiB at 8 GPUs -- generated in HBM on the root GPU by lzs_gen_blocks_kernel; a "step" is the
@@ -19,7 +22,8 @@ un-overlapped pass after the timed region (`phases_ms`, `compute_only_GBps`, `sc
 
 How it starts (the parent never touches the GPU):
 
-    python bench.py                            # 1 GPU, in this process
+    python bench.py                            # 1 GPU, in this process (the headline only)
+    python bench.py --full                     # ... and every check and secondary figure
     python bench.py --gpus 8                   # no WORLD_SIZE in the environment: launches its own
                                                # 8 ranks (a child `python -m torch.distributed.run`)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -237,6 +241,41 @@ def pmc_limiter(cls: str):
     return dict(rec, kernel_source_sha256=doc["kernel_source_sha256"], how=doc.get("how")), None
 
 
+DUMP_SAMPLE_BLOCKS = 128        # compressed blocks kept whole by --dump-outputs (128 x 73744 float32 = 38 MB)
+DUMP_SAMPLE_SEED = 20240501
+
+
+def dump_outputs(out_dir: str, slots, lens) -> dict:
+    """--dump-outputs: what the caller of lzs_compress_batch_device received from the last timed step, as .npy files
+    that two builds can be compared with, file for file:
+      compressed_lengths.npy        float64 [nb]      every block's compressed length
+      compressed_checksums.npy      float64 [nb]      every block's sum of byte[i] * (i + 1) over its compressed bytes
+                                                      (exact: at most 255 * 73731 * 73732 / 2 < 2**53)
+      compressed_sample_index.npy   float64 [S]       a fixed, seeded, sorted sample of S block indices
+      compressed_sample.npy         float32 [S, stride] those blocks' slots, zero past each block's length
+    Bytes past a block's length are not part of the output (the slots are not cleared), so they count nowhere."""
+    os.makedirs(out_dir, exist_ok=True)
+    nb, stride = slots.shape
+    lens64 = lens.to(torch.int64)
+    w = torch.arange(1, stride + 1, dtype=torch.int64, device=slots.device)
+    sums = torch.empty(nb, dtype=torch.int64, device=slots.device)
+    for lo in range(0, nb, 512):
+        hi = min(nb, lo + 512)
+        live = w[None, :] <= lens64[lo:hi, None]
+        sums[lo:hi] = (slots[lo:hi].to(torch.int64) * w * live).sum(1)
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nb, min(nb, DUMP_SAMPLE_BLOCKS), replace=False))
+    idx = torch.from_numpy(pick).to(slots.device)
+    sample = slots.index_select(0, idx)
+    sample = sample * (torch.arange(stride, device=slots.device)[None, :] < lens64.index_select(0, idx)[:, None])
+    arrays = {"compressed_lengths": lens64.cpu().numpy().astype(np.float64),
+              "compressed_checksums": sums.cpu().numpy().astype(np.float64),
+              "compressed_sample_index": pick.astype(np.float64),
+              "compressed_sample": sample.cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def emit(result: dict) -> None:
     """The ONE JSON line, last on stdout: RCCL writes a version banner through C stdio, which a pipe
     holds back until exit -- flush it out first."""
@@ -275,6 +314,15 @@ def parse_args(argv):
     ap.add_argument("--allow-shared-gpu", action="store_true",
                     help="ranks may share a GPU (LOCAL_RANK modulo the device count): for testing the launch and "
                          "fallback machinery on a one-GPU box; RCCL itself refuses two ranks on one device")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also measure and check everything else -- the device copy, the block "
+                         "decoder, single_stream, the cpu_baseline with every block against the host codec, the other two "
+                         "classes and config5_world1 (the --no-* switches above still drop single pieces).  Without it a "
+                         "run sets up, warms up, times the steps and prints the line.  (N > 1 lines are the same either way.)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write what the last step computed to DIR/*.npy (e.g. bench_outputs/; float32 / float64, "
+                         "under 64 MB): every block's compressed length and position-weighted byte sum, and the compressed "
+                         "bytes of a fixed, seeded sample of blocks")
     return ap.parse_args(argv)
 
 
@@ -981,6 +1029,23 @@ def single(args) -> int:
     }
     limiter, limiter_note = pmc_limiter(args.workload) if nb == 16384 else (None, "the counters were taken at 16384 blocks per launch")
     result["roofline"]["limiter"] = limiter if limiter else limiter_note
+    if args.dump_outputs:
+        info = dump_outputs(args.dump_outputs, slots, lens)
+        print(f"bench.py: wrote {', '.join(info['files'])} ({info['bytes']} bytes) to {info['dir']}", file=sys.stderr, flush=True)
+    if args.full:
+        # the buffers are handed over, so that full_extras can free them before the other classes are set up
+        bufs = [host, x, slots, lens]
+        del host, x, slots, lens
+        full_extras(args, dev, result, bufs, lens_h, nb, achieved, avg_ms, ratio)
+    emit(result)
+    return 0
+
+
+def full_extras(args, dev, result, bufs, lens_h, nb, achieved, avg_ms, ratio) -> None:
+    """--full, N = 1: everything the line carries beside the headline, each piece measured after the timed steps.
+    `bufs` = [host blocks, device blocks, slots, lengths] of the headline launch; emptied here."""
+    host, x, slots, lens = bufs
+    bufs.clear()
     # the box's own streaming figure next to the 8 TB/s of the data sheet (SURVEY.md 8d: report
     # the fraction against both): a device-to-device copy of the same 1 GiB, read + written
     try:
@@ -1027,7 +1092,7 @@ def single(args) -> int:
             result["single_stream"] = {"error": str(exc)}
     if not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(host, lens_h, slots)
-    del slots, x, host
+    del slots, x, host, lens
     if not args.no_other_classes:
         # BASELINE.json configs[2] and [3] (or whichever two classes the headline is not), same launch, same check
         result["other_classes"] = {}
@@ -1054,13 +1119,13 @@ def single(args) -> int:
             result["config5_world1"] = config5_world1(args, dev)
         except Exception as exc:                      # noqa: BLE001 -- an extra, never the contract line's problem
             result["config5_world1"] = {"error": f"{type(exc).__name__}: {exc}"}
-    emit(result)
-    return 0
 
 
 def main() -> int:
     argv = sys.argv[1:]
     args = parse_args(argv)
+    if args.dump_outputs and (args.gpus > 1 or args.sharded_job):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the N = 1 launch only")
     role = os.environ.get("LZS_BENCH_ROLE")
     if role == "job":
         return worker_job(args)

@@ -98,6 +98,20 @@ def test_check_ranges_every_block_and_samples():
             assert len(got) <= max(2, (hi - lo + every - 1) // every + 1)
 
 
+def test_a_plain_run_is_lean_unless_full_is_asked():
+    """--full is off by default (the extras after the headline are its), --dump-outputs takes a directory, and asking
+    for the outputs of an N > 1 job is refused before anything is launched."""
+    b = _bench_module()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LZS_BENCH_ROLE", "LZS_BENCH_DIR")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "out"],
+                       capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+    assert r.returncode != 0 and "N = 1" in r.stderr
+
+
 def test_run_token_names_one_launch():
     b = _bench_module()
     tok = b.run_token()

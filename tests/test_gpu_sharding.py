@@ -66,7 +66,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu_falls_back():
 def test_bench_default_line_checks_every_block_and_carries_the_config5_fields():
     """The driver's N = 1 command (smaller batch): the contract line, the every-block comparison with
     the host codec, and the config-5 job at world size 1 with the fields of the N > 1 lines."""
-    line, _ = _bench(["--gpus", "1", "--blocks", "2048", "--steps", "3", "--warmup", "1", "--no-single-stream"])
+    line, _ = _bench(["--gpus", "1", "--blocks", "2048", "--steps", "3", "--warmup", "1", "--no-single-stream", "--full"])
     assert line["n_gpus"] == 1 and line["unit"] == "GB/s" and line["roofline"]["bound"] == "hbm"
     cb = line["cpu_baseline"]
     assert cb["gpu_output_bit_exact_on_sample"] is True and cb["check"]["blocks_compared"] == cb["check"]["of"] == 2048
@@ -85,6 +85,33 @@ def test_bench_default_line_checks_every_block_and_carries_the_config5_fields():
     assert "limiter" in line["roofline"]
 
 
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the N = 1 line carries the headline and nothing measured after it; --dump-outputs writes what the
+    last timed step computed, and those files are the oracle's streams for the blocks they hold."""
+    import oracle
+    from lzs_compression_amd import workload
+    line, _ = _bench(["--gpus", "1", "--blocks", "2048", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["unit"] == "GB/s" and line["dtype"] == "u8"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert not {"cpu_baseline", "other_classes", "config5_world1", "single_stream", "block_decoder"} & set(line)
+    arrays = {n: np.load(tmp_path / (n + ".npy")) for n in
+              ("compressed_lengths", "compressed_checksums", "compressed_sample_index", "compressed_sample")}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    blocks = workload.fill("text", 2048, 65536)
+    want, want_len, _ = oracle.run_blocks(oracle.oracle(), blocks, threads=4)
+    assert np.array_equal(arrays["compressed_lengths"], want_len.astype(np.float64))
+    w = np.arange(1, want.shape[1] + 1, dtype=np.int64)
+    sums = [int((want[b, :want_len[b]].astype(np.int64) * w[:want_len[b]]).sum()) for b in range(2048)]
+    assert np.array_equal(arrays["compressed_checksums"], np.array(sums, dtype=np.float64))
+    idx = arrays["compressed_sample_index"].astype(np.int64)
+    assert len(idx) == 128 and np.all(np.diff(idx) > 0)
+    for j, b in enumerate(idx):
+        n = int(want_len[b])
+        got = arrays["compressed_sample"][j]
+        assert np.array_equal(got[:n], want[b, :n].astype(np.float32)) and not got[n:].any(), b
+
+
 def test_bench_under_torch_distributed_run_with_one_rank():
     """The driver's launch form at N = 1, should it use it: `torch.distributed.run --nproc-per-node 1
     bench.py --gpus 1`.  The config-5 extra makes a rendezvous of its own there (the environment
@@ -93,7 +120,7 @@ def test_bench_under_torch_distributed_run_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LZS_BENCH_ROLE", "LZS_BENCH_DIR")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--blocks", "2048", "--steps", "2",
-                        "--warmup", "1", "--no-single-stream", "--no-cpu-baseline"],
+                        "--warmup", "1", "--no-single-stream", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=150, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -157,24 +157,46 @@ def test_fast_finder_equals_written_rule():
         assert O.compress(data) == O.compress_brute(data)
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref not built here")
-def test_live_differential_vs_reference():
-    R = oracle.ref()
+def differential_outputs(C):
+    """Per fuzz input (seed 5), every output of codec C the differential compares, in order: the one-shot compression at
+    full and at seven smaller capacities, garbage decoded into three capacities, a cut stream and the stream decoded
+    into half the room."""
     rng = np.random.default_rng(5)
+    per_input = []
     for data in _fuzz_inputs(rng, 400):
-        want = R.compress(data)
-        assert O.compress(data) == want
-        for cap in (0, 1, 2, 3, 7, 100, len(want) - 1 if want else 0):
-            cap = max(cap, 0)
-            assert O.compress(data, cap) == R.compress(data, cap)
-        assert O.decompress(want, len(data) + 3) == data
+        want = C.compress(data)
+        outs = [want] + [C.compress(data, max(cap, 0)) for cap in (0, 1, 2, 3, 7, 100, len(want) - 1 if want else 0)]
+        assert C.decompress(want, len(data) + 3) == data
         # garbage / truncated streams, bounded outputs
         junk = bytes(rng.integers(0, 256, int(rng.integers(0, 200)), dtype=np.uint8))
-        for cap in (0, 5, 1000):
-            assert O.decompress(junk, cap) == R.decompress(junk, cap)
+        outs += [C.decompress(junk, cap) for cap in (0, 5, 1000)]
         cut = want[:int(rng.integers(0, len(want) + 1))]
-        assert O.decompress(cut, len(data) + 3) == R.decompress(cut, len(data) + 3)
-        assert O.decompress(want, len(data) // 2) == R.decompress(want, len(data) // 2)
+        outs += [C.decompress(cut, len(data) + 3), C.decompress(want, len(data) // 2)]
+        per_input.append(outs)
+    return per_input
+
+
+def outputs_digest(outs):
+    """One digest of a fuzz input's outputs (each length-prefixed), as tests/golden/ref_digests.json stores them."""
+    h = hashlib.sha256()
+    for o in outs:
+        h.update(len(o).to_bytes(4, "little") + o)
+    return h.hexdigest()[:32]
+
+
+def test_live_differential_vs_reference():
+    """The restatement against the reference on 400 fuzz inputs: every output equal to the reference's, by the digests
+    tests/golden/ref_digests.json holds (minted from the compiled reference by tests/golden/make_ref_digests.py) and,
+    where oracle/_ref was built, byte for byte against the reference itself."""
+    ours = differential_outputs(O)
+    want = golden_json("ref_digests.json")["oracle_differential"]
+    assert len(want) == len(ours) == 400
+    for i, outs in enumerate(ours):
+        assert outputs_digest(outs) == want[i], i
+    if oracle.have_ref():
+        theirs = differential_outputs(oracle.ref())
+        for i, (a, b) in enumerate(zip(ours, theirs)):
+            assert a == b, i
 
 
 @pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref not built here")

@@ -18,12 +18,12 @@ import numpy as np
 import pytest
 
 import oracle
-from conftest import golden_bytes, length_bits, uncompressible_sequence
+from conftest import golden_bytes, golden_json, length_bits, uncompressible_sequence
 import lzs_compression_amd as lzs
 from lzs_compression_amd import workload
 
 O = oracle.oracle()
-R = oracle.ref()
+R = oracle.ref() if oracle.have_ref() else None
 
 
 @pytest.fixture
@@ -282,51 +282,11 @@ def _first_long_offset_zero(stream: bytes):
             length = 15
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref/liblzs_ref.so was not built (needs /root/reference)")
-def test_incremental_decoder_on_malformed_streams_against_the_reference_itself(host):
-    """Garbage through lzs_decompress_incremental() (host route: what a caller's small pieces get) beside the compiled
-    reference's own incremental decoder on a zeroed parameter block.  Byte for byte the same -- except from the first token
-    with a LONG OFFSET OF 0 on, which no compressor emits: the reference's incremental decoder reads a length there and
-    copies from the oldest bytes of its ring, which lzs_decompress_init() never cleared (lzs-decompression.c:420-428,
-    585-593: the caller's memory until 2047 bytes have been produced), while every decoder of this build applies the
-    one-shot decoder's rule (:280: no length field, no copy) whatever the size of the piece.  INTEGRATION.md section 2
-    says so; up to that token the outputs agree."""
+def malformed_streams():
+    """The 400 streams of the test below, each with the room it is decoded into and the piece size our side takes."""
     import random
-    import struct
-    ref = ctypes.CDLL(os.path.join(os.path.dirname(oracle.__file__), "_ref", "liblzs_ref.so"))
-    ref.lzs_decompress_incremental.restype = ctypes.c_size_t
-    ref.lzs_decompress_incremental.argtypes = [ctypes.c_void_p]
-    ref.lzs_decompress_init.argtypes = [ctypes.c_void_p]
-
-    def ref_decode(stream, room):
-        raw = ctypes.create_string_buffer(2096)                 # LzsDecompressParameters_t, zeroed
-        ref.lzs_decompress_init(ctypes.addressof(raw))
-        src = ctypes.create_string_buffer(bytes(stream), max(len(stream), 1))
-        dst = ctypes.create_string_buffer(room)
-        struct.pack_into("<QQQQ", raw, 0, ctypes.addressof(src), ctypes.addressof(dst), len(stream), room)
-        n = 0
-        for _ in range(64):                                     # (a call returns at every end marker)
-            n += ref.lzs_decompress_incremental(ctypes.addressof(raw))
-            if struct.unpack_from("<Q", raw, 16)[0] == 0 and not raw.raw[32] & lzs.STATUS_END_MARKER:
-                break
-        return dst.raw[:n]
-
-    def our_decode(stream, room, piece):
-        d, out, pos = lzs.IncrementalDecompressor(), bytearray(), 0
-        while pos < len(stream) and len(out) < room:
-            pending = stream[pos:pos + piece]
-            pos += len(pending)
-            for _ in range(64):
-                got, used, status = d.step(pending, room - len(out))
-                out += got
-                pending = pending[used:]
-                if not pending or len(out) >= room:
-                    break
-        return bytes(out)
-
     rng = random.Random(20261004)
     valid = O.compress(bytes(workload.fill("text", 1, 3000).reshape(-1)))
-    same = differing = 0
     for it in range(400):
         n = rng.randint(1, 360)
         kind = it % 4
@@ -344,14 +304,77 @@ def test_incremental_decoder_on_malformed_streams_against_the_reference_itself(h
             bits += "".join(rng.choice("01") for _ in range(8 * n))
             bits = bits[:len(bits) // 8 * 8]
             stream = bytes(int(bits[i:i + 8], 2) for i in range(0, len(bits), 8))
-        room = 20000
-        want = ref_decode(stream, room)
-        got = our_decode(stream, room, rng.choice((1, 7, 64, 4096)))
+        yield stream, 20000, rng.choice((1, 7, 64, 4096))
+
+
+def ref_incremental_decode(stream, room):
+    """The compiled reference's own lzs_decompress_incremental() on a zeroed parameter block (oracle/_ref/liblzs_ref.so)."""
+    import struct
+    ref = ctypes.CDLL(os.path.join(os.path.dirname(oracle.__file__), "_ref", "liblzs_ref.so"))
+    ref.lzs_decompress_incremental.restype = ctypes.c_size_t
+    ref.lzs_decompress_incremental.argtypes = [ctypes.c_void_p]
+    ref.lzs_decompress_init.argtypes = [ctypes.c_void_p]
+    raw = ctypes.create_string_buffer(2096)                     # LzsDecompressParameters_t, zeroed
+    ref.lzs_decompress_init(ctypes.addressof(raw))
+    src = ctypes.create_string_buffer(bytes(stream), max(len(stream), 1))
+    dst = ctypes.create_string_buffer(room)
+    struct.pack_into("<QQQQ", raw, 0, ctypes.addressof(src), ctypes.addressof(dst), len(stream), room)
+    n = 0
+    for _ in range(64):                                         # (a call returns at every end marker)
+        n += ref.lzs_decompress_incremental(ctypes.addressof(raw))
+        if struct.unpack_from("<Q", raw, 16)[0] == 0 and not raw.raw[32] & lzs.STATUS_END_MARKER:
+            break
+    return dst.raw[:n]
+
+
+def malformed_digests(out, cut, room):
+    """What tests/golden/ref_digests.json keeps of the reference's output for one stream: its digest and, where the
+    stream has a long offset of 0 inside the room, the digest of the output up to that token."""
+    import hashlib
+    d = lambda b: hashlib.sha256(b).hexdigest()[:32]             # noqa: E731
+    return [d(out), d(out[:cut]) if cut is not None and cut < room else None]
+
+
+def test_incremental_decoder_on_malformed_streams_against_the_reference_itself(host):
+    """Garbage through lzs_decompress_incremental() (host route: what a caller's small pieces get) beside the compiled
+    reference's own incremental decoder on a zeroed parameter block.  Byte for byte the same -- except from the first token
+    with a LONG OFFSET OF 0 on, which no compressor emits: the reference's incremental decoder reads a length there and
+    copies from the oldest bytes of its ring, which lzs_decompress_init() never cleared (lzs-decompression.c:420-428,
+    585-593: the caller's memory until 2047 bytes have been produced), while every decoder of this build applies the
+    one-shot decoder's rule (:280: no length field, no copy) whatever the size of the piece.  INTEGRATION.md section 2
+    says so; up to that token the outputs agree.  The reference's outputs are the digests tests/golden/ref_digests.json
+    holds (tests/golden/make_ref_digests.py) and, where oracle/_ref was built, the reference itself."""
+    def our_decode(stream, room, piece):
+        d, out, pos = lzs.IncrementalDecompressor(), bytearray(), 0
+        while pos < len(stream) and len(out) < room:
+            pending = stream[pos:pos + piece]
+            pos += len(pending)
+            for _ in range(64):
+                got, used, status = d.step(pending, room - len(out))
+                out += got
+                pending = pending[used:]
+                if not pending or len(out) >= room:
+                    break
+        return bytes(out)
+
+    fixture = golden_json("ref_digests.json")["incremental_decoder_on_malformed_streams"]
+    live = oracle.have_ref()
+    same = differing = 0
+    for it, (stream, room, piece) in enumerate(malformed_streams()):
+        got = our_decode(stream, room, piece)
         cut = _first_long_offset_zero(stream)
+        mine = malformed_digests(got, cut, room)
+        if live:
+            want = ref_incremental_decode(stream, room)
+            assert malformed_digests(want, cut, room) == fixture[it], it      # (the stored digests are the reference's)
         if cut is None or cut >= room:
-            assert got == want, (it, stream.hex())
+            assert mine[0] == fixture[it][0], (it, stream.hex())
+            if live:
+                assert got == want, (it, stream.hex())
             same += 1
         else:
-            assert got[:cut] == want[:cut], (it, cut, stream.hex())
-            differing += got != want
+            assert mine[1] == fixture[it][1], (it, cut, stream.hex())
+            if live:
+                assert got[:cut] == want[:cut], (it, cut, stream.hex())
+            differing += mine[0] != fixture[it][0]
     assert same >= 100 and differing >= 20          # (both kinds were met)

@@ -2,7 +2,7 @@
 # Launcher-path and PCIe-inclusive sanity checks on the 1-GPU box.
 cd $GRAFT_REPO_ROOT
 echo "== torchrun nproc=1 (driver's launch form, WORLD_SIZE=1)"
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-200
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --full 2>&1 | tail -1 | cut -c1-200
 echo "== nccl world of 1: sharding helpers on device tensors"
 timeout 300 python - <<'PY'
 import os, torch, torch.distributed as dist

@@ -9,9 +9,9 @@ timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | grep -v "^RCCL version\|
 # ... and once more the way a production process runs the library: the environment read once (no LZS_DEV_ENV), every call on the
 # device; the tests that flip a switch of the library skip themselves (tests/conftest.py)
 LZS_TEST_CACHED_ENV=1 LZS_ROUTE=device timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | grep -v "^RCCL version\|^HIP version\|^ROCm version\|^Hostname\|^Librccl path" | tail -5 | tee $OUT/pytest_gpu_cached_env.txt
-timeout 600 python bench.py --steps 10 --warmup 2 2>/dev/null | tail -1 | tee $OUT/bench_text.json
-timeout 300 python bench.py --steps 10 --warmup 2 --workload lowent --no-config5 --no-other-classes 2>/dev/null | tail -1 | tee $OUT/bench_lowent.json
-timeout 300 python bench.py --steps 10 --warmup 2 --workload random --no-config5 --no-other-classes 2>/dev/null | tail -1 | tee $OUT/bench_random.json
+timeout 600 python bench.py --steps 10 --warmup 2 --full 2>/dev/null | tail -1 | tee $OUT/bench_text.json
+timeout 300 python bench.py --steps 10 --warmup 2 --full --workload lowent --no-config5 --no-other-classes 2>/dev/null | tail -1 | tee $OUT/bench_lowent.json
+timeout 300 python bench.py --steps 10 --warmup 2 --full --workload random --no-config5 --no-other-classes 2>/dev/null | tail -1 | tee $OUT/bench_random.json
 export TMPDIR=/tmp
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rocprof_stats -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-config5 --no-other-classes > $OUT/rocprof_bench.log 2>&1
