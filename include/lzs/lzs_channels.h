@@ -1,0 +1,94 @@
+/*
+ * lzs/lzs_channels.h -- additive entry points of the MI355X build of liblzs: many channels, one packet each, per launch.
+ *
+ * A channel is one LZS history carried from packet to packet, the "sequential history" of RFC 1974: a packet may refer back
+ * into the packets before it on the same channel.  The reference keeps such a history in one parameter block per stream
+ * (lzs_compress_incremental() / lzs_decompress_incremental(), lzs.h), one call per packet.  The calls below take thousands of
+ * channels in one launch -- the shape of a PPP or tunnel endpoint that holds one history per link or session.
+ *
+ * CHANNEL STATE.  A channel is an opaque slot of LZS_CHANNEL_STATE_BYTES bytes in device memory, 4-byte aligned:
+ *
+ *     offset 0   uint32_t hist_len         bytes of history, 0 .. 2047
+ *     offset 4   reserved, zero            (to offset 64)
+ *     offset 64  uint8_t  hist[2048]       hist[0 .. hist_len): the history, oldest byte first; the rest zero
+ *
+ * An all-zero slot is a new channel: lzs_compress_init_full() for the compressor, lzs_decompress_init() for the
+ * decompressor.  Setting hist_len to 0 resets a channel.  Compressor and decompressor states have the same layout but are
+ * separate arrays; after a packet that went through both cleanly, the compressor's slot and the peer decompressor's slot hold
+ * the same bytes (both calls rewrite all of hist[]: the history, then zeros).
+ *
+ * All functions return LZS_OK (0) or a negative LZS_E_* code (lzs_batch.h); lzs_last_error() gives the message.
+ */
+#ifndef LZS_MI355X_LZS_CHANNELS_H
+#define LZS_MI355X_LZS_CHANNELS_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "lzs_batch.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define LZS_CHANNEL_STATE_BYTES  2112u   /* one channel's slot: 64-byte header + 2048 bytes of history */
+#define LZS_CHANNEL_HISTORY_AT   64u     /* offset of hist[] in a slot */
+#define LZS_CHANNELS_MAX         0x7FFFFFFFu   /* packets per call */
+
+/*
+ * Device-pointer channel compression, asynchronous on `hip_stream`.
+ *
+ *   packet b input  : d_in  + b * in_stride,  length d_in_len ? d_in_len[b] : in_len (at most LZS_BLOCK_MAX)
+ *   packet b output : d_out + b * out_stride, capacity out_cap;  d_out_len[b]: bytes written
+ *   packet b channel: c = d_channel ? d_channel[b] : b;  its state: d_states + c * LZS_CHANNEL_STATE_BYTES
+ *
+ * Packet b's bytes are what lzs_compress_incremental(&P_c, true) writes when P_c was initialised and fed the channel's earlier
+ * packets the same way, and the packet is given whole with room for LZS_COMPRESSED_MAX(len) bytes: a stream that starts at
+ * bit 0 and ends with the end marker and its padding, whose matches may reach back into the channel's history.  Afterwards
+ * the channel's history is the last min(2047, hist_len + len) bytes of history | packet.
+ *
+ * d_status[b] (d_status may be NULL) receives the reference's LZS_C_STATUS_* bits: END_MARKER | INPUT_FINISHED |
+ * INPUT_STARVED for a whole packet.  If out_cap is too small the output is cut there, as lzs_compress() cuts it; the history
+ * still advances, and the status has NO_OUTPUT_BUFFER_SPACE instead of END_MARKER -- the peer cannot follow, so reset the
+ * channel.  A slot with hist_len > 2047 is not a state: that packet gets ERROR and d_out_len[b] = 0, and nothing else of it
+ * is written or changed.
+ *
+ * A CHANNEL MAY APPEAR AT MOST ONCE PER CALL (packets of one channel depend on each other: give them in successive calls).
+ * If one repeats, what that channel's packets and state receive is undefined; the other channels are not affected.
+ *
+ * Arguments are checked before the device is asked (LZS_E_ARG): d_states and d_out_len must be given, d_states 4-byte
+ * aligned, d_out_len must not be the array d_in_len, npackets at most LZS_CHANNELS_MAX.  Without a device a valid call
+ * returns LZS_E_NO_DEVICE.  No allocation, no synchronisation: safe to capture into a hipGraph -- with the caveat of the
+ * batch calls of lzs_batch.h: once per device and process the library asks the device how it orders same-address LDS
+ * exchanges (a 0.1 ms kernel on a stream of its own, at the first entry into the library on that device, which allocates and
+ * waits; `hip_stream` is not touched by it).  Call lzs_backend_info() first if the very first call is to be captured.
+ */
+int lzs_compress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                 const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                 const uint32_t *d_channel, void *d_states, uint8_t *d_status,
+                                 size_t npackets, void *hip_stream);
+
+/*
+ * Device-pointer channel decompression: the same arguments, LZS_D_STATUS_* bits.  Each packet is decoded until its first end
+ * marker, the end of its bytes or out_cap, with copies reaching into the channel's history; for a well-formed packet the
+ * output is what lzs_decompress_incremental() gives on that channel's parameter block.  Bytes after the end marker are
+ * ignored.  Status: END_MARKER; NO_OUTPUT_BUFFER_SPACE when out_cap stopped it first (also when a copy was cut at out_cap,
+ * whatever follows it: the output is not the packet's, so reset the channel); INPUT_STARVED | INPUT_FINISHED when the bits
+ * ran out first.  Afterwards the channel's history is the last min(2047, hist_len + produced) bytes of history | output.
+ * A slot with hist_len > 2047 gets ERROR and d_out_len[b] = 0, as above.
+ *
+ * Differences from the reference: a packet that stops early keeps no partial token -- only the history carries over (RFC 1974
+ * packets are whole).  An offset reaching before the channel's history reads zeros; a long offset of 0 follows the rule of
+ * lzs_decompress_batch_device.  Malformed input never makes a packet read or write outside its own slots
+ * and its channel's state.
+ */
+int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                   const uint32_t *d_channel, void *d_states, uint8_t *d_status,
+                                   size_t npackets, void *hip_stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* LZS_MI355X_LZS_CHANNELS_H */

@@ -43,6 +43,7 @@ _lib = None
 _vp, _sz, _u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
 _BATCH_DEV = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp]
 _BATCH_HOST = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz]
+_CHANNELS_DEV = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp]
 
 
 def lib() -> ctypes.CDLL:
@@ -89,6 +90,10 @@ def lib() -> ctypes.CDLL:
         L.lzs_simple_compress_init.restype, L.lzs_simple_compress_init.argtypes = None, [_vp]
         L.lzs_simple_compress_incremental.restype, L.lzs_simple_compress_incremental.argtypes = _sz, [_vp, ctypes.c_bool]
         L.lzs_decompress_incremental.restype, L.lzs_decompress_incremental.argtypes = _sz, [_vp]
+        for name in ("lzs_compress_channels_device", "lzs_decompress_channels_device"):
+            if hasattr(L, name):        # (an older build named by LZS_LIBRARY, for A/B runs, has none)
+                f = getattr(L, name)
+                f.restype, f.argtypes = ctypes.c_int, _CHANNELS_DEV
         _lib = L
     return _lib
 
@@ -378,3 +383,120 @@ def incremental_compress(data: bytes, in_chunk: int, out_chunk: int, simple: boo
         if calls > 32 * (len(data) // max(1, min(in_chunk, out_chunk)) + 64):
             raise LzsError(LZS_E_HIP, "lzs_compress_incremental makes no progress")
     return bytes(out)
+
+
+# ------------------------------------------- many channels, one packet each (lzs_channels.h)
+CHANNEL_STATE_BYTES = 2112          # LZS_CHANNEL_STATE_BYTES: uint32 hist_len, reserved to 64, hist[2048]
+
+
+def new_channel_states(n: int, device=None):
+    """``n`` new channels: a zeroed CUDA uint8 tensor [n, CHANNEL_STATE_BYTES] (an all-zero slot is a fresh
+    lzs_compress_init_full() / lzs_decompress_init(); compressor and decompressor each need their own array)."""
+    import torch
+    return torch.zeros((n, CHANNEL_STATE_BYTES), dtype=torch.uint8, device="cuda" if device is None else device)
+
+
+def _device_channels(fn, x, in_len, channels, states, out_cap, out, out_len, status, stream):
+    import torch
+    assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.stride(1) == 1, \
+        "packets must be a CUDA uint8 tensor [npackets, stride] with contiguous rows"
+    nb = x.shape[0]
+    assert states.is_cuda and states.dtype == torch.uint8 and states.dim() == 2 and states.is_contiguous() \
+        and states.shape[1] == CHANNEL_STATE_BYTES, "states must be a contiguous CUDA uint8 tensor [nchannels, CHANNEL_STATE_BYTES]"
+    if channels is None:
+        assert states.shape[0] >= nb, "without channel ids packet b uses channel b"
+    else:
+        assert channels.is_cuda and channels.dtype == torch.int32 and channels.numel() == nb and channels.is_contiguous()
+    if out is None:
+        out = torch.empty((nb, (max(out_cap, 1) + 15) // 16 * 16), dtype=torch.uint8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.shape[0] == nb and out.stride(1) == 1 and out.shape[1] >= out_cap
+    if out_len is None:
+        out_len = torch.empty(nb, dtype=torch.int32, device=x.device)
+    assert out_len.is_cuda and out_len.dtype == torch.int32 and out_len.numel() == nb
+    if status is None:
+        status = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.numel() == nb
+    if in_len is not None:
+        assert in_len.is_cuda and in_len.dtype == torch.int32 and in_len.numel() == nb
+    _check(fn(out.data_ptr(), out.stride(0) if nb > 1 else out.shape[1], out_cap, out_len.data_ptr(),
+              x.data_ptr(), x.stride(0) if nb > 1 else x.shape[1],
+              None if in_len is None else in_len.data_ptr(), x.shape[1],
+              None if channels is None else channels.data_ptr(), states.data_ptr(), status.data_ptr(), nb,
+              _stream_handle(stream)))
+    return out, out_len, status
+
+
+def compress_channels(x, in_len, channels, states, out_capacity: Optional[int] = None, out=None, out_len=None, status=None,
+                      stream=None):
+    """lzs_compress_channels_device(): row b of ``x`` (CUDA uint8 [npackets, stride], ``in_len[b]`` bytes or whole rows) is
+    one packet on channel ``channels[b]`` (CUDA int32, or None: channel b), compressed with that channel's history in
+    ``states`` (new_channel_states) as lzs_compress_incremental(add_end_marker) would, and the history advanced.  A channel
+    may appear at most once per call (ChannelCodec splits repeated ids).  Asynchronous on ``stream``.
+    Returns (slots [npackets, slot_stride] uint8, lengths int32, status uint8: LZS_C_STATUS_* bits)."""
+    cap = compressed_max(x.shape[1]) if out_capacity is None else out_capacity
+    return _device_channels(lib().lzs_compress_channels_device, x, in_len, channels, states, cap, out, out_len, status, stream)
+
+
+def decompress_channels(x, in_len, channels, states, out_capacity: int, out=None, out_len=None, status=None, stream=None):
+    """lzs_decompress_channels_device(): the reverse, with the decompressor's own ``states``; arguments as
+    compress_channels, status LZS_D_STATUS_* bits (END_MARKER for a whole packet)."""
+    return _device_channels(lib().lzs_decompress_channels_device, x, in_len, channels, states, out_capacity, out, out_len,
+                            status, stream)
+
+
+def _occurrence_rank(channels) -> np.ndarray:
+    """rank[b] = how many packets before b have the same channel id."""
+    ch = np.asarray(channels, dtype=np.int64).reshape(-1)
+    n = ch.size
+    order = np.argsort(ch, kind="stable")
+    srt = ch[order]
+    first = np.ones(n, dtype=bool)
+    first[1:] = srt[1:] != srt[:-1]
+    start = np.maximum.accumulate(np.where(first, np.arange(n), 0)) if n else np.zeros(0, dtype=np.int64)
+    rank = np.empty(n, dtype=np.int64)
+    rank[order] = np.arange(n) - start
+    return rank
+
+
+class ChannelCodec:
+    """``nchannels`` channels with a compressor and a decompressor state array each (``enc_states``, ``dec_states``).
+    Unlike the raw calls, a batch may name a channel more than once: it is split into launches of distinct ids, in order
+    (launch k takes every channel's k-th packet), so that packet k of a channel always sees its packets before k."""
+
+    def __init__(self, nchannels: int, device=None):
+        self.enc_states = new_channel_states(nchannels, device)
+        self.dec_states = new_channel_states(nchannels, device)
+
+    def _run(self, call, states, x, in_len, channels, out_cap, stream):
+        import torch
+        ids = np.asarray(channels, dtype=np.int64).reshape(-1)
+        nb = x.shape[0]
+        assert ids.size == nb and (nb == 0 or (ids.min() >= 0 and ids.max() < states.shape[0])), "channel ids out of range"
+        out = torch.empty((nb, (max(out_cap, 1) + 15) // 16 * 16), dtype=torch.uint8, device=x.device)
+        out_len = torch.empty(nb, dtype=torch.int32, device=x.device)
+        status = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        rank = _occurrence_rank(ids)
+        for r in range(int(rank.max()) + 1 if nb else 0):
+            sel = np.nonzero(rank == r)[0]
+            if sel.size == nb:       # every id once: one launch over the caller's own tensors
+                call(x, in_len, torch.from_numpy(ids.astype(np.int32)).to(x.device), states, out_cap, out, out_len, status, stream)
+                break
+            idx = torch.from_numpy(sel).to(x.device)
+            o, ol, st = call(x.index_select(0, idx).contiguous(), None if in_len is None else in_len.index_select(0, idx).contiguous(),
+                             torch.from_numpy(ids[sel].astype(np.int32)).to(x.device), states, out_cap, None, None, None, stream)
+            out[idx, :o.shape[1]] = o
+            out_len[idx] = ol
+            status[idx] = st
+        return out, out_len, status
+
+    def compress(self, x, in_len, channels, out_capacity: Optional[int] = None, stream=None):
+        """Row b of ``x`` on channel ``channels[b]`` (a host sequence; ids may repeat).  Returns (slots, lengths, status)."""
+        cap = compressed_max(x.shape[1]) if out_capacity is None else out_capacity
+        return self._run(lambda *a: compress_channels(*a[:4], out_capacity=a[4], out=a[5], out_len=a[6], status=a[7], stream=a[8]),
+                         self.enc_states, x, in_len, channels, cap, stream)
+
+    def decompress(self, x, in_len, channels, out_capacity: int, stream=None):
+        """The reverse on the decompressor states.  Returns (out, lengths, status)."""
+        return self._run(lambda *a: decompress_channels(*a[:4], out_capacity=a[4], out=a[5], out_len=a[6], status=a[7], stream=a[8]),
+                         self.dec_states, x, in_len, channels, out_capacity, stream)
+

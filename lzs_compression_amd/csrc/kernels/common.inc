@@ -20,6 +20,9 @@ struct __attribute__((aligned(16))) WaveLds {
     uint32_t stage[kStage / 4];
 };
 
+// A channel's state slot (include/lzs/lzs_channels.h): uint32 hist_len, reserved to byte 64, then 2048 bytes of history.
+constexpr uint32_t kChanStateBytes = 2112u, kChanHistAt = 64u;
+
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // A value the optimiser may not look through (keeps a select a select, a compare a compare).

@@ -63,6 +63,8 @@ constexpr uint32_t kRefillUnit  = 128u * kW;      // bytes a REFILL stores at a 
 //   LZS_WGV_PACK_BY_CHUNK           PACK formats a wave's two chunks one after the other (default: in one pass when their
 //                                   tokens are no more than 64 together)
 //   LZS_WGV_SEGMENTS                the variant also serves lzs_compress_segments_kernel
+//   LZS_WGV_CHANNELS                the inclusion serves lzs_compress_channels_wg_kernel alone: the job reads a two-source view,
+//                                   [a channel's history | the packet] (wg_view_* below), and nothing else is compiled in it
 //   LZS_WGV_LEAN                    constants of SEARCH as literals (2.5 cycles an instruction) instead of registers (2): the
 //                                   variant that runs six workgroups per CU has 80 vector registers and not one more
 //   LZS_WGV_PRIO                    wave priorities by phase (s_setprio): SEARCH 0, CHAIN's two waves 3, the other phases 2
@@ -756,7 +758,49 @@ struct WgJob {
     uint32_t *open_info;            // a piece of a stream that will go on (lzs_compress_incremental):
                                     // {offset, start} of the job's last token if that is a match
                                     // reaching the end of the data so far (n), {0, 0} otherwise; or null
+#ifdef LZS_WGV_CHANNELS
+    const uint8_t *hist;            // the view: positions [0, hlen) are hist[], [hlen, n) are src[0 .. n - hlen)
+    uint32_t hlen;
+    uint8_t *status;                // LZS_C_STATUS_* of the packet
+#endif
 };
+
+#ifdef LZS_WGV_CHANNELS
+// The two-source view of a channel's job: byte q of [history | packet], zero from n on.
+__device__ __forceinline__ uint32_t wg_view_byte(const WgJob &job, uint32_t q)
+{
+    return q < job.hlen ? job.hist[q] : (q < job.n ? job.src[q - job.hlen] : 0u);
+}
+// 16 bytes of the view at p (a multiple of 16: REFILL's and OPEN's ring loads), zero from n on
+__device__ __forceinline__ uint4 wg_view_load16(const WgJob &job, uint32_t p)
+{
+    const uint32_t h = job.hlen;
+    if (p + 16u <= h) return load16(job.hist, p, h, ((uintptr_t)job.hist & 15u) == 0, ((uintptr_t)job.hist & 3u) == 0);
+    if (p >= h) {
+        if (p >= job.n) return make_uint4(0u, 0u, 0u, 0u);
+        const uint8_t *q = job.src + (p - h);
+        return load16(q, 0u, job.n - p, ((uintptr_t)q & 15u) == 0, ((uintptr_t)q & 3u) == 0);
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t k = 0; k < 16u; k++) w[k >> 2] |= wg_view_byte(job, p + k) << (8u * (k & 3u));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// 16 bytes of the view at any q with q + 16 <= n (OPEN's comparisons)
+__device__ __forceinline__ u32x4 wg_view_read16(const WgJob &job, uint32_t q)
+{
+    u32x4 v;
+    if (q >= job.hlen) {
+        __builtin_memcpy(&v, job.src + (q - job.hlen), 16);
+    } else if (q + 16u <= job.hlen) {
+        __builtin_memcpy(&v, job.hist + q, 16);
+    } else {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        for (uint32_t k = 0; k < 16u; k++) w[k >> 2] |= wg_view_byte(job, q + k) << (8u * (k & 3u));
+        v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    }
+    return v;
+}
+#endif
 
 __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgOut o)
 {
@@ -769,6 +813,9 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
     const uint32_t head0 = o.head;
     const bool src16   = ((uintptr_t)src & 15u) == 0;
     const bool src4    = ((uintptr_t)src & 3u) == 0;
+#ifdef LZS_WGV_CHANNELS
+    (void)src16; (void)src4;                                   // (the view loads by its own rules)
+#endif
 
     for (uint32_t i = tid; i < (kNo3 ? 1u : kWgHead3); i += kWgThreads) L.head3[i] = ~0u;
     for (uint32_t i = tid; i < kWgHead2; i += kWgThreads) L.head2[i] = ~0u;
@@ -782,7 +829,7 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
     uint32_t c = job.c0;         // start of the next token
     uint32_t loaded = job.w0;    // ring holds [loaded-4096, loaded)
     uint32_t next = job.w0;      // next batch of 64 positions to build
-#ifndef LZS_NO_PREFETCH
+#if !defined(LZS_NO_PREFETCH) && !defined(LZS_WGV_CHANNELS)
     // The half KiB a REFILL stores is requested one pool earlier (every thread asks for the 16
     // bytes its lane & 31 would store -- an unconditional bounded buffer load, straight into
     // `pre`, eight requests for the same bytes -- so that nobody stands at the barrier behind a
@@ -835,7 +882,9 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
                 // by VALU issue, and four waves computing addresses for 4 bytes each cost four times this
                 if (wave == ((loaded / kRefillUnit) & (kW - 1u)) && lane < kRefillUnit / 16u) {
                     const uint32_t p = loaded + 16 * lane;
-#ifndef LZS_NO_PREFETCH
+#if defined(LZS_WGV_CHANNELS)     // (no prefetch: the view has two sources)
+                    const uint4 v = wg_view_load16(job, p);
+#elif !defined(LZS_NO_PREFETCH)
                     const uint4 v = pre_at == loaded ? make_uint4(pre.x, pre.y, pre.z, pre.w) : load16(src, p, n, src16, src4);
 #else
                     const uint4 v = load16(src, p, n, src16, src4);
@@ -846,7 +895,7 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
                 }
                 loaded += kRefillUnit;
             }
-#ifndef LZS_NO_PREFETCH
+#if !defined(LZS_NO_PREFETCH) && !defined(LZS_WGV_CHANNELS)
             if (src16 && loaded + kRefillUnit <= n) {
                 pre = __builtin_amdgcn_raw_buffer_load_b128(src_rsrc, (int)(loaded + 16u * (lane & (kRefillUnit / 16u - 1u))), 0, 0);
                 pre_at = loaded;
@@ -1183,14 +1232,23 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
                     uint32_t eq = 0;
                     if (mine == 16u) {
                         u32x4 va, vb;
+#ifdef LZS_WGV_CHANNELS
+                        va = wg_view_read16(job, q);
+                        vb = wg_view_read16(job, q - off);
+#else
                         __builtin_memcpy(&va, src + q, 16);
                         __builtin_memcpy(&vb, src + q - off, 16);
+#endif
                         const uint32_t e = lcp12(va.x ^ vb.x, va.y ^ vb.y, va.z ^ vb.z);
                         const uint32_t x3 = va.w ^ vb.w;
                         const uint32_t e3 = x3 ? (uint32_t)__builtin_ctz(x3) >> 3 : 4u;
                         eq = e < 12u ? e : 12u + e3;
                     } else {
+#ifdef LZS_WGV_CHANNELS
+                        while (eq < mine && wg_view_byte(job, q + eq) == wg_view_byte(job, q + eq - off)) eq++;
+#else
                         while (eq < mine && src[q + eq] == src[q + eq - off]) eq++;
+#endif
                     }
                     const uint64_t stops = __builtin_amdgcn_ballot_w64(eq < 16u);
                     const uint32_t l = stops ? (uint32_t)__builtin_ctzll(stops) : 64u;
@@ -1247,7 +1305,11 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
                     const uint32_t from = upto - loaded > kWgRing ? upto - kWgRing : loaded;
                     const uint32_t p = from + 16u * tid;
                     if (p < upto) {
+#ifdef LZS_WGV_CHANNELS
+                        const uint4 v = wg_view_load16(job, p);
+#else
                         const uint4 v = load16(src, p, n, src16, src4);
+#endif
                         const uint32_t at = (p & kWgRingMask) >> 2;
                         *reinterpret_cast<uint4 *>(&L.ring[at]) = v;
                         if (at == 0) *reinterpret_cast<uint4 *>(&L.ring[kWgRingWords]) = v;
@@ -1295,9 +1357,14 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
         }
         const uint32_t total = o.flushed + nbytes;
         if (job.out_len && lane == 0) *job.out_len = total < o.cap ? total : o.cap;
+#ifdef LZS_WGV_CHANNELS
+        // all of the packet was taken; cut at the capacity, the stream lacks its end (lzs_compress_incremental's flags)
+        if (job.status && lane == 0) *job.status = (uint8_t)(total <= o.cap ? 0x07u : 0x0Bu);
+#endif
     }
 }
 
+#ifndef LZS_WGV_CHANNELS
 #ifdef LZS_WGV_WAVES          // (waves per SIMD the register allocation is held to: an occupancy experiment of round 6)
 __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(LZS_WGV_WAVES, LZS_WGV_WAVES)))
 #else
@@ -1334,6 +1401,7 @@ void lzs_compress_blocks_wg_kernel(uint8_t *__restrict__ out, size_t out_stride,
     o.limit = out_cap; o.ored = false;
     wg_compress_job(L, job, o);
 }
+#endif  // !LZS_WGV_CHANNELS
 
 // One long stream cut into segments of `seg` bytes (a multiple of 64), one workgroup each.  The
 // search is a pure function of (input, position), so a segment only needs the 2047 bytes before it
@@ -1401,6 +1469,68 @@ void lzs_compress_segments_kernel(uint8_t *__restrict__ slots, size_t slot_strid
 
 #endif  // LZS_WGV_SEGMENTS
 
+// Many channels, one packet each (include/lzs/lzs_channels.h, DESIGN.md 3.10): packet b is compressed on channel
+// c = channel[b] as lzs_compress_incremental(add_end_marker) would on that channel's parameter block -- one job over the view
+// [history | packet] with w0 = 0 (the chains are built over the history too), c0 = hlen (tokens start in the packet), the
+// end marker at n.  Then the channel's history becomes the last min(2047, n) bytes of the view: read by every thread into the
+// LDS ring (free once the job is done) BEFORE the barrier, written to the slot after it -- the new history overlaps the old.
+#ifdef LZS_WGV_CHANNELS
+#ifdef LZS_WGV_WAVES
+__global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(LZS_WGV_WAVES, LZS_WGV_WAVES)))
+#else
+__global__ __launch_bounds__(kWgThreads)
+#endif
+void lzs_compress_channels_wg_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
+                                     uint32_t *__restrict__ out_len,
+                                     const uint8_t *__restrict__ in, size_t in_stride,
+                                     const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
+                                     const uint32_t *__restrict__ channel, uint8_t *__restrict__ states,
+                                     uint8_t *__restrict__ status, uint32_t npackets)
+{
+    __shared__ BlkLds L;
+    const uint32_t b = blockIdx.x;
+    if (b >= npackets) return;
+    const uint32_t ch = channel ? channel[b] : b;
+    uint8_t *const st = states + (size_t)ch * kChanStateBytes;
+    const uint32_t h = uniform(*reinterpret_cast<const uint32_t *>(st));
+    const uint32_t len = in_len ? in_len[b] : in_len_uniform;
+    if (h > kWindow) {                                         // not a state: nothing is written, nothing changes
+        if (threadIdx.x == 0) { out_len[b] = 0; if (status) status[b] = 0x10u; }
+        return;
+    }
+    WgJob job;
+    job.src = in + (size_t)b * in_stride;
+    job.hist = st + kChanHistAt; job.hlen = h;
+    job.n = h + len;
+    job.cend = job.n; job.c0 = h; job.w0 = 0; job.last = true;
+    job.out_len = out_len + b; job.exit_pos = nullptr; job.nbits = nullptr; job.open_info = nullptr;
+    job.status = status ? status + b : nullptr;
+    WgOut o;
+    o.flushed = 0; o.head = 0;
+    o.dst = out + (size_t)b * out_stride;
+    o.cap = out_cap;
+    o.aligned4 = ((uintptr_t)o.dst & 3u) == 0;
+    o.limit = out_cap; o.ored = false;
+    wg_compress_job(L, job, o);
+    // ---- the new history: hist[0, H) = view[n - H, n), hist[H, 2048) = 0 (the decoder writes the same bytes)
+    __syncthreads();                                           // every read of the ring and of the old history is done
+    const uint32_t H = job.n < kWindow ? job.n : kWindow, base = job.n - H;
+    static_assert(kWgRingWords >= 512u && kWgThreads * 2u >= 512u, "the 2048 bytes of history are staged in the ring");
+    for (uint32_t w = threadIdx.x; w < 512u; w += kWgThreads) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t i = 4u * w + k;
+            if (i < H) v |= wg_view_byte(job, base + i) << (8u * k);
+        }
+        L.ring[w] = v;
+    }
+    __syncthreads();
+    uint32_t *const hist = reinterpret_cast<uint32_t *>(st + kChanHistAt);
+    for (uint32_t w = threadIdx.x; w < 512u; w += kWgThreads) hist[w] = L.ring[w];
+    if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(st) = H;
+}
+#endif  // LZS_WGV_CHANNELS
+
 #undef LZS_WGV_HEAD3
 #undef LZS_WGV_HEAD2
 #undef LZS_WGV_SUBSTEPS
@@ -1408,6 +1538,7 @@ void lzs_compress_segments_kernel(uint8_t *__restrict__ slots, size_t slot_strid
 #undef LZS_HOPS_HERE
 #undef LZS_WGV_CHAIN_SAFE
 #undef LZS_WGV_SEGMENTS
+#undef LZS_WGV_CHANNELS
 #undef LZS_WGV_PACK_BY_CHUNK
 #undef LZS_WGV_PRIO
 #undef LZS_WGV_LEAN

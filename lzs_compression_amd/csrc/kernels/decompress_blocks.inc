@@ -807,13 +807,22 @@ typedef __attribute__((address_space(3))) uint8_t dec_lds_u8_t;
 __device__ __forceinline__ uint32_t dec_lds_at(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p; }
 __device__ __forceinline__ dec_lds_u8_t *dec_lds_byte(uint32_t at) { return (dec_lds_u8_t *)(uintptr_t)at; }
 
+// CHAN (lzs_decompress_channels_grp_kernel): stream b is a packet of channel channel[b] (b if NULL) -- the channel's history is
+// put into the part of the stream's window before output byte 0 (where the plain decoder reads zeros) and the last 2047 bytes
+// of history | output go back to the state slot at the end.
+struct DecChan {
+    uint8_t *states = nullptr;
+    const uint32_t *channel = nullptr;
+    uint8_t *status = nullptr;
+};
+
 // The same decoder with its flags as masks: the one-word feed with one token a trip or two (the 96-bit form stays above).
-template <bool TWO, bool WIDE, bool CONCAT>
+template <bool TWO, bool WIDE, bool CONCAT, bool CHAN = false>
 __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
                                       uint32_t *__restrict__ out_len,
                                       const uint8_t *__restrict__ in, size_t in_stride,
                                       const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
-                                      uint32_t nblocks, uint32_t concat_arg, uint32_t per_wave)
+                                      uint32_t nblocks, uint32_t concat_arg, uint32_t per_wave, DecChan ch = DecChan())
 {
     const uint32_t lane = threadIdx.x;
     const uint32_t g = lane / kDecLanes, j = lane % kDecLanes;
@@ -823,7 +832,15 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     for (uint32_t i = lane; i < sizeof(L.ring) / 16u; i += 64u) reinterpret_cast<uint4 *>(&L.ring[0][0])[i] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
 
-    const bool live = b < nblocks && g < per_wave;
+    uint8_t *cst = nullptr;                                        // CHAN: the stream's state slot ...
+    uint32_t hlen = 0;                                             // ... and its history's length (> 2047: not a state)
+    if constexpr (CHAN) {
+        if (b < nblocks && g < per_wave) {
+            cst = ch.states + (size_t)(ch.channel ? ch.channel[b] : b) * kChanStateBytes;
+            hlen = *reinterpret_cast<const uint32_t *>(cst);
+        }
+    }
+    const bool live = b < nblocks && g < per_wave && (!CHAN || hlen <= kWindow);
     const uint32_t bb = live ? b : 0u;
     uint8_t *ring8 = reinterpret_cast<uint8_t *>(L.ring[g]);
     uint8_t *dummy8 = reinterpret_cast<uint8_t *>(&L.dummy[lane]);
@@ -832,6 +849,19 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint8_t *dst       = out + (size_t)bb * out_stride;
     const bool dst16   = ((uintptr_t)dst & 15u) == 0;
     const uint32_t cap = live ? out_cap : 0u;
+    if constexpr (CHAN) {
+        // history byte i is output byte i - hlen: window position kDecRing - hlen + i, which no output reaches before that
+        // byte is more than 2047 behind (the argument of the zeros above)
+        if (live) {
+            const uint32_t *hist = reinterpret_cast<const uint32_t *>(cst + kChanHistAt);
+            for (uint32_t w = j; w < 512u; w += kDecLanes) {
+                const uint32_t v = hist[w];
+                for (uint32_t k = 0; k < 4u; k++)
+                    if (4u * w + k < hlen) ring8[kDecRing - hlen + 4u * w + k] = (uint8_t)(v >> (8u * k));
+            }
+        }
+        __syncthreads();
+    }
 
     // ---- the input as aligned words: word k holds stream bytes [4k - skew, 4k - skew + 4).  A
     // group takes 16 x kDecLanes bytes at a time: lane j holds words 4j .. 4j + 3 of the current
@@ -905,6 +935,8 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint32_t m_ext = 0;                                            // "a length nibble follows", as a mask
     uint32_t cpos = 0, fpos = 0;                                   // count and flushed modulo kDecRing
     uint32_t m_done = live ? 0u : ~0u;                             // the stream has stopped, as a mask
+    uint32_t m_eos = 0u;                                           // (CHAN) ... at an end marker
+    uint32_t m_cut = 0u;                                           // (CHAN) a copy lost bytes to the room: no end marker counts after it
     // overlapping copies replicate with period off: byte idx of a step comes from byte idx mod off.  Lane j's
     // bytes are j and j + 8: a 3-bit entry per off = 0 .. 8 (0 and 8 and more: j itself), a 4-bit one per off = 0 .. 15
     uint32_t mod_lo = 0; uint64_t mod_hi = 0;
@@ -1023,6 +1055,13 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         const uint32_t m_stop = m_lt(have, need) | m_z(room);
         const uint32_t m_go = m_nor(m_done, m_stop);
         const uint32_t m_endm = m_mat & m_zoff & m_short;         // end marker (:255-260 / file rule :564-576)
+        // (CHAN) the end marker is reached; it needs no room, so a full output may end at it -- also behind the closing
+        // length nibble 0 of a copy that filled the output.  Not after a copy the room cut short (m_cut): its token was
+        // consumed whole but not all of its bytes were written, so the output is not the packet's
+        if constexpr (CHAN) {
+            const uint32_t m_nib0_end = m_ext & m_z(e) & m_z(((top << 4) >> 23) ^ 0x180u) & ~m_lt(have, 13u);
+            m_eos |= m_andnot((m_endm & ~m_lt(have, 9u)) | m_nib0_end, m_done | m_cut);
+        }
         uint32_t consume = m_sel(m_lit, (kv << 3) + kv, need);
         // file rule: after an end marker drop the pad bits up to the byte boundary and go on
         if (CONCAT) consume += m_endm & ((have - used) & 7u);
@@ -1032,6 +1071,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         const uint32_t off_next = m_andnot(off_now, m_andnot(m_mat & m_zoff, m_short));
         const uint32_t m_ext_next = m_sel(m_ext, m_lt(14u, e), m_copying & m_lt(7u, len));
         const uint32_t m = min16(copy_len, room);
+        if constexpr (CHAN) m_cut |= m_andnot(m_go, m_lit) & m_lt(m, copy_len);   // (a run of literals is cut unread, a copy is not)
         const uint32_t nA = m_sel(m_lit, kv, m) & m_go;           // bytes of this step's (first) token
         // ---- TWO: a second token in the same trip (see lzs_decompress_blocks_grp for when; two of its conditions follow
         // from the others -- a second offset of 0 cannot be >= both lengths together, and a first copy cut by the room
@@ -1137,6 +1177,31 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         dst[i] = ring8[r];
     }
     if (live && j == 0u) out_len[b] = count;
+    if constexpr (CHAN) {
+        if (live) {
+            // the new history: hist[0, H) = the last H bytes of history | output (output byte count - H + i is at window
+            // position cpos - H + i), hist[H, 2048) = 0 -- the bytes the compressor writes
+            const uint32_t H = min(hlen + count, kWindow);
+            uint32_t *hist = reinterpret_cast<uint32_t *>(cst + kChanHistAt);
+            for (uint32_t w = j; w < 512u; w += kDecLanes) {
+                uint32_t v = 0;
+                for (uint32_t k = 0; k < 4u; k++) {
+                    const uint32_t i = 4u * w + k;
+                    uint32_t r = cpos + kDecRing - H + i;
+                    r = r >= kDecRing ? r - kDecRing : r;
+                    if (i < H) v |= (uint32_t)ring8[r] << (8u * k);
+                }
+                hist[w] = v;
+            }
+            if (j == 0u) {
+                *reinterpret_cast<uint32_t *>(cst) = H;
+                if (ch.status) ch.status[b] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
+            }
+        } else if (cst && j == 0u) {                               // not a state: nothing is written, nothing changes
+            out_len[b] = 0;
+            if (ch.status) ch.status[b] = 0x10u;
+        }
+    }
 }
 
 template <bool CONCAT>
@@ -1175,4 +1240,32 @@ void lzs_decompress_blocks_grp_kernel(uint8_t *__restrict__ out, size_t out_stri
     else           lzs_decompress_blocks_grp<false, false, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
 #endif
 #endif
+}
+
+// Many channels, one packet each (include/lzs/lzs_channels.h, DESIGN.md 3.10): lzs_decompress_blocks_grp_kernel<false> with every
+// stream's window starting with its channel's history, and the history carried back.
+__global__ __launch_bounds__(64)
+void lzs_decompress_channels_grp_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
+                                        uint32_t *__restrict__ out_len,
+                                        const uint8_t *__restrict__ in, size_t in_stride,
+                                        const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
+                                        const uint32_t *__restrict__ channel, uint8_t *__restrict__ states,
+                                        uint8_t *__restrict__ status, uint32_t npackets, uint32_t per_wave)
+{
+    __shared__ DecGroupLds L;
+    // (the form by the wavefront's ratio of input to room, as lzs_decompress_blocks_grp_kernel picks it)
+    uint64_t total = 0, blocks = 0;
+    const uint32_t b0 = blockIdx.x * per_wave;
+    for (uint32_t g = 0; g < per_wave && b0 + g < npackets; g++) {
+        total += in_len ? in_len[b0 + g] : in_len_uniform;
+        blocks++;
+    }
+    const uint64_t full = blocks * (uint64_t)out_cap;
+    const bool two = uniform((4ull * total > full && 10ull * total < 9ull * full) ? 1u : 0u) != 0u;
+    const bool wide = uniform(10ull * total >= 9ull * full ? 1u : 0u) != 0u;
+    DecChan ch;
+    ch.states = states; ch.channel = channel; ch.status = status;
+    if (two)       lzs_decompress_blocks_grp_m<true, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
+    else if (wide) lzs_decompress_blocks_grp_m<false, true, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
+    else           lzs_decompress_blocks_grp_m<false, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
 }

@@ -1,0 +1,49 @@
+/*
+ * lzs_channels.c -- many channels, one packet each (include/lzs/lzs_channels.h): the arguments are checked here, the
+ * kernels (lzs_compress_channels_wg_kernel, lzs_decompress_channels_grp_kernel in lzs_kernels.hip) do the rest.
+ */
+#include "lzs_internal.h"
+#include "lzs/lzs_channels.h"
+
+typedef int (*channel_launch_fn)(void *, size_t, uint32_t, uint32_t *, const void *, size_t, const uint32_t *, uint32_t,
+                                 const uint32_t *, void *, uint8_t *, uint32_t, void *);
+
+static int device_channels(const char *who, channel_launch_fn launch, void *d_out, size_t out_stride, size_t out_cap,
+                           uint32_t *d_out_len, const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                           const uint32_t *d_channel, void *d_states, uint8_t *d_status, size_t npackets, void *stream)
+{
+    if (npackets == 0) return LZS_OK;
+    if (npackets > LZS_CHANNELS_MAX) return fail(LZS_E_ARG, "%s: too many packets (%zu)", who, npackets);
+    if (!d_out_len) return fail(LZS_E_ARG, "%s: out_len is NULL", who);
+    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
+    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
+    if (!d_in && (in_len || d_in_len)) return fail(LZS_E_ARG, "%s: input is NULL", who);
+    if (!d_out && out_cap) return fail(LZS_E_ARG, "%s: output is NULL", who);
+    if (in_len > LZS_BLOCK_MAX) return fail(LZS_E_ARG, "%s: packet of %zu bytes exceeds LZS_BLOCK_MAX", who, in_len);
+    if (d_in_len && (const void *)d_in_len == (const void *)d_out_len)
+        return fail(LZS_E_ARG, "%s: d_out_len and d_in_len are the same array", who);
+    int rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const uint32_t cap32 = out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap;
+    const int e = launch(d_out, out_stride, cap32, d_out_len, d_in, in_stride, d_in_len, (uint32_t)in_len, d_channel, d_states,
+                         d_status, (uint32_t)npackets, stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                 const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                 const uint32_t *d_channel, void *d_states, uint8_t *d_status,
+                                 size_t npackets, void *hip_stream)
+{
+    return device_channels("lzs_compress_channels_device", lzs_hip_launch_compress_channels, d_out, out_stride, out_cap,
+                           d_out_len, d_in, in_stride, d_in_len, in_len, d_channel, d_states, d_status, npackets, hip_stream);
+}
+
+int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                   const uint32_t *d_channel, void *d_states, uint8_t *d_status,
+                                   size_t npackets, void *hip_stream)
+{
+    return device_channels("lzs_decompress_channels_device", lzs_hip_launch_decompress_channels, d_out, out_stride, out_cap,
+                           d_out_len, d_in, in_stride, d_in_len, in_len, d_channel, d_states, d_status, npackets, hip_stream);
+}

@@ -147,6 +147,15 @@ typedef struct {
 } lzs_dec_resume_t;
 int lzs_hip_launch_decode_resume(lzs_dec_resume_t *d_state, const void *d_in, uint32_t n,
                                  void *d_out, uint32_t cap, void *stream);
+/* Many channels, one packet each (include/lzs/lzs_channels.h; lzs_channels.c checks the arguments): packet b is compressed /
+ * decompressed on channel d_channel[b] (b if NULL) with the history in that channel's LZS_CHANNEL_STATE_BYTES-byte slot of
+ * d_states, which is advanced; d_status[b] (or NULL) receives the LZS_C_STATUS_* / LZS_D_STATUS_* bits. */
+int lzs_hip_launch_compress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                     const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                                     const uint32_t *d_channel, void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
+int lzs_hip_launch_decompress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                       const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                                       const uint32_t *d_channel, void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
 int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
                            size_t slot_stride, const uint32_t *d_len, uint32_t nblocks,
                            void *stream);

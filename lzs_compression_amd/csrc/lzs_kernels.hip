@@ -55,51 +55,25 @@ namespace {
 // order-independent CHAIN for a device that fails the LDS ordering check, and the two a block's class may ask for.
 namespace wgv_text {
 #define LZS_WGV_SEGMENTS 1
-#define LZS_WGV_PRIO 1
-#ifndef LZS_EXP_TEXT_EXIT16
-#define LZS_WGV_EXIT8 1
-#endif
-// Round 6: SIX workgroups per CU.  A sixth workgroup is +8.9 % at equal work (profiles/r06/ab_s19) and until now cost more in buckets
-// than it gave (1792 / 1024 -> 1024 / 512: -9.5 %; round 5's ab_s41: 72.6 against 74.7) -- with multipliers that spread a text's
-// grams (kernels/compress_wg.inc, tools/sim/hash_sim.c) the smaller tables have FEWER collisions than the large ones had:
-// 26.7 KB of LDS, SEARCH's constants as literals and the allocation held to 80 registers.  profiles/r06/ab_s31 ... ab_s34:
-// 74.6 -> 76.8 (the multipliers alone, 1792 / 1024, five workgroups) -> 79.1 GB/s (1024 / 512 buckets, six).
-// 1152 three-byte buckets since PARSE's exit functions are one byte a position (26 720 B; 26 848 is the most six workgroups leave
-// each other): 3.52 candidates a walk visits instead of 3.74, +0.6 ... 1.0 % (profiles/r06/ab_s48).
-#ifndef LZS_EXP_TEXT_HEAD3
-#define LZS_EXP_TEXT_HEAD3 1152
-#endif
-#ifndef LZS_EXP_TEXT_HEAD2
-#define LZS_EXP_TEXT_HEAD2 512
-#endif
-#ifndef LZS_EXP_TEXT_WAVES
-#define LZS_EXP_TEXT_WAVES 6
-#endif
-#define LZS_WGV_HEAD3 LZS_EXP_TEXT_HEAD3
-#define LZS_WGV_HEAD2 LZS_EXP_TEXT_HEAD2
-#if LZS_EXP_TEXT_WAVES > 0
-#define LZS_WGV_WAVES LZS_EXP_TEXT_WAVES
-#endif
-#ifndef LZS_EXP_TEXT_NOT_LEAN
-#define LZS_WGV_LEAN 1
-#endif
-#ifndef LZS_HASH3_MUL         // (the best of 8000 for 1024 / 512 buckets and of 6000 for 1152 / 512; -DLZS_HASH3_MUL= / -DLZS_HASH2_MUL= override: tools/probes/ab.sh)
-#define LZS_WGV_HASH3_MUL 0x897397u
-#endif
-#ifndef LZS_HASH2_MUL
-#define LZS_WGV_HASH2_MUL 0x64EBAD33u
-#endif
-#ifdef LZS_EXP_TEXT_POOL      // (tools/probes/ab.sh: round 6's pool of 256, profiles/r06/ab_s3)
-#define LZS_WGV_POOL LZS_EXP_TEXT_POOL
-#endif
-#ifdef LZS_EXP_TEXT_WG_WAVES
-#define LZS_WGV_WG_WAVES LZS_EXP_TEXT_WG_WAVES
-#endif
+#include "kernels/wgv_text_shape.inc"
 #include "kernels/compress_wg.inc"
 }
 namespace wgv_safe {
 #define LZS_WGV_CHAIN_SAFE 1
 #define LZS_WGV_SEGMENTS 1
+#define LZS_WGV_PRIO 1
+#include "kernels/compress_wg.inc"
+}
+// The channel kernel (lzs_compress_channels_wg_kernel: [history | packet] as one view) in the default shape and in the
+// order-independent CHAIN form; nothing else is compiled into these two.
+namespace wgv_text_ch {
+#define LZS_WGV_CHANNELS 1
+#include "kernels/wgv_text_shape.inc"
+#include "kernels/compress_wg.inc"
+}
+namespace wgv_safe_ch {
+#define LZS_WGV_CHANNELS 1
+#define LZS_WGV_CHAIN_SAFE 1
 #define LZS_WGV_PRIO 1
 #include "kernels/compress_wg.inc"
 }
@@ -550,6 +524,20 @@ int lzs_hip_launch_decompress_concat(void *d_out, size_t out_stride, uint32_t ou
     return launch_decompress(d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len, nblocks, stream, 1);
 }
 
+int lzs_hip_launch_decompress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                       const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                                       const uint32_t *d_channel, void *d_states, uint8_t *d_status, uint32_t npackets, void *stream)
+{
+    if (npackets == 0) return 0;
+    // (eight streams to a wavefront unless their input is too far apart for one 32-bit extent: launch_decompress's rule)
+    const unsigned long long longest = d_in_len ? 0xC0000400ull : in_len;
+    const uint32_t per_wave = (unsigned long long)in_stride * (kDecGroups - 1u) + longest < 0xFFFFFF00ull ? kDecGroups : 1u;
+    hipLaunchKernelGGL(lzs_decompress_channels_grp_kernel, dim3((npackets + per_wave - 1) / per_wave), dim3(64), 0, (hipStream_t)stream,
+                       (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
+                       d_channel, (uint8_t *)d_states, d_status, npackets, per_wave);
+    return (int)hipGetLastError();
+}
+
 #endif  // !LZS_TU_COMPRESS
 #ifndef LZS_TU_DECOMPRESS
 int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const void *d_in, uint32_t n,
@@ -571,6 +559,25 @@ int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const vo
                            (uint8_t *)d_slots, slot_stride, (const uint8_t *)d_in, n, seg, nseg,
                            d_entry, d_dirty, d_exit, (unsigned long long *)d_nbits,
                            (uint8_t *)d_out, (const unsigned long long *)d_bit_at, lim, d_open);
+    return (int)hipGetLastError();
+}
+
+// Many channels, one packet each: the default shape, or the order-independent CHAIN where the device needs it (as above).
+int lzs_hip_launch_compress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                     const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                                     const uint32_t *d_channel, void *d_states, uint8_t *d_status, uint32_t npackets, void *stream)
+{
+    if (npackets == 0) return 0;
+    int chain_mode = 0;
+    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
+    if (chain_mode != 0)
+        hipLaunchKernelGGL(wgv_safe_ch::lzs_compress_channels_wg_kernel, dim3(npackets), dim3(wgv_safe_ch::kWgThreads), 0, (hipStream_t)stream,
+                           (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
+                           d_channel, (uint8_t *)d_states, d_status, npackets);
+    else
+        hipLaunchKernelGGL(wgv_text_ch::lzs_compress_channels_wg_kernel, dim3(npackets), dim3(wgv_text_ch::kWgThreads), 0, (hipStream_t)stream,
+                           (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
+                           d_channel, (uint8_t *)d_states, d_status, npackets);
     return (int)hipGetLastError();
 }
 
