@@ -53,8 +53,9 @@ extern "C" {
  * channel.  A slot with hist_len > 2047 is not a state: that packet gets ERROR and d_out_len[b] = 0, and nothing else of it
  * is written or changed.
  *
- * A CHANNEL MAY APPEAR AT MOST ONCE PER CALL (packets of one channel depend on each other: give them in successive calls).
- * If one repeats, what that channel's packets and state receive is undefined; the other channels are not affected.
+ * A CHANNEL MAY APPEAR AT MOST ONCE PER CALL (packets of one channel depend on each other: give them in successive calls, or
+ * in one call of the burst entries below).  If one repeats, what that channel's packets and state receive is undefined; the
+ * other channels are not affected.
  *
  * Arguments are checked before the device is asked (LZS_E_ARG): d_states and d_out_len must be given, d_states 4-byte
  * aligned, d_out_len must not be the array d_in_len, npackets at most LZS_CHANNELS_MAX.  Without a device a valid call
@@ -86,6 +87,41 @@ int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_ca
                                    const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
                                    const uint32_t *d_channel, void *d_states, uint8_t *d_status,
                                    size_t npackets, void *hip_stream);
+
+/*
+ * BURSTS: many packets per channel in one call -- a queue drained as it stands, busy links with many packets, most with none.
+ *
+ * The arguments are those of the calls above, and three more: nchannels (the slots in d_states), and a device work area
+ * d_work of work_bytes bytes, 256-byte aligned, at least lzs_channels_burst_work_bytes(npackets, nchannels).  Both burst calls
+ * take the same size: a little over one channel slot a packet.
+ *
+ * REPEATS ALLOWED.  d_channel (required here) may name a channel any number of times; the packets of one channel are taken in
+ * ascending b.  Every packet's d_out bytes, d_out_len and d_status, and every channel's final slot, are byte for byte what
+ * this gives: split the call into ranks (rank k = the k-th packet of every channel) and make one call of
+ * lzs_compress_channels_device / lzs_decompress_channels_device per rank, in order.  So the rules above hold packet by
+ * packet: a compressed packet cut at out_cap still advances its channel's history, a decoder copy cut at out_cap keeps
+ * NO_OUTPUT_BUFFER_SPACE, and a channel whose slot has hist_len > 2047 gives ERROR and d_out_len[b] = 0 for every one of its
+ * packets and keeps its slot untouched.  In addition d_channel[b] >= nchannels gives that packet ERROR and d_out_len[b] = 0.
+ *
+ * Arguments are checked before the device is asked (LZS_E_ARG), as above, and: d_channel and d_work must be given, d_work
+ * 256-byte aligned, work_bytes no smaller than the size above, nchannels not 0 when there are packets and at most
+ * LZS_CHANNELS_MAX.  No allocation and no synchronisation (the work area holds all scratch): safe to capture into a hipGraph,
+ * with the caveat of the calls above.  A work area serves one call at a time.  Compression runs all packets in parallel
+ * (each packet's history is input: the last 2047 bytes of its channel's slot and of the channel's packets before it);
+ * decompression decodes each channel's packets in order, one decoder stream a channel, the channels with the most
+ * compressed bytes first.
+ */
+size_t lzs_channels_burst_work_bytes(size_t npackets, size_t nchannels);
+
+int lzs_compress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                       const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                       const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
+                                       void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
+
+int lzs_decompress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                         const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                         const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
+                                         void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
 
 #ifdef __cplusplus
 }

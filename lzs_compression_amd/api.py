@@ -44,6 +44,7 @@ _vp, _sz, _u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
 _BATCH_DEV = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz, _vp]
 _BATCH_HOST = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _sz]
 _CHANNELS_DEV = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp]
+_BURST_DEV = [_vp, _sz, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp]
 
 
 def lib() -> ctypes.CDLL:
@@ -94,6 +95,12 @@ def lib() -> ctypes.CDLL:
             if hasattr(L, name):        # (an older build named by LZS_LIBRARY, for A/B runs, has none)
                 f = getattr(L, name)
                 f.restype, f.argtypes = ctypes.c_int, _CHANNELS_DEV
+        for name in ("lzs_compress_channels_burst_device", "lzs_decompress_channels_burst_device"):
+            if hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = ctypes.c_int, _BURST_DEV
+        if hasattr(L, "lzs_channels_burst_work_bytes"):
+            L.lzs_channels_burst_work_bytes.restype, L.lzs_channels_burst_work_bytes.argtypes = _sz, [_sz, _sz]
         _lib = L
     return _lib
 
@@ -442,6 +449,51 @@ def decompress_channels(x, in_len, channels, states, out_capacity: int, out=None
     compress_channels, status LZS_D_STATUS_* bits (END_MARKER for a whole packet)."""
     return _device_channels(lib().lzs_decompress_channels_device, x, in_len, channels, states, out_capacity, out, out_len,
                             status, stream)
+
+
+# ------------------------------------------- many packets per channel in one call (lzs_channels.h, bursts)
+_BURST_WORK = {}                    # device -> the work area the burst calls reuse (grown on demand)
+
+
+def channels_burst_work_bytes(npackets: int, nchannels: int) -> int:
+    """lzs_channels_burst_work_bytes(): the device work area both burst calls need."""
+    return int(lib().lzs_channels_burst_work_bytes(npackets, nchannels))
+
+
+def _device_burst(fn, x, in_len, channels, states, out_cap, out, out_len, status, work, stream):
+    import torch
+    assert channels is not None and channels.is_cuda and channels.dtype == torch.int32 and channels.is_contiguous() \
+        and channels.numel() == x.shape[0], "channels must be a contiguous CUDA int32 tensor [npackets]"
+    nb, nch = x.shape[0], states.shape[0]
+    need = channels_burst_work_bytes(nb, nch)
+    if work is None:
+        work = _BURST_WORK.get(str(x.device))
+        if work is None or work.numel() < need:
+            work = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
+            _BURST_WORK[str(x.device)] = work
+    assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous(), "work must be a contiguous CUDA uint8 tensor"
+    return _device_channels(lambda *a: fn(*a[:10], nch, a[10], work.data_ptr(), work.numel(), *a[11:]), x, in_len, channels,
+                            states, out_cap, out, out_len, status, stream)
+
+
+def compress_channels_burst(x, in_len, channels, states, out_capacity: Optional[int] = None, out=None, out_len=None, status=None,
+                            work=None, stream=None):
+    """lzs_compress_channels_burst_device(): as compress_channels, but ``channels`` (CUDA int32, required) may repeat: the packets
+    of a channel are taken in row order, each with the history of the ones before it -- what ChannelCodec.compress gives, in one
+    call, with no host synchronisation.  An id >= len(states) gives that packet STATUS_ERROR and length 0.  ``work``: a CUDA
+    uint8 tensor of channels_burst_work_bytes() bytes or more (default: one per device, kept and reused -- give each stream
+    that runs burst calls at the same time its own).  Returns (slots, lengths int32, status uint8)."""
+    cap = compressed_max(x.shape[1]) if out_capacity is None else out_capacity
+    return _device_burst(lib().lzs_compress_channels_burst_device, x, in_len, channels, states, cap, out, out_len, status, work,
+                         stream)
+
+
+def decompress_channels_burst(x, in_len, channels, states, out_capacity: int, out=None, out_len=None, status=None, work=None,
+                              stream=None):
+    """lzs_decompress_channels_burst_device(): the reverse, on the decompressor's states -- what ChannelCodec.decompress gives,
+    in one call.  Arguments as compress_channels_burst.  Returns (out, lengths int32, status uint8: LZS_D_STATUS_* bits)."""
+    return _device_burst(lib().lzs_decompress_channels_burst_device, x, in_len, channels, states, out_capacity, out, out_len,
+                         status, work, stream)
 
 
 def _occurrence_rank(channels) -> np.ndarray:

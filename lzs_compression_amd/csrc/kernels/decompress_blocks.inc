@@ -814,16 +814,54 @@ struct DecChan {
     uint8_t *states = nullptr;
     const uint32_t *channel = nullptr;
     uint8_t *status = nullptr;
+    // RUN (lzs_decompress_runs_grp_kernel, CHAN as well): stream b is a RUN of one channel's packets, decoded one after the
+    // other in the same window.  The packets sorted by channel (skey / sidx: channel id -- nchannels for one out of range --
+    // and packet at each sorted position); run b starts at sorted position run_at[b] and ends before run_end[run_at[b]];
+    // run_key[b] == 0: there is no run b.
+    const uint32_t *run_key = nullptr, *run_at = nullptr, *run_end = nullptr, *skey = nullptr, *sidx = nullptr;
+    uint32_t nchannels = 0;
 };
 
+// (CHAN) hist[0, H) of the state slot = the H window bytes before position cpos, hist[H, 2048) = 0 -- the bytes the compressor
+// writes
+__device__ __forceinline__ void dec_put_history(uint8_t *cst, const uint8_t *ring8, uint32_t cpos, uint32_t H, uint32_t j)
+{
+    uint32_t *hist = reinterpret_cast<uint32_t *>(cst + kChanHistAt);
+    for (uint32_t w = j; w < 512u; w += kDecLanes) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t i = 4u * w + k;
+            uint32_t r = cpos + kDecRing - H + i;
+            r = r >= kDecRing ? r - kDecRing : r;
+            if (i < H) v |= (uint32_t)ring8[r] << (8u * k);
+        }
+        hist[w] = v;
+    }
+}
+
+// (RUN) 16 window bytes from any position a < kDecRing + kDecPiece, wrapping: a packet's output starts where the one before
+// it ended, so its drains are not aligned to the window
+__device__ __forceinline__ uint4 dec_ring_load16(const uint8_t *ring8, uint32_t a)
+{
+    a = a >= kDecRing ? a - kDecRing : a;
+    const uint32_t *ring = reinterpret_cast<const uint32_t *>(ring8);
+    const uint32_t s = a & 3u;
+    uint32_t w = a >> 2, v[5];
+#pragma unroll
+    for (uint32_t k = 0; k < 5u; k++) { v[k] = ring[w]; w = w + 1u == kDecRing / 4u ? 0u : w + 1u; }
+    return make_uint4(__builtin_amdgcn_alignbyte(v[1], v[0], s), __builtin_amdgcn_alignbyte(v[2], v[1], s),
+                      __builtin_amdgcn_alignbyte(v[3], v[2], s), __builtin_amdgcn_alignbyte(v[4], v[3], s));
+}
+
 // The same decoder with its flags as masks: the one-word feed with one token a trip or two (the 96-bit form stays above).
-template <bool TWO, bool WIDE, bool CONCAT, bool CHAN = false>
+template <bool TWO, bool WIDE, bool CONCAT, bool CHAN = false, bool RUN = false>
 __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
                                       uint32_t *__restrict__ out_len,
                                       const uint8_t *__restrict__ in, size_t in_stride,
                                       const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
                                       uint32_t nblocks, uint32_t concat_arg, uint32_t per_wave, DecChan ch = DecChan())
 {
+    static_assert(CHAN || !RUN, "a run is a channel's");
     const uint32_t lane = threadIdx.x;
     const uint32_t g = lane / kDecLanes, j = lane % kDecLanes;
     const uint32_t b = blockIdx.x * per_wave + g;                  // per_wave: kDecGroups, or 1 (see the launcher)
@@ -834,21 +872,42 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
 
     uint8_t *cst = nullptr;                                        // CHAN: the stream's state slot ...
     uint32_t hlen = 0;                                             // ... and its history's length (> 2047: not a state)
-    if constexpr (CHAN) {
+    uint32_t r_at = 0, r_end = 0;                                  // RUN: the run's sorted positions
+    if constexpr (RUN) {
+        if (b < nblocks && g < per_wave && ch.run_key[b] != 0u) {
+            r_at = ch.run_at[b];
+            r_end = ch.run_end[r_at];
+            const uint32_t c = ch.skey[r_at];
+            if (c < ch.nchannels) {
+                cst = ch.states + (size_t)c * kChanStateBytes;
+                hlen = *reinterpret_cast<const uint32_t *>(cst);
+            }
+        }
+    } else if constexpr (CHAN) {
         if (b < nblocks && g < per_wave) {
             cst = ch.states + (size_t)(ch.channel ? ch.channel[b] : b) * kChanStateBytes;
             hlen = *reinterpret_cast<const uint32_t *>(cst);
         }
     }
-    const bool live = b < nblocks && g < per_wave && (!CHAN || hlen <= kWindow);
-    const uint32_t bb = live ? b : 0u;
+    // (RUN: `live` is the run's here -- a channel id in range, a state -- and the current packet's in the loop below)
+    bool live = RUN ? (cst != nullptr && hlen <= kWindow) : (b < nblocks && g < per_wave && (!CHAN || hlen <= kWindow));
+    const bool live_run = live;
+    uint32_t bb = live ? b : 0u;
     uint8_t *ring8 = reinterpret_cast<uint8_t *>(L.ring[g]);
     uint8_t *dummy8 = reinterpret_cast<uint8_t *>(&L.dummy[lane]);
     const uint8_t *src = in + (size_t)bb * in_stride;
-    const uint32_t n   = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
+    uint32_t n   = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
     uint8_t *dst       = out + (size_t)bb * out_stride;
-    const bool dst16   = ((uintptr_t)dst & 15u) == 0;
-    const uint32_t cap = live ? out_cap : 0u;
+    bool dst16   = ((uintptr_t)dst & 15u) == 0;
+    uint32_t cap = live ? out_cap : 0u;
+    if constexpr (RUN) {                                           // a run that is not decoded: every packet of it is an ERROR
+        if (!live_run)
+            for (uint32_t at = r_at + j; at < r_end; at += kDecLanes) {
+                const uint32_t p = ch.sidx[at];
+                out_len[p] = 0;
+                if (ch.status) ch.status[p] = 0x10u;
+            }
+    }
     if constexpr (CHAN) {
         // history byte i is output byte i - hlen: window position kDecRing - hlen + i, which no output reaches before that
         // byte is more than 2047 behind (the argument of the zeros above)
@@ -863,6 +922,25 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         __syncthreads();
     }
 
+    // RUN: one trip of this loop per packet of the run (the k-th of every group's run side by side); the window and its
+    // position carry over from packet to packet, the bit feed and the token state start afresh.  Otherwise one trip.
+    uint32_t run_pos = 0;                                          // (RUN) the window position after the packets so far
+    uint32_t produced = 0;                                         // (RUN) output of the run so far
+    uint32_t pb = b;                                               // the packet
+    for (uint32_t k = 0;; k++) {
+    if constexpr (RUN) {
+        const uint32_t at = r_at + k;
+        live = live_run && at < r_end;
+        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+        pb = live ? ch.sidx[at] : 0u;
+        bb = pb;
+        src = in + (size_t)bb * in_stride;
+        n = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
+        dst = out + (size_t)bb * out_stride;
+        dst16 = ((uintptr_t)dst & 15u) == 0;
+        cap = live ? out_cap : 0u;
+    }
+
     // ---- the input as aligned words: word k holds stream bytes [4k - skew, 4k - skew + 4).  A
     // group takes 16 x kDecLanes bytes at a time: lane j holds words 4j .. 4j + 3 of the current
     // chunk (one coalesced load for the group) and of the next one, requested a chunk ahead; the
@@ -875,9 +953,11 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     // the whole wavefront, not waited for until the chunk is needed.
     const uint32_t skew = (uint32_t)((uintptr_t)src & 3u);
     const uint32_t b0 = blockIdx.x * per_wave;
-    const uint8_t *wave_in = in + (size_t)b0 * in_stride;
+    // (RUN: the packets of a trip lie anywhere in the input -- the launcher sees to it that all of it is one 32-bit extent, or
+    // gives each wavefront one run)
+    const uint8_t *wave_in = RUN ? (per_wave == 1u ? src : in) : in + (size_t)b0 * in_stride;
     const uintptr_t in_lo = (uintptr_t)wave_in & ~(uintptr_t)3;
-    const uint32_t rel = live ? (uint32_t)((size_t)(b - b0) * in_stride) : 0u;      // my stream, from wave_in
+    const uint32_t rel = live ? (uint32_t)(RUN ? (per_wave == 1u ? (size_t)0 : (size_t)pb * in_stride) : (size_t)(b - b0) * in_stride) : 0u;      // my stream, from wave_in
     uint32_t wave_end = 0;
 #pragma unroll
     for (uint32_t gg = 0; gg < kDecGroups; gg++) {
@@ -933,7 +1013,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint32_t bits_lo = 0;                                          // (WIDE: bits 64..95 of the buffer, left-aligned)
     uint32_t count = 0, flushed = 0, off = 0;
     uint32_t m_ext = 0;                                            // "a length nibble follows", as a mask
-    uint32_t cpos = 0, fpos = 0;                                   // count and flushed modulo kDecRing
+    uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? run_pos : 0u;  // count and flushed modulo kDecRing
     uint32_t m_done = live ? 0u : ~0u;                             // the stream has stopped, as a mask
     uint32_t m_eos = 0u;                                           // (CHAN) ... at an end marker
     uint32_t m_cut = 0u;                                           // (CHAN) a copy lost bytes to the room: no end marker counts after it
@@ -1157,7 +1237,9 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
                     const uint32_t p = flushed + kDecPiece * piece + 16u * j;
                     uint32_t fp = fpos + kDecPiece * piece;
                     fp = fp >= kDecRing ? fp - kDecRing : fp;
-                    const uint4 v = *reinterpret_cast<const uint4 *>(ring8 + fp + 16u * j);
+                    uint4 v;
+                    if constexpr (RUN) v = dec_ring_load16(ring8, fp + 16u * j);
+                    else v = *reinterpret_cast<const uint4 *>(ring8 + fp + 16u * j);
                     if (dst16) {
                         *reinterpret_cast<uint4 *>(dst + p) = v;
                     } else {
@@ -1176,23 +1258,17 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         r = r >= kDecRing ? r - kDecRing : r;
         dst[i] = ring8[r];
     }
-    if (live && j == 0u) out_len[b] = count;
-    if constexpr (CHAN) {
+    if (live && j == 0u) out_len[pb] = count;
+    if constexpr (RUN) {
+        if (live && j == 0u && ch.status) ch.status[pb] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
+        produced += live ? count : 0u;
+        run_pos = cpos;
+    } else if constexpr (CHAN) {
         if (live) {
             // the new history: hist[0, H) = the last H bytes of history | output (output byte count - H + i is at window
             // position cpos - H + i), hist[H, 2048) = 0 -- the bytes the compressor writes
             const uint32_t H = min(hlen + count, kWindow);
-            uint32_t *hist = reinterpret_cast<uint32_t *>(cst + kChanHistAt);
-            for (uint32_t w = j; w < 512u; w += kDecLanes) {
-                uint32_t v = 0;
-                for (uint32_t k = 0; k < 4u; k++) {
-                    const uint32_t i = 4u * w + k;
-                    uint32_t r = cpos + kDecRing - H + i;
-                    r = r >= kDecRing ? r - kDecRing : r;
-                    if (i < H) v |= (uint32_t)ring8[r] << (8u * k);
-                }
-                hist[w] = v;
-            }
+            dec_put_history(cst, ring8, cpos, H, j);
             if (j == 0u) {
                 *reinterpret_cast<uint32_t *>(cst) = H;
                 if (ch.status) ch.status[b] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
@@ -1200,6 +1276,16 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         } else if (cst && j == 0u) {                               // not a state: nothing is written, nothing changes
             out_len[b] = 0;
             if (ch.status) ch.status[b] = 0x10u;
+        }
+    }
+    if constexpr (!RUN) break;
+    }
+    // (RUN) the run's history goes back once, at its end
+    if constexpr (RUN) {
+        if (live_run) {
+            const uint32_t H = min(hlen + produced, kWindow);
+            dec_put_history(cst, ring8, run_pos, H, j);
+            if (j == 0u) *reinterpret_cast<uint32_t *>(cst) = H;
         }
     }
 }
@@ -1268,4 +1354,40 @@ void lzs_decompress_channels_grp_kernel(uint8_t *__restrict__ out, size_t out_st
     if (two)       lzs_decompress_blocks_grp_m<true, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
     else if (wide) lzs_decompress_blocks_grp_m<false, true, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
     else           lzs_decompress_blocks_grp_m<false, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
+}
+
+// Many packets per channel (include/lzs/lzs_channels.h, lzs_decompress_channels_burst_device; DESIGN.md 3.11): group g of
+// wavefront w decodes run w * per_wave + g of the runs sorted longest first -- its channel's history preloaded once, its packets
+// one after the other in the same window, the history written back once.  The form as lzs_decompress_channels_grp_kernel
+// picks it, from the wavefront's runs.
+__global__ __launch_bounds__(64)
+void lzs_decompress_runs_grp_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
+                                    uint32_t *__restrict__ out_len,
+                                    const uint8_t *__restrict__ in, size_t in_stride,
+                                    const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
+                                    const uint32_t *__restrict__ run_key, const uint32_t *__restrict__ run_at,
+                                    const uint32_t *__restrict__ run_end, const uint32_t *__restrict__ skey,
+                                    const uint32_t *__restrict__ sidx, uint32_t nchannels, uint8_t *__restrict__ states,
+                                    uint8_t *__restrict__ status, uint32_t nruns, uint32_t per_wave)
+{
+    __shared__ DecGroupLds L;
+    uint64_t total = 0, blocks = 0;
+    const uint32_t b0 = blockIdx.x * per_wave;
+    if (b0 >= nruns || run_key[b0] == 0u) return;                 // (runs are sorted by weight: none from here on)
+    for (uint32_t g = 0; g < per_wave && b0 + g < nruns; g++) {
+        const uint32_t w = run_key[b0 + g];                        // 1 + the run's compressed bytes (saturated), 0: no run
+        if (w == 0u) break;
+        const uint32_t at = run_at[b0 + g];
+        total += w - 1u;
+        blocks += run_end[at] - at;
+    }
+    const uint64_t full = blocks * (uint64_t)out_cap;
+    const bool two = uniform((4ull * total > full && 10ull * total < 9ull * full) ? 1u : 0u) != 0u;
+    const bool wide = uniform(10ull * total >= 9ull * full ? 1u : 0u) != 0u;
+    DecChan ch;
+    ch.states = states; ch.status = status;
+    ch.run_key = run_key; ch.run_at = run_at; ch.run_end = run_end; ch.skey = skey; ch.sidx = sidx; ch.nchannels = nchannels;
+    if (two)       lzs_decompress_blocks_grp_m<true, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
+    else if (wide) lzs_decompress_blocks_grp_m<false, true, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
+    else           lzs_decompress_blocks_grp_m<false, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
 }

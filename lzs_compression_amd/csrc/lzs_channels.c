@@ -39,6 +39,62 @@ int lzs_compress_channels_device(void *d_out, size_t out_stride, size_t out_cap,
                            d_out_len, d_in, in_stride, d_in_len, in_len, d_channel, d_states, d_status, npackets, hip_stream);
 }
 
+size_t lzs_channels_burst_work_bytes(size_t npackets, size_t nchannels)
+{
+    (void)nchannels;                                  /* (today's layout does not depend on it) */
+    return lzs_hip_burst_work_bytes(npackets > LZS_CHANNELS_MAX ? (size_t)LZS_CHANNELS_MAX : npackets);
+}
+
+/* Many packets per channel (lzs_channels_burst.hip): the checks of device_channels, and those of the ids and the work area. */
+static int device_burst(const char *who, int decompress, void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                        const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len, const uint32_t *d_channel,
+                        void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets,
+                        void *stream)
+{
+    if (npackets == 0) return LZS_OK;
+    if (npackets > LZS_CHANNELS_MAX) return fail(LZS_E_ARG, "%s: too many packets (%zu)", who, npackets);
+    if (!d_out_len) return fail(LZS_E_ARG, "%s: out_len is NULL", who);
+    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
+    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
+    if (!d_channel) return fail(LZS_E_ARG, "%s: channel is NULL", who);
+    if (nchannels == 0) return fail(LZS_E_ARG, "%s: no channels for %zu packets", who, npackets);
+    if (nchannels > LZS_CHANNELS_MAX) return fail(LZS_E_ARG, "%s: too many channels (%zu)", who, nchannels);
+    if (!d_work) return fail(LZS_E_ARG, "%s: work is NULL", who);
+    if ((uintptr_t)d_work & 255u) return fail(LZS_E_ARG, "%s: work is not 256-byte aligned", who);
+    const size_t need = lzs_channels_burst_work_bytes(npackets, nchannels);
+    if (work_bytes < need)
+        return fail(LZS_E_ARG, "%s: work_bytes %zu is smaller than lzs_channels_burst_work_bytes() = %zu", who, work_bytes, need);
+    if (!d_in && (in_len || d_in_len)) return fail(LZS_E_ARG, "%s: input is NULL", who);
+    if (!d_out && out_cap) return fail(LZS_E_ARG, "%s: output is NULL", who);
+    if (in_len > LZS_BLOCK_MAX) return fail(LZS_E_ARG, "%s: packet of %zu bytes exceeds LZS_BLOCK_MAX", who, in_len);
+    if (d_in_len && (const void *)d_in_len == (const void *)d_out_len)
+        return fail(LZS_E_ARG, "%s: d_out_len and d_in_len are the same array", who);
+    int rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const uint32_t cap32 = out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap;
+    const int e = lzs_hip_burst(decompress, d_out, out_stride, cap32, d_out_len, d_in, in_stride, d_in_len, (uint32_t)in_len,
+                                d_channel, d_states, (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                       const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                       const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
+                                       void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
+{
+    return device_burst("lzs_compress_channels_burst_device", 0, d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len,
+                        in_len, d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+}
+
+int lzs_decompress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                         const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                         const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
+                                         void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
+{
+    return device_burst("lzs_decompress_channels_burst_device", 1, d_out, out_stride, out_cap, d_out_len, d_in, in_stride,
+                        d_in_len, in_len, d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+}
+
 int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
                                    const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
                                    const uint32_t *d_channel, void *d_states, uint8_t *d_status,

@@ -156,6 +156,22 @@ int lzs_hip_launch_compress_channels(void *d_out, size_t out_stride, uint32_t ou
 int lzs_hip_launch_decompress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                                        const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                                        const uint32_t *d_channel, void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
+/* Many packets per channel (lzs_channels_burst.hip): the runs of a burst, one per group of a wavefront, longest first --
+ * d_run_key[r] (1 + compressed bytes, 0: no run r; descending) and d_run_at[r] (its first position in the order by channel),
+ * d_run_end[position of a run's first packet] (one past its last), d_skey / d_sidx (channel, nchannels if out of range, and
+ * packet at each position). */
+int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                                   const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
+                                   const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
+                                   uint8_t *d_status, uint32_t npackets, void *stream);
+/* Many packets per channel (lzs_channels_burst.hip; lzs_channels.c checks the arguments): the work area's size, and one burst
+ * through compression (decompress 0) or decompression (1) -- the grouping, then the kernels above. */
+size_t lzs_hip_burst_work_bytes(size_t npackets);
+int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                  const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                  const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
+                  void *d_work, uint32_t npackets, void *stream);
 int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
                            size_t slot_stride, const uint32_t *d_len, uint32_t nblocks,
                            void *stream);

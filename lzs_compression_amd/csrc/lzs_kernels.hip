@@ -538,6 +538,22 @@ int lzs_hip_launch_decompress_channels(void *d_out, size_t out_stride, uint32_t 
     return (int)hipGetLastError();
 }
 
+int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                                   const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
+                                   const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
+                                   uint8_t *d_status, uint32_t npackets, void *stream)
+{
+    if (npackets == 0) return 0;
+    // (a wavefront's runs take packets from anywhere in the input: eight runs to a wavefront if all of it is one 32-bit extent)
+    const unsigned long long longest = d_in_len ? 0xC0000400ull : in_len;
+    const uint32_t per_wave = (unsigned long long)in_stride * (npackets - 1u) + longest < 0xFFFFFF00ull ? kDecGroups : 1u;
+    hipLaunchKernelGGL(lzs_decompress_runs_grp_kernel, dim3((npackets + per_wave - 1) / per_wave), dim3(64), 0, (hipStream_t)stream,
+                       (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
+                       d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets, per_wave);
+    return (int)hipGetLastError();
+}
+
 #endif  // !LZS_TU_COMPRESS
 #ifndef LZS_TU_DECOMPRESS
 int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const void *d_in, uint32_t n,
