@@ -110,8 +110,16 @@ int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_ca
  * (each packet's history is input: the last 2047 bytes of its channel's slot and of the channel's packets before it);
  * decompression decodes each channel's packets in order, one decoder stream a channel, the channels with the most
  * compressed bytes first.
+ *
+ * LONG RUNS.  One decoder stream a channel makes the busiest channel the decoder's time.  A work area of at least
+ * lzs_channels_burst_split_work_bytes(npackets, nchannels, out_cap) bytes -- the burst size plus about two bytes per packet and
+ * byte of out_cap; SIZE_MAX where that does not fit a size_t -- lets lzs_decompress_channels_burst_device decode the packets of
+ * long runs all at once and settle what they copy from each other afterwards.  The results are the same byte
+ * for byte with either size of work area: d_out up to each d_out_len[b] and nothing past it, d_out_len, d_status, the slots.
+ * The compressor ignores the extra room.
  */
 size_t lzs_channels_burst_work_bytes(size_t npackets, size_t nchannels);
+size_t lzs_channels_burst_split_work_bytes(size_t npackets, size_t nchannels, size_t out_cap);
 
 int lzs_compress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
                                        const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,

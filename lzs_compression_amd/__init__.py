@@ -5,7 +5,7 @@ reference's one-shot C-ABI (include/lzs/lzs.h); this package is its ctypes front
 the seeded workload generators used by the benchmark and tests.  No CPU codec, no
 fallback: without the built library or without a GPU, calls raise.
 """
-from .api import (CHANNEL_STATE_BYTES, ChannelCodec, channels_burst_work_bytes, compress_channels, compress_channels_burst,
+from .api import (CHANNEL_STATE_BYTES, ChannelCodec, channels_burst_split_work_bytes, channels_burst_work_bytes, compress_channels, compress_channels_burst,
                   decompress_channels, decompress_channels_burst, new_channel_states)
 from .api import (IncrementalCompressor, IncrementalDecompressor, LzsError, backend_info, compact, compress, compress_batch, compress_blocks,
                   compress_stream, compressed_max, decompress, decompress_batch, decompress_blocks, decompress_blocks_sync, decompress_concat,
@@ -13,7 +13,7 @@ from .api import (IncrementalCompressor, IncrementalDecompressor, LzsError, back
 from .api import (STATUS_END_MARKER, STATUS_ERROR, STATUS_INPUT_FINISHED, STATUS_INPUT_STARVED, STATUS_NO_OUTPUT_BUFFER_SPACE)
 from . import workload
 
-__all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
+__all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_bytes", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
            "decompress_channels", "decompress_channels_burst", "new_channel_states",
            "IncrementalCompressor", "IncrementalDecompressor", "LzsError", "backend_info", "compact", "compress", "compress_batch", "compress_blocks",
            "compress_stream", "compressed_max", "decompress", "decompress_batch", "decompress_blocks", "decompress_blocks_sync", "decompress_concat",

@@ -101,6 +101,9 @@ def lib() -> ctypes.CDLL:
                 f.restype, f.argtypes = ctypes.c_int, _BURST_DEV
         if hasattr(L, "lzs_channels_burst_work_bytes"):
             L.lzs_channels_burst_work_bytes.restype, L.lzs_channels_burst_work_bytes.argtypes = _sz, [_sz, _sz]
+        if hasattr(L, "lzs_channels_burst_split_work_bytes"):
+            L.lzs_channels_burst_split_work_bytes.restype = _sz
+            L.lzs_channels_burst_split_work_bytes.argtypes = [_sz, _sz, _sz]
         _lib = L
     return _lib
 
@@ -460,12 +463,20 @@ def channels_burst_work_bytes(npackets: int, nchannels: int) -> int:
     return int(lib().lzs_channels_burst_work_bytes(npackets, nchannels))
 
 
-def _device_burst(fn, x, in_len, channels, states, out_cap, out, out_len, status, work, stream):
+def channels_burst_split_work_bytes(npackets: int, nchannels: int, out_capacity: int) -> int:
+    """lzs_channels_burst_split_work_bytes(): the work area with which decompress_channels_burst may split long runs over the
+    device -- channels_burst_work_bytes() plus about two bytes per packet and byte of ``out_capacity``."""
+    if not hasattr(lib(), "lzs_channels_burst_split_work_bytes"):      # (an older build named by LZS_LIBRARY, for A/B runs: no split)
+        return channels_burst_work_bytes(npackets, nchannels)
+    return int(lib().lzs_channels_burst_split_work_bytes(npackets, nchannels, out_capacity))
+
+
+def _device_burst(fn, x, in_len, channels, states, out_cap, out, out_len, status, work, stream, split=False):
     import torch
     assert channels is not None and channels.is_cuda and channels.dtype == torch.int32 and channels.is_contiguous() \
         and channels.numel() == x.shape[0], "channels must be a contiguous CUDA int32 tensor [npackets]"
     nb, nch = x.shape[0], states.shape[0]
-    need = channels_burst_work_bytes(nb, nch)
+    need = channels_burst_split_work_bytes(nb, nch, out_cap) if split else channels_burst_work_bytes(nb, nch)
     if work is None:
         work = _BURST_WORK.get(str(x.device))
         if work is None or work.numel() < need:
@@ -491,9 +502,11 @@ def compress_channels_burst(x, in_len, channels, states, out_capacity: Optional[
 def decompress_channels_burst(x, in_len, channels, states, out_capacity: int, out=None, out_len=None, status=None, work=None,
                               stream=None):
     """lzs_decompress_channels_burst_device(): the reverse, on the decompressor's states -- what ChannelCodec.decompress gives,
-    in one call.  Arguments as compress_channels_burst.  Returns (out, lengths int32, status uint8: LZS_D_STATUS_* bits)."""
+    in one call.  Arguments as compress_channels_burst.  The default work area has channels_burst_split_work_bytes() bytes, with
+    which long runs are split over the device; a caller's ``work`` decides by its size (the results are the same).
+    Returns (out, lengths int32, status uint8: LZS_D_STATUS_* bits)."""
     return _device_burst(lib().lzs_decompress_channels_burst_device, x, in_len, channels, states, out_capacity, out, out_len,
-                         status, work, stream)
+                         status, work, stream, split=True)
 
 
 def _occurrence_rank(channels) -> np.ndarray:

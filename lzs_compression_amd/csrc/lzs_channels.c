@@ -45,6 +45,21 @@ size_t lzs_channels_burst_work_bytes(size_t npackets, size_t nchannels)
     return lzs_hip_burst_work_bytes(npackets > LZS_CHANNELS_MAX ? (size_t)LZS_CHANNELS_MAX : npackets);
 }
 
+/* The burst decoder's larger work area: the burst size and a 16-bit origin for every byte a packet may produce (the split
+ * route's tables are where the compressor has its slots).  SIZE_MAX where that does not fit a size_t: no work area is that large, so no call splits. */
+size_t lzs_channels_burst_split_work_bytes(size_t npackets, size_t nchannels, size_t out_cap)
+{
+    const size_t n = npackets > LZS_CHANNELS_MAX ? (size_t)LZS_CHANNELS_MAX : npackets;
+    const size_t cap = out_cap > 0xFFFFFFFFu ? (size_t)0xFFFFFFFFu : out_cap;
+    const size_t base = lzs_channels_burst_work_bytes(n, nchannels);
+    if (cap != 0 && n > (SIZE_MAX - base) / 2u / cap) return SIZE_MAX;
+    return base + 2u * n * cap;
+}
+
+/* Runs of at least this many compressed bytes are split over the device where the work area allows it (DESIGN.md 3.12 has the
+ * sweep: the crossover of both routes on queues with one long run); LZS_BURST_SPLIT_MIN overrides it. */
+#define BURST_SPLIT_MIN_DEFAULT 8192u
+
 /* Many packets per channel (lzs_channels_burst.hip): the checks of device_channels, and those of the ids and the work area. */
 static int device_burst(const char *who, int decompress, void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
                         const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len, const uint32_t *d_channel,
@@ -72,8 +87,13 @@ static int device_burst(const char *who, int decompress, void *d_out, size_t out
     int rc = require_device();
     if (rc != LZS_OK) return rc;
     const uint32_t cap32 = out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap;
+    /* the decoder may split long runs if the caller gave it the room for the origins (the compressor ignores extra room) */
+    const int split = decompress && work_bytes >= lzs_channels_burst_split_work_bytes(npackets, nchannels, cap32);
+    const lzs_env_t *env = lzs_env();
+    const uint32_t split_min = env->burst_split_set ? env->burst_split_min : BURST_SPLIT_MIN_DEFAULT;
     const int e = lzs_hip_burst(decompress, d_out, out_stride, cap32, d_out_len, d_in, in_stride, d_in_len, (uint32_t)in_len,
-                                d_channel, d_states, (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, stream);
+                                d_channel, d_states, (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, split, split_min,
+                                stream);
     return e ? hip_fail(e, who) : LZS_OK;
 }
 

@@ -166,12 +166,15 @@ int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_
                                    const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
                                    uint8_t *d_status, uint32_t npackets, void *stream);
 /* Many packets per channel (lzs_channels_burst.hip; lzs_channels.c checks the arguments): the work area's size, and one burst
- * through compression (decompress 0) or decompression (1) -- the grouping, then the kernels above. */
+ * through compression (decompress 0) or decompression (1) -- the grouping, then the kernels above.  `split` (decompression;
+ * the work area then holds lzs_hip_burst_work_bytes() + 2 * npackets * out_cap bytes): the
+ * runs of at least `split_min` compressed bytes are decoded by all their packets at once with per-byte origins and resolved
+ * afterwards (lzs_burst_parse_kernel, lzs_burst_resolve_kernel), the others by lzs_hip_launch_decompress_runs. */
 size_t lzs_hip_burst_work_bytes(size_t npackets);
 int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                   const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
-                  void *d_work, uint32_t npackets, void *stream);
+                  void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream);
 int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
                            size_t slot_stride, const uint32_t *d_len, uint32_t nblocks,
                            void *stream);

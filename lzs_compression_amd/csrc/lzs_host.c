@@ -263,6 +263,7 @@ static void env_read(lzs_env_t *e)
     v = get("LZS_BATCH_SEG_MB"); e->batch_seg_mb = v ? (int)strtol(v, NULL, 10) : 0;
     v = get("LZS_PIPE_MIN_MB"); e->pipe_min_mb = v ? (int)strtol(v, NULL, 10) : 0;
     v = get("LZS_STAGING_FAIL_MB"); e->staging_fail_mb = v ? (int)strtol(v, NULL, 10) : 0;
+    v = get("LZS_BURST_SPLIT_MIN"); e->burst_split_set = v != NULL; e->burst_split_min = v ? (uint32_t)strtoul(v, NULL, 10) : 0;
     v = get("LZS_ROUTE"); e->route = !v ? LZS_ROUTE_AUTO : (v[0] == 'd' ? LZS_ROUTE_DEVICE : (v[0] == 'h' ? LZS_ROUTE_HOST : LZS_ROUTE_AUTO));
 }
 

@@ -44,6 +44,8 @@ typedef struct {
     int      staging_fail_mb;       /* LZS_STAGING_FAIL_MB (tests): device reservations above this many MiB fail like a full device */
     int      route;                 /* LZS_ROUTE: 0 by size (the default), 1 "device": every call on the device, 2 "host": the small
                                      * calls' host route for every size it can take, and no device needed (lzs_hostcodec.c) */
+    int      burst_split_set;       /* LZS_BURST_SPLIT_MIN is given: the burst decoder splits the runs of at least ... */
+    uint32_t burst_split_min;       /* ... this many compressed bytes over the device (0: every run; unset: the default, lzs_channels.c) */
 } lzs_env_t;
 LZS_HIDDEN const lzs_env_t *lzs_env(void);
 

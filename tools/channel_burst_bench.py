@@ -10,13 +10,20 @@ Wall time per call including host work (the ids live on the device: ChannelCodec
 bytes, and library calls (ChannelCodec: one per rank).  Both sides are checked against each other before timing.  Prints one
 JSON line per class, shape and direction, and writes them to --out.
 
-    python tools/channel_burst_bench.py --out profiles/r08/channel_burst.txt
+The decoder is timed twice: with a work area of lzs_channels_burst_work_bytes() (burst_ms: one decoder stream a run) and with
+one of lzs_channels_burst_split_work_bytes() (split_ms: long runs split over the device).  --sweep times both
+on queues of shape c with a long run of 2 ... 300 packets, the threshold set so that only that run is split: where the
+default of LZS_BURST_SPLIT_MIN comes from.  LZS_LIBRARY=<an older liblzs.so> gives that build's figures (no split there).
+
+    python tools/channel_burst_bench.py --out profiles/r09/channel_burst_split.txt
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+os.environ.setdefault("LZS_DEV_ENV", "1")          # --sweep sets LZS_BURST_SPLIT_MIN between calls
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 if ROOT not in sys.path:
@@ -29,12 +36,12 @@ import lzs_compression_amd as lzs  # noqa: E402
 from lzs_compression_amd import api as A  # noqa: E402
 
 
-def _ids(shape, nch, rng):
+def _ids(shape, nch, rng, run=300):
     if shape == "a":
         return np.tile(np.arange(nch), 4)
     if shape == "b":
         return (rng.zipf(1.1, 4 * nch) - 1) % nch
-    return rng.permutation(np.concatenate([np.zeros(300, dtype=np.int64), np.arange(1, nch)]))
+    return rng.permutation(np.concatenate([np.zeros(run, dtype=np.int64), np.arange(1, nch)]))
 
 
 def _wall(fn, reps):
@@ -58,15 +65,21 @@ def main():
     ap.add_argument("--classes", default="text,lowent,random")
     ap.add_argument("--shapes", default="a,b,c")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08", "channel_burst.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "channel_burst_split.txt"))
+    ap.add_argument("--no-codec", action="store_true", help="do not time ChannelCodec (checked against it all the same)")
+    ap.add_argument("--sweep", action="store_true", help="shape c with a long run of 2 ... 300 packets, decoder only, both routes")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     nch, P = a.channels, a.packet
     lines = []
-    for cls in a.classes.split(","):
-        for shape in a.shapes.split(","):
+    has_split = hasattr(lzs.lib(), "lzs_channels_burst_split_work_bytes")
+    cases = [(cls, shape, 300) for cls in a.classes.split(",") for shape in a.shapes.split(",")]
+    if a.sweep:
+        cases = [(cls, "c", run) for cls in a.classes.split(",") for run in (2, 3, 4, 6, 8, 12, 16, 32, 64, 128, 300)]
+    if True:
+        for cls, shape, run in cases:
             rng = np.random.default_rng(1)
-            ids = _ids(shape, nch, rng)
+            ids = _ids(shape, nch, rng, run)
             n = ids.size
             x = lzs.workload.fill_device(cls, n, P)             # packet b: block b of the class (no history shared by design)
             ch = torch.from_numpy(ids.astype(np.int32)).cuda()
@@ -87,8 +100,16 @@ def main():
             y, yl = got[0], got[1]
             comp = int(yl.sum().item())
 
+            small = torch.empty(lzs.channels_burst_work_bytes(n, nch), dtype=torch.uint8, device="cuda")
+            large = torch.empty(lzs.channels_burst_split_work_bytes(n, nch, P), dtype=torch.uint8, device="cuda")
+            if a.sweep:                                         # only the long run is split: the others are one packet each
+                os.environ["LZS_BURST_SPLIT_MIN"] = str(int(yl[ch != 0].max().item()) + 1)
+
             def burst_d():
-                return lzs.decompress_channels_burst(y, yl, ch, lzs.new_channel_states(nch), P)
+                return lzs.decompress_channels_burst(y, yl, ch, lzs.new_channel_states(nch), P, work=small)
+
+            def split_d():
+                return lzs.decompress_channels_burst(y, yl, ch, lzs.new_channel_states(nch), P, work=large)
 
             def codec_d():
                 codec = lzs.ChannelCodec(nch)
@@ -97,13 +118,28 @@ def main():
             back, want_d = burst_d(), codec_d()
             torch.cuda.synchronize()
             assert torch.equal(back[0][:, :P], x) and torch.equal(back[1], want_d[1]), f"{cls}/{shape}: decompress differs"
+            back = split_d()
+            torch.cuda.synchronize()
+            assert torch.equal(back[0][:, :P], x) and torch.equal(back[1], want_d[1]) and torch.equal(back[2], want_d[2]), \
+                f"{cls}/{shape}: decompress with the larger work area differs"
             for direction, fb, fc in (("compress", burst_c, codec_c), ("decompress", burst_d, codec_d)):
-                tb, tc = _wall(fb, a.reps), _wall(fc, a.reps)
+                if a.sweep and direction == "compress":
+                    continue
+                tb = _wall(fb, a.reps)
                 line = {"tool": "channel_burst_bench", "class": cls, "shape": shape, "direction": direction, "packets": n,
                         "channels": nch, "packet": P, "ranks": ranks, "ratio": round(comp / (n * P), 4),
                         "burst_ms": round(tb * 1e3, 3), "burst_GBps": round(n * P / tb / 1e9, 2), "burst_calls": 1,
-                        "codec_ms": round(tc * 1e3, 3), "codec_GBps": round(n * P / tc / 1e9, 2), "codec_calls": ranks,
-                        "speedup": round(tc / tb, 2), "device": torch.cuda.get_device_name(0)}
+                        "device": torch.cuda.get_device_name(0)}
+                if direction == "decompress" and has_split:
+                    ts = _wall(split_d, a.reps)
+                    line.update({"split_ms": round(ts * 1e3, 3), "split_GBps": round(n * P / ts / 1e9, 2),
+                                 "split_speedup": round(tb / ts, 2)})
+                if not a.no_codec and not a.sweep:
+                    tc = _wall(fc, a.reps)
+                    line.update({"codec_ms": round(tc * 1e3, 3), "codec_GBps": round(n * P / tc / 1e9, 2), "codec_calls": ranks,
+                                 "speedup": round(tc / tb, 2)})
+                if a.sweep:
+                    line.update({"long_run": run, "split_min": int(os.environ["LZS_BURST_SPLIT_MIN"])})
                 print(json.dumps(line), flush=True)
                 lines.append(json.dumps(line))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
