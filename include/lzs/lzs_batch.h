@@ -99,6 +99,39 @@ int lzs_decompress_batch_device_sync(void *d_out, size_t out_stride, size_t out_
                                      size_t in_len, size_t nblocks);
 
 /*
+ * How long every block of a batch decodes to, and how its decoding ends, WITHOUT decoding it: what a caller needs to choose
+ * out_cap or to allocate the output before any of the decode calls (LZS_DECOMPRESSED_MAX() is no bound: see lzs.h).
+ *
+ *   block b    : d_in + b * in_stride, length d_in_len ? d_in_len[b] : in_len, as above
+ *   d_size[b]  : exactly what lzs_decompress_batch_device() writes to d_out_len[b] when called with out_cap = limit -- and what
+ *                lzs_decompress_channels_device() (lzs_channels.h) writes for the same bytes on any valid channel, whatever
+ *                its history: a stream's length depends on its tokens and the capacity, never on the bytes it copies
+ *   d_status[b]: (d_status may be NULL) the LZS_D_STATUS_* byte lzs_decompress_channels_device() writes with out_cap = limit:
+ *                END_MARKER if an end marker was reached -- it needs no room, and it does not count after a copy that `limit`
+ *                cut short, also not behind that copy's closing length nibble 0 --, otherwise NO_OUTPUT_BUFFER_SPACE if
+ *                d_size[b] >= limit, otherwise INPUT_STARVED | INPUT_FINISHED.  Never ERROR: the call sees no channel slot.
+ *
+ * A long offset of 0 has no length field and copies nothing, bytes after the end marker are ignored: the decoders' rules.
+ * limit <= 0xFFFFFFFF (LZS_E_ARG above it).  limit = 0xFFFFFFFF asks for the true size; a block that decodes to more reports
+ * limit and NO_OUTPUT_BUFFER_SPACE.  limit = 0 is out_cap = 0: size 0, END_MARKER for a stream that begins with its marker.
+ * d_size and d_in (with nblocks > 0) are required, d_size must not be the array d_in_len, in_len and nblocks are bounded as
+ * for lzs_decompress_batch_device(); nblocks == 0 is LZS_OK and touches nothing.
+ *
+ * A token walk, one GPU lane a block: no output traffic, no window, no allocation, no synchronisation -- asynchronous on
+ * `hip_stream` and safe to capture into a hipGraph (the note on the very first call into the library applies).  Any
+ * alignment of d_in and in_stride; nothing is read outside the aligned 32-bit words that hold a block's own bytes, and a
+ * block's result depends on nothing outside [block start, block start + length).
+ *
+ * The call is sized for MANY blocks.  On an MI355X 65 536 packets of 1500 bytes of text take 0.51 ms (decoding them into
+ * scratch memory: 0.80 ms) and 16 384 blocks of 64 KiB of text 18.6 ms (decoding: 7.5 ms); DESIGN.md 3.13 has every
+ * row.  One block is one lane's serial walk however large it is, so a few huge blocks get no help from it: a single block of
+ * 1 MiB of text takes 157 ms.
+ */
+int lzs_decompressed_size_batch_device(uint32_t *d_size, uint8_t *d_status,
+                                       const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                       size_t limit, size_t nblocks, void *hip_stream);
+
+/*
  * ONE stream from device memory, on the whole device: the result of
  * lzs_compress(d_out, out_cap, d_in, in_len) (reference lzs-compression.c:249-467) for buffers
  * already in HBM.  The stream is cut into segments (0.5 KiB .. 64 KiB), one workgroup each; where each

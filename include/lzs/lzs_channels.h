@@ -82,6 +82,13 @@ int lzs_compress_channels_device(void *d_out, size_t out_stride, size_t out_cap,
  * packets are whole).  An offset reaching before the channel's history reads zeros; a long offset of 0 follows the rule of
  * lzs_decompress_batch_device.  Malformed input never makes a packet read or write outside its own slots
  * and its channel's state.
+ *
+ * SIZING THE OUTPUT.  lzs_decompressed_size_batch_device() (lzs_batch.h) applies unchanged to channel and burst packets: give
+ * it the packets (d_in, in_stride, d_in_len, in_len, npackets as here) and a limit, and it reports for every packet the
+ * d_out_len[b] and d_status[b] this call and the burst call below would write with out_cap = limit on a valid channel,
+ * whatever the channel's history -- a packet's length does not depend on the bytes it copies.  With limit = 0xFFFFFFFF these
+ * are the packets' true sizes: what out_cap, or an output tensor, has to hold before lzs_decompress_channels*_device is
+ * called.  It sees no slot, so it never reports ERROR and changes no history.
  */
 int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
                                    const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,

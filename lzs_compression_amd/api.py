@@ -104,6 +104,9 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "lzs_channels_burst_split_work_bytes"):
             L.lzs_channels_burst_split_work_bytes.restype = _sz
             L.lzs_channels_burst_split_work_bytes.argtypes = [_sz, _sz, _sz]
+        if hasattr(L, "lzs_decompressed_size_batch_device"):      # (an older build named by LZS_LIBRARY, for A/B runs, has none)
+            L.lzs_decompressed_size_batch_device.restype = ctypes.c_int
+            L.lzs_decompressed_size_batch_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp]
         _lib = L
     return _lib
 
@@ -298,6 +301,60 @@ def compact(slots, lengths, stream=None, dense=None, offsets=None):
                                     slots.stride(0) if nb > 1 else slots.shape[1],
                                     lengths.data_ptr(), nb, _stream_handle(stream)))
     return dense, offsets
+
+
+# -------------------------------------------------- sizes before decoding (lzs_batch.h)
+SIZE_LIMIT_NONE = 0xFFFFFFFF        # limit of the size query that asks for the true size
+
+
+def decompressed_sizes(x, in_len=None, limit: Optional[int] = None, size=None, status=None, stream=None):
+    """lzs_decompressed_size_batch_device(): what decoding each row of ``x`` (CUDA uint8 [nblocks, stride], ``in_len[b]`` bytes or
+    whole rows) at an output capacity of ``limit`` would give, without decoding -- a token walk, no output traffic.  ``limit``
+    None: 0xFFFFFFFF, the true size.  Returns (size int32 [nblocks] -- the bits of a uint32: a size of 2 GiB and more reads
+    negative --, status uint8 [nblocks]: the STATUS_* bits decompress_channels gives at ``out_capacity=limit``, STATUS_END_MARKER
+    for a whole stream); both may be passed in for reuse.  The same for channel and burst packets, whatever their channel's
+    history.  Asynchronous on ``stream``."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.stride(1) == 1, \
+        "blocks must be a CUDA uint8 tensor [nblocks, stride] with contiguous rows"
+    nb = x.shape[0]
+    limit = SIZE_LIMIT_NONE if limit is None else int(limit)
+    if size is None:
+        size = torch.empty(nb, dtype=torch.int32, device=x.device)
+    assert size.is_cuda and size.dtype == torch.int32 and size.numel() == nb and size.is_contiguous()
+    if status is None:
+        status = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.numel() == nb and status.is_contiguous()
+    if in_len is not None:
+        assert in_len.is_cuda and in_len.dtype == torch.int32 and in_len.numel() == nb
+    _check(lib().lzs_decompressed_size_batch_device(
+        size.data_ptr(), status.data_ptr(), x.data_ptr(), x.stride(0) if nb > 1 else x.shape[1],
+        None if in_len is None else in_len.data_ptr(), x.shape[1], limit, nb, _stream_handle(stream)))
+    return size, status
+
+
+def decompress_blocks_dense(x, in_len=None, stream=None):
+    """The rows of ``x`` (whole LZS streams, as for decompress_blocks) decoded into ONE dense byte string by a caller who does
+    not know their sizes: decompressed_sizes(), one host read of the largest size, decompress_blocks() at that capacity, then
+    compact().  Returns (dense uint8, offsets int64 [nblocks + 1]): block b is dense[offsets[b]:offsets[b + 1]].  Raises
+    ValueError naming the first block that does not end in an end marker (a truncated stream).  Peak device memory is
+    nblocks * max(size) bytes of slots beside the dense result of the same capacity; one host read, which waits for the
+    sizes."""
+    import torch
+    nb = x.shape[0]
+    size, status = decompressed_sizes(x, in_len, None, stream=stream)
+    if nb == 0:
+        return torch.empty(0, dtype=torch.uint8, device=x.device), torch.zeros(1, dtype=torch.int64, device=x.device)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        bad = status != STATUS_END_MARKER
+        first = bad.to(torch.uint8).argmax()
+        top = torch.stack([(size.to(torch.int64) & 0xFFFFFFFF).max(), bad.any().to(torch.int64), first.to(torch.int64),
+                           status[first].to(torch.int64)]).cpu()                         # the one host read
+    cap, any_bad, first_bad, its_status = (int(v) for v in top)
+    if any_bad:
+        raise ValueError(f"decompress_blocks_dense: block {first_bad} does not end in an end marker (status 0x{its_status:02x})")
+    slots, lens = decompress_blocks(x, in_len, cap, stream=stream)
+    return compact(slots, lens, stream=stream)
 
 
 # ------------------------------------------------------ incremental interface (lzs.h)

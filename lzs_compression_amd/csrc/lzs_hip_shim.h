@@ -178,6 +178,11 @@ int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_c
 int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
                            size_t slot_stride, const uint32_t *d_len, uint32_t nblocks,
                            void *stream);
+/* The size query (lzs_decoded_size.hip; lzs_size_query.c checks the arguments): d_size[b] / d_status[b] (or NULL) = the length
+ * and the LZS_D_STATUS_* bits the decoders give stream b at a capacity of `limit`, by a token walk, one lane a stream. */
+int lzs_hip_launch_decoded_size(uint32_t *d_size, uint8_t *d_status, const void *d_in, size_t in_stride,
+                                const uint32_t *d_in_len, uint32_t in_len, uint32_t limit, uint32_t nblocks,
+                                void *stream);
 
 #ifdef __cplusplus
 }
