@@ -80,6 +80,10 @@ class _Codec:
         return ctypes.cast(self._d, ctypes.c_void_p).value
 
 
+# what lzs_oracle_decompress_channel counts (the enum beside it), in order
+CHANNEL_COUNTERS = ("zero_bytes", "crossing", "overlap", "long_small", "long_zero", "cut", "nibble0_marker", "nibble0_full")
+
+
 class _Oracle(_Codec):
     def __init__(self):
         if not os.path.exists(_ORACLE_SO):
@@ -94,6 +98,11 @@ class _Oracle(_Codec):
         self.lib.lzs_oracle_trace.restype = ctypes.c_size_t
         self.lib.lzs_oracle_trace.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                               ctypes.c_size_t]
+        self.lib.lzs_oracle_decompress_channel.restype = ctypes.c_size_t
+        self.lib.lzs_oracle_decompress_channel.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+            ctypes.c_void_p, ctypes.c_void_p]
 
     def compress_brute(self, data: bytes, cap: Optional[int] = None) -> bytes:
         return self._call(self._lzs_oracle_compress_brute, data,
@@ -105,6 +114,33 @@ class _Oracle(_Codec):
         rec = np.zeros((max_tok, 3), dtype=np.uint32)
         n = self.lib.lzs_oracle_trace(ctypes.addressof(src), len(data), rec.ctypes.data, max_tok)
         return rec[:min(n, max_tok)]
+
+    def decompress_channel(self, hist: bytes, data: bytes, cap: int, counters: Optional[np.ndarray] = None,
+                           trace: bool = False):
+        """One packet of a channel through the plain model of include/lzs/lzs_channels.h (lzs_oracle_decompress_channel):
+        ``hist`` is the channel's history (at most 2047 bytes), ``cap`` the output capacity.  Returns (output bytes, status
+        byte, new history) -- and, with ``trace``, the token list [(output position, offset or 0, bytes produced, bit
+        position)] and the bit at which the packet stopped (its marker's first bit, if it stopped at one).  ``counters``: a
+        uint64 array of len(CHANNEL_COUNTERS) that the call adds to."""
+        assert len(hist) <= 2047
+        room = min(cap, 30 * len(data) + 16)          # a nibble gives at most 15 bytes: no packet decodes to more
+        src = ctypes.create_string_buffer(bytes(data), len(data) + 1)
+        old = ctypes.create_string_buffer(bytes(hist), len(hist) + 1)
+        dst = ctypes.create_string_buffer(room + 1)
+        new = ctypes.create_string_buffer(2048)
+        new_h, ntok, status, stop = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint8(0), ctypes.c_uint64(0)
+        if counters is not None:
+            assert counters.dtype == np.uint64 and counters.size == len(CHANNEL_COUNTERS) and counters.flags.c_contiguous
+        max_tok = 2 * len(data) + 1 if trace else 0   # no token is shorter than four bits
+        rec = np.zeros((max_tok, 4), dtype=np.uint32) if trace else None
+        n = self.lib.lzs_oracle_decompress_channel(
+            ctypes.addressof(dst), cap, ctypes.addressof(src), len(data), ctypes.addressof(old), len(hist),
+            ctypes.addressof(new), ctypes.addressof(new_h), ctypes.addressof(status),
+            None if counters is None else counters.ctypes.data, None if rec is None else rec.ctypes.data, max_tok,
+            ctypes.addressof(ntok), ctypes.addressof(stop))
+        assert n <= room
+        got = (dst.raw[:n], int(status.value), new.raw[:new_h.value])
+        return got + (rec[:ntok.value], int(stop.value)) if trace else got
 
 
 _oracle: Optional[_Oracle] = None

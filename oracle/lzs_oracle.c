@@ -343,3 +343,207 @@ size_t lzs_oracle_trace(const uint8_t *in, size_t n, uint32_t *rec, size_t max_t
     }
     return t;
 }
+
+/* ------------------------------------------------------------------ */
+/* One packet of a channel (include/lzs/lzs_channels.h: "Device-pointer */
+/* channel decompression", and the status rule of lzs_batch.h), a bit   */
+/* at a time.  The channel's history hist[0, h), h <= 2047, lies before */
+/* the packet's output; what lies before the history reads as zero.     */
+/*                                                                      */
+/*  - The packet stops at its first end marker, at the end of its bits, */
+/*    or at the capacity.  A token that lacks some of its bits, or that */
+/*    finds no room at all, stops the packet and is not consumed.       */
+/*  - The end marker needs no room.  It counts (END_MARKER) unless a    */
+/*    copy was cut at the capacity before it; it also counts behind the */
+/*    closing nibble 0 of a copy that exactly filled the output.        */
+/*  - A long offset of 0 takes its 13 bits and copies nothing.          */
+/*  - Status: END_MARKER (0x04) if the marker counted, else             */
+/*    NO_OUTPUT_BUFFER_SPACE (0x08) if the output is full, else         */
+/*    INPUT_STARVED | INPUT_FINISHED (0x03).                            */
+/*  - The new history is the last min(2047, h + produced) bytes of      */
+/*    history | output, whatever stopped the packet.                    */
+/*                                                                      */
+/* counters[] (may be NULL) are ADDED to, so that a test can prove its  */
+/* inputs reached the edges.  trace[] (may be NULL) receives up to      */
+/* max_tok records {output position, offset (0 = literal), bytes        */
+/* produced, bit position}, one a token (a copy with all its nibbles    */
+/* is one token), and *ntok the token count.  *stop_bit (may be NULL)   */
+/* receives the bit at which the packet stopped: the marker's first bit */
+/* if it stopped at one.                                                */
+/* ------------------------------------------------------------------ */
+enum {
+    CH_ZERO_BYTES = 0,   /* bytes read as zero from before the history              */
+    CH_CROSSING,         /* copies whose source runs from the history into the packet */
+    CH_OVERLAP,          /* copies with offset < length                              */
+    CH_LONG_SMALL,       /* offsets 1..127 written in the 11-bit form                */
+    CH_LONG_ZERO,        /* long offset 0 tokens taken                               */
+    CH_CUT,              /* copies cut at the capacity                               */
+    CH_NIBBLE0_MARKER,   /* closing nibble 0 followed by a counted marker            */
+    CH_NIBBLE0_FULL,     /* ... of which: the copy had exactly filled the output     */
+    CH_COUNTERS
+};
+
+typedef struct {
+    size_t   start;      /* output position of the open copy token's first byte */
+    size_t   rec;        /* its record in the trace */
+    unsigned off;
+    int      open, from_history, from_packet;
+} copy_t;
+
+static void copy_close(copy_t *t, size_t count, uint64_t *ctr)
+{
+    if (!t->open)
+        return;
+    t->open = 0;
+    if (!ctr)
+        return;
+    if (t->from_history && t->from_packet)
+        ctr[CH_CROSSING]++;
+    if (count - t->start > t->off)
+        ctr[CH_OVERLAP]++;
+}
+
+size_t lzs_oracle_decompress_channel(uint8_t *out, size_t cap, const uint8_t *in, size_t n,
+                                     const uint8_t *hist, size_t h,
+                                     uint8_t *new_hist, size_t *new_h, uint8_t *status,
+                                     uint64_t *counters, uint32_t *trace, size_t max_tok, size_t *ntok,
+                                     uint64_t *stop_bit)
+{
+    cursor_t r = { in, (uint64_t)n * 8u, 0 };
+    size_t   count = 0, tok = 0;
+    int      extended = 0, cut = 0, marker = 0;
+    copy_t   t = { 0, 0, 0, 0, 0, 0 };
+
+    for (;;) {
+        size_t   room = cap - count;
+        size_t   at_start = count;
+        uint64_t bit_start = r.at;
+        unsigned len;
+
+        if (extended) {
+            /* a closing nibble 0 and the marker right behind it: the packet is whole even with no room left */
+            if (!cut && bits_left(&r) >= 13 && peek_bits(&r, 13) == 0x180) {
+                marker = 1;
+                r.at += 4;
+                if (counters) {
+                    counters[CH_NIBBLE0_MARKER]++;
+                    if (room == 0)
+                        counters[CH_NIBBLE0_FULL]++;
+                }
+                break;
+            }
+            if (bits_left(&r) < 4 || room == 0)
+                break;
+            len = take_bits(&r, 4);
+            if (len != NIBBLE_MAX)
+                extended = 0;
+        } else {
+            copy_close(&t, count, counters);
+            if (bits_left(&r) >= 1 && peek_bits(&r, 1) == 0) {          /* literal */
+                if (bits_left(&r) < 9 || room == 0)
+                    break;
+                out[count++] = (uint8_t)take_bits(&r, 9);
+                if (trace && tok < max_tok) {
+                    trace[4 * tok + 0] = (uint32_t)at_start; trace[4 * tok + 1] = 0;
+                    trace[4 * tok + 2] = 1;                  trace[4 * tok + 3] = (uint32_t)bit_start;
+                }
+                tok++;
+                continue;
+            }
+            if (bits_left(&r) < 2)
+                break;
+            unsigned head, off;
+            if (peek_bits(&r, 2) == 3) {                                 /* short offset */
+                if (bits_left(&r) < 9)
+                    break;
+                off = peek_bits(&r, 9) & 0x7F;
+                head = 9;
+                if (off == 0) {                                          /* the end marker: needs no room */
+                    marker = !cut;
+                    break;
+                }
+            } else {                                                     /* long offset */
+                if (bits_left(&r) < 13)
+                    break;
+                off = peek_bits(&r, 13) & 0x7FF;
+                head = 13;
+                if (off == 0) {                                          /* 13 bits, no copy */
+                    if (room == 0)
+                        break;
+                    r.at += 13;
+                    if (counters)
+                        counters[CH_LONG_ZERO]++;
+                    if (trace && tok < max_tok) {
+                        trace[4 * tok + 0] = (uint32_t)at_start; trace[4 * tok + 1] = 0;
+                        trace[4 * tok + 2] = 0;                  trace[4 * tok + 3] = (uint32_t)bit_start;
+                    }
+                    tok++;
+                    continue;
+                }
+            }
+            /* length: 00 01 10 -> 2 3 4 ; 11xy -> 5 6 7 8, then nibbles while they are 15 */
+            unsigned width;
+            if (bits_left(&r) < head + 2)
+                break;
+            r.at += head;
+            unsigned code = peek_bits(&r, 4);
+            if (code < 0xC) { len = 2 + (code >> 2); width = 2; }
+            else            { len = 5 + (code - 0xC); width = 4; }
+            if (bits_left(&r) < width || room == 0) {
+                r.at = bit_start;
+                break;
+            }
+            r.at += width;
+            if (counters && head == 13 && off <= SHORT_MAX)
+                counters[CH_LONG_SMALL]++;
+            extended = (len == TOKEN_MAX);
+            t.start = count; t.off = off; t.open = 1; t.from_history = t.from_packet = 0;
+            t.rec = tok++;
+            if (trace && t.rec < max_tok) {
+                trace[4 * t.rec + 0] = (uint32_t)count; trace[4 * t.rec + 1] = off;
+                trace[4 * t.rec + 2] = 0;               trace[4 * t.rec + 3] = (uint32_t)bit_start;
+            }
+        }
+
+        /* the bytes of this code or nibble, as many as there is room for */
+        for (unsigned i = 0; i < len; i++) {
+            if (count == cap) {
+                cut = 1;
+                if (counters)
+                    counters[CH_CUT]++;
+                break;
+            }
+            uint8_t v = 0;
+            if (count >= t.off) {
+                v = out[count - t.off];
+                t.from_packet = 1;
+            } else {
+                size_t back = t.off - count;                             /* 1 = the history's newest byte */
+                t.from_history = 1;
+                if (back <= h)
+                    v = hist[h - back];
+                else if (counters)
+                    counters[CH_ZERO_BYTES]++;
+            }
+            out[count++] = v;
+        }
+        if (trace && t.rec < max_tok)
+            trace[4 * t.rec + 2] = (uint32_t)(count - t.start);
+    }
+    copy_close(&t, count, counters);
+
+    *status = marker ? 0x04 : (count >= cap ? 0x08 : 0x03);
+    if (ntok)
+        *ntok = tok;
+    if (stop_bit)
+        *stop_bit = r.at;
+
+    /* the last min(2047, h + count) bytes of history | output, oldest first */
+    size_t keep = h + count < WINDOW ? h + count : WINDOW;
+    for (size_t i = 0; i < keep; i++) {
+        size_t back = keep - i;                                          /* distance from the end of history | output */
+        new_hist[i] = back <= count ? out[count - back] : hist[h - (back - count)];
+    }
+    *new_h = keep;
+    return count;
+}

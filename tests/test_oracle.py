@@ -210,3 +210,20 @@ def test_reference_own_unit_tests_pass():
         if os.path.exists(p):
             r = subprocess.run([p], capture_output=True, text=True)
             assert r.returncode == 0 and "0 Failures" in r.stdout, r.stdout
+
+
+def test_channel_model_on_synthesised_packets():
+    """lzs_oracle_decompress_channel on a few token-built packets (tests/test_channel_model.py holds it to everything else; here
+    it also runs in the sanitizer builds of the checkers): the history law, counters and trace at several capacities."""
+    import test_channel_model as M
+    rng = np.random.default_rng(7)
+    counters = np.zeros(len(oracle.CHANNEL_COUNTERS), dtype=np.uint64)
+    packets = M.synth_batch(rng, 80) + [M.synth_big_copy(rng, 5000)]
+    for i, p in enumerate(packets):
+        hist = M.random_hist(rng, int(rng.choice(M.HIST_LENS)))
+        for cap in (6000, 100, 1, 0):
+            out, st, new, tokens, stop = O.decompress_channel(hist, p, cap, counters, trace=True)
+            assert new == (hist + out)[-2047:] and st in (M.END, M.FULL, M.STARVED) and stop <= 8 * len(p), (i, cap)
+            assert sum(int(t[2]) for t in tokens) == len(out) <= cap, (i, cap)
+            assert O.decompress_channel(b"", p, cap)[0] == O.decompress(p, cap), (i, cap)
+    assert counters.all(), counters
