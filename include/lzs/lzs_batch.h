@@ -174,6 +174,51 @@ int lzs_compact_device(void *d_dense, uint64_t *d_offsets, const void *d_slots, 
                        const uint32_t *d_len, size_t nblocks, void *hip_stream);
 
 /*
+ * PACKED streams and packed outputs: blocks addressed by OFFSETS instead of a stride -- what lzs_compact_device() produces, how
+ * a shard arrives over RCCL, how a file of concatenated streams with a length table or a drained packet queue lies in memory.
+ * ("Ragged" in this library means per-block lengths in a strided array; this is the other thing.)  The three calls below and
+ * lzs_decompress_channels_packed_device() (lzs_channels.h) share their addressing:
+ *
+ *   input   block b starts at d_in + d_in_off[b].  With d_in_len NULL its length is d_in_off[b + 1] - d_in_off[b]: nblocks + 1
+ *           entries are read and must not decrease.  With d_in_len given its length is d_in_len[b]: only nblocks entries of
+ *           d_in_off are read, in any order.  Any alignment; nothing is read outside the aligned 32-bit words that hold the
+ *           block's own bytes -- by the size query and by the decoders.
+ *   output  block b is written at d_out + d_out_off[b]; its room -- its out_cap -- is d_out_off[b + 1] - d_out_off[b], clamped
+ *           to 0xFFFFFFFF.  nblocks + 1 entries are always read.  Any alignment.
+ *   result  bytes [0, d_out_len[b]) of the block's room, d_out_len[b], d_status[b] (and the channel's slot) are byte for byte
+ *           what the strided call gives for that stream alone with out_cap = its room: lzs_decompressed_size_batch_device()
+ *           with the same limit, lzs_decompress_batch_device(), lzs_decompress_channels_device().
+ *   containment  block b stores to d_out[d_out_off[b] .. d_out_off[b] + d_out_len[b]) and to NO other byte of d_out: not to
+ *           the rest of its room, not to its neighbours' first and last bytes, which lie right beside its own here.
+ *   not a block  an entry whose input or output offsets decrease, or whose length exceeds LZS_BLOCK_MAX: d_out_len[b] = 0
+ *           (d_size[b] = 0), status ERROR (0x10) where there is a status array, nothing of it is read or written, its channel's
+ *           slot is untouched, and the other blocks are unaffected.
+ *
+ * All four are asynchronous on `hip_stream`, allocate nothing, do not synchronise and may be captured into a hipGraph (the
+ * note on the very first call into the library applies).  Checked before the device is asked (LZS_E_ARG, the call's name in
+ * lzs_last_error()): a required pointer that is NULL, an offset array that is not 8-byte aligned, d_out_len / d_size being the
+ * array d_in_len, nblocks > 0x7FFFFFFF, limit > 0xFFFFFFFF, a bad align.  Offsets are uint64_t; a torch int64 tensor holds the
+ * same bits.  Not offered: packed compression, packed bursts, host-buffer entries.
+ *
+ * lzs_offsets_from_sizes_device: d_offsets[0] = 0, d_offsets[b + 1] = d_offsets[b] + round_up(d_size[b], align); nblocks + 1
+ * entries, the total in d_offsets[nblocks]; nblocks == 0 writes d_offsets[0] = 0.  `align`: a power of two from 1 to 256 -- 16
+ * gives every block a 16-byte-aligned start.  The scan of lzs_compact_device() with padding.
+ */
+int lzs_offsets_from_sizes_device(uint64_t *d_offsets, const uint32_t *d_size, size_t align, size_t nblocks, void *hip_stream);
+
+/* lzs_decompressed_size_batch_device() for packed streams: `limit` as there, d_status may be NULL (ERROR only for an entry
+ * that is not a block); nblocks == 0 is LZS_OK and touches nothing. */
+int lzs_decompressed_size_packed_device(uint32_t *d_size, uint8_t *d_status, const void *d_in, const uint64_t *d_in_off,
+                                        const uint32_t *d_in_len, size_t limit, size_t nblocks, void *hip_stream);
+
+/* lzs_decompress_batch_device() from packed streams to packed outputs.  Sizes from the call above, offsets from
+ * lzs_offsets_from_sizes_device(), one allocation of d_offsets[nblocks] bytes, this call: the decoded batch costs its own
+ * bytes of device memory and no slots (INTEGRATION.md has the lines).  Eight streams share a wavefront; where their input lies
+ * more than 4 GiB apart they are decoded one after the other, which is slow and right. */
+int lzs_decompress_batch_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                       const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks, void *hip_stream);
+
+/*
  * Host-buffer batches: same per-block contract, buffers in host memory.  The call
  * stages through device memory it allocates and frees itself and returns when the
  * results are in `out` / `out_len`.  in_len_each may be NULL (every block in_len bytes).

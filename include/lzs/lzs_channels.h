@@ -96,6 +96,19 @@ int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_ca
                                    size_t npackets, void *hip_stream);
 
 /*
+ * lzs_decompress_channels_device() from PACKED packets to packed outputs: packet b lies at d_in + d_in_off[b] and is decoded to
+ * d_out + d_out_off[b] with d_out_off[b + 1] - d_out_off[b] bytes of room -- the addressing, the containment, the entries that
+ * are not a block (ERROR, d_out_len[b] = 0, the channel's slot untouched) and the argument checks are those of "PACKED streams"
+ * in lzs_batch.h; d_states must be given and 4-byte aligned.  One packet per channel per call: the rule on repeated channels
+ * above holds.  Every packet's bytes, d_out_len[b], d_status[b] and its channel's slot are byte for byte what
+ * lzs_decompress_channels_device() gives for that packet alone with out_cap = its room; a slot with hist_len > 2047 gets ERROR
+ * and d_out_len[b] = 0 as there.  lzs_decompressed_size_packed_device() sizes the rooms.  Packed bursts are not offered.
+ */
+int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                          const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                          void *d_states, uint8_t *d_status, size_t npackets, void *hip_stream);
+
+/*
  * BURSTS: many packets per channel in one call -- a queue drained as it stands, busy links with many packets, most with none.
  *
  * The arguments are those of the calls above, and three more: nchannels (the slots in d_states), and a device work area

@@ -12,6 +12,7 @@ from .api import (IncrementalCompressor, IncrementalDecompressor, LzsError, back
                   decompress_stream, decompressed_max, incremental_compress, last_error, lib, release_thread_cache)
 from .api import (STATUS_END_MARKER, STATUS_ERROR, STATUS_INPUT_FINISHED, STATUS_INPUT_STARVED, STATUS_NO_OUTPUT_BUFFER_SPACE)
 from .api import decompress_blocks_dense, decompressed_sizes
+from .api import decompress_channels_packed, decompress_dense, decompress_packed, decompressed_sizes_packed, offsets_from_sizes
 from . import workload
 
 __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_bytes", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
@@ -20,4 +21,5 @@ __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_byt
            "compress_stream", "compressed_max", "decompress", "decompress_batch", "decompress_blocks", "decompress_blocks_sync", "decompress_concat",
            "decompress_stream", "decompressed_max", "incremental_compress", "last_error", "lib", "release_thread_cache", "workload",
            "STATUS_END_MARKER", "STATUS_ERROR", "STATUS_INPUT_FINISHED", "STATUS_INPUT_STARVED", "STATUS_NO_OUTPUT_BUFFER_SPACE",
-           "decompress_blocks_dense", "decompressed_sizes"]
+           "decompress_blocks_dense", "decompressed_sizes",
+           "decompress_channels_packed", "decompress_dense", "decompress_packed", "decompressed_sizes_packed", "offsets_from_sizes"]

@@ -107,6 +107,15 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "lzs_decompressed_size_batch_device"):      # (an older build named by LZS_LIBRARY, for A/B runs, has none)
             L.lzs_decompressed_size_batch_device.restype = ctypes.c_int
             L.lzs_decompressed_size_batch_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp]
+        if hasattr(L, "lzs_decompress_batch_packed_device"):      # (the same: the packed calls)
+            L.lzs_offsets_from_sizes_device.restype = ctypes.c_int
+            L.lzs_offsets_from_sizes_device.argtypes = [_vp, _vp, _sz, _sz, _vp]
+            L.lzs_decompressed_size_packed_device.restype = ctypes.c_int
+            L.lzs_decompressed_size_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp]
+            L.lzs_decompress_batch_packed_device.restype = ctypes.c_int
+            L.lzs_decompress_batch_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+            L.lzs_decompress_channels_packed_device.restype = ctypes.c_int
+            L.lzs_decompress_channels_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
         _lib = L
     return _lib
 
@@ -339,7 +348,7 @@ def decompress_blocks_dense(x, in_len=None, stream=None):
     compact().  Returns (dense uint8, offsets int64 [nblocks + 1]): block b is dense[offsets[b]:offsets[b + 1]].  Raises
     ValueError naming the first block that does not end in an end marker (a truncated stream).  Peak device memory is
     nblocks * max(size) bytes of slots beside the dense result of the same capacity; one host read, which waits for the
-    sizes."""
+    sizes.  decompress_dense() does the same from packed streams without the slots."""
     import torch
     nb = x.shape[0]
     size, status = decompressed_sizes(x, in_len, None, stream=stream)
@@ -355,6 +364,141 @@ def decompress_blocks_dense(x, in_len=None, stream=None):
         raise ValueError(f"decompress_blocks_dense: block {first_bad} does not end in an end marker (status 0x{its_status:02x})")
     slots, lens = decompress_blocks(x, in_len, cap, stream=stream)
     return compact(slots, lens, stream=stream)
+
+
+# ------------------------------- packed streams, packed outputs (lzs_batch.h, lzs_channels.h)
+def _packed_input(data, in_off, in_len, nb=None):
+    """The checks of a packed input; returns the number of blocks (``nb`` if given)."""
+    import torch
+    assert data.is_cuda and data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous(), \
+        "packed streams are one contiguous CUDA uint8 tensor"
+    assert in_off.is_cuda and in_off.dtype == torch.int64 and in_off.dim() == 1 and in_off.is_contiguous(), \
+        "offsets are a contiguous CUDA int64 tensor"
+    if in_len is not None:
+        assert in_len.is_cuda and in_len.dtype == torch.int32 and in_len.dim() == 1 and in_len.is_contiguous()
+        n = in_len.numel() if nb is None else nb
+        assert in_len.numel() == n and in_off.numel() >= n
+    else:
+        n = max(in_off.numel() - 1, 0) if nb is None else nb
+        assert in_off.numel() >= n + 1, "without in_len the offsets have nblocks + 1 entries"
+    return n
+
+
+def offsets_from_sizes(size, align: int = 1, offsets=None, stream=None):
+    """lzs_offsets_from_sizes_device(): offsets[0] = 0, offsets[b + 1] = offsets[b] + size[b] rounded up to ``align`` (a power of
+    two from 1 to 256) -- int64 [nblocks + 1], the total in offsets[-1].  ``size``: CUDA int32 [nblocks], read as uint32 (what
+    decompressed_sizes_packed returns).  Asynchronous on ``stream``."""
+    import torch
+    assert size.is_cuda and size.dtype == torch.int32 and size.dim() == 1 and size.is_contiguous()
+    nb = size.numel()
+    if offsets is None:
+        offsets = torch.empty(nb + 1, dtype=torch.int64, device=size.device)
+    assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.numel() == nb + 1 and offsets.is_contiguous()
+    _check(lib().lzs_offsets_from_sizes_device(offsets.data_ptr(), size.data_ptr(), int(align), nb, _stream_handle(stream)))
+    return offsets
+
+
+def decompressed_sizes_packed(data, in_off, in_len=None, limit: Optional[int] = None, size=None, status=None, stream=None):
+    """lzs_decompressed_size_packed_device(): decompressed_sizes() for packed streams -- block b is the ``in_len[b]`` bytes of
+    ``data`` (CUDA uint8, one dimension) at ``in_off[b]`` (int64), or data[in_off[b]:in_off[b + 1]] without ``in_len``.  Returns
+    (size int32 [nblocks], status uint8 [nblocks]); an entry that is not a block (decreasing offsets, a length above 3 GiB) has
+    size 0 and STATUS_ERROR.  Asynchronous on ``stream``."""
+    import torch
+    nb = _packed_input(data, in_off, in_len)
+    limit = SIZE_LIMIT_NONE if limit is None else int(limit)
+    if size is None:
+        size = torch.empty(nb, dtype=torch.int32, device=data.device)
+    assert size.is_cuda and size.dtype == torch.int32 and size.numel() == nb and size.is_contiguous()
+    if status is None:
+        status = torch.empty(nb, dtype=torch.uint8, device=data.device)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.numel() == nb and status.is_contiguous()
+    _check(lib().lzs_decompressed_size_packed_device(
+        size.data_ptr(), status.data_ptr(), _ptr(data, in_off), in_off.data_ptr(), None if in_len is None else in_len.data_ptr(),
+        limit, nb, _stream_handle(stream)))
+    return size, status
+
+
+def _ptr(t, other):
+    """An empty tensor has no address, and the C calls want one: every block in it is empty and every room in it 0, so nothing is
+    read or written through the stand-in."""
+    return t.data_ptr() or other.data_ptr()
+
+
+def _packed_output(out, out_off):
+    import torch
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous()
+    assert out_off.is_cuda and out_off.dtype == torch.int64 and out_off.dim() == 1 and out_off.is_contiguous() and out_off.numel() >= 1
+    return out_off.numel() - 1
+
+
+def decompress_packed(data, in_off, out, out_off, in_len=None, out_len=None, stream=None):
+    """lzs_decompress_batch_packed_device(): block b (as for decompressed_sizes_packed) decoded to out[out_off[b]:out_off[b + 1]]
+    -- that slice is its room, its out_capacity.  ``out``: CUDA uint8, one dimension; ``out_off``: int64 [nblocks + 1].  Nothing of
+    ``out`` outside out[out_off[b] : out_off[b] + out_len[b]] is written.  Returns (out, out_len int32 [nblocks]).  Asynchronous."""
+    import torch
+    nb = _packed_output(out, out_off)
+    _packed_input(data, in_off, in_len, nb)
+    if out_len is None:
+        out_len = torch.empty(nb, dtype=torch.int32, device=data.device)
+    assert out_len.is_cuda and out_len.dtype == torch.int32 and out_len.numel() == nb and out_len.is_contiguous()
+    _check(lib().lzs_decompress_batch_packed_device(
+        _ptr(out, out_off), out_off.data_ptr(), out_len.data_ptr(), _ptr(data, in_off), in_off.data_ptr(),
+        None if in_len is None else in_len.data_ptr(), nb, _stream_handle(stream)))
+    return out, out_len
+
+
+def decompress_channels_packed(data, in_off, channels, states, out, out_off, in_len=None, out_len=None, status=None, stream=None):
+    """lzs_decompress_channels_packed_device(): decompress_channels() from packed packets to packed outputs, one packet per
+    channel per call (``channels``: int32 [npackets] or None for packet b on channel b; ``states`` from new_channel_states).
+    Returns (out, out_len int32, status uint8).  Asynchronous."""
+    import torch
+    nb = _packed_output(out, out_off)
+    _packed_input(data, in_off, in_len, nb)
+    if out_len is None:
+        out_len = torch.empty(nb, dtype=torch.int32, device=data.device)
+    assert out_len.is_cuda and out_len.dtype == torch.int32 and out_len.numel() == nb and out_len.is_contiguous()
+    if status is None:
+        status = torch.empty(nb, dtype=torch.uint8, device=data.device)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.numel() == nb and status.is_contiguous()
+    if channels is not None:
+        assert channels.is_cuda and channels.dtype == torch.int32 and channels.numel() == nb and channels.is_contiguous()
+    assert states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()
+    _check(lib().lzs_decompress_channels_packed_device(
+        _ptr(out, out_off), out_off.data_ptr(), out_len.data_ptr(), _ptr(data, in_off), in_off.data_ptr(),
+        None if in_len is None else in_len.data_ptr(), None if channels is None else channels.data_ptr(), states.data_ptr(),
+        status.data_ptr(), nb, _stream_handle(stream)))
+    return out, out_len, status
+
+
+def decompress_dense(data, in_off, in_len=None, align: int = 1, stream=None):
+    """Packed streams (whole LZS streams, as for decompressed_sizes_packed) decoded into ONE dense byte string by a caller who
+    does not know their sizes: decompressed_sizes_packed(), offsets_from_sizes(), one host read -- the total, and the first
+    block that does not end in its end marker --, one allocation of exactly the total, decompress_packed().  Returns (dense
+    uint8 [total], offsets int64 [nblocks + 1]); block b is dense[offsets[b] : offsets[b] + size[b]], and with ``align`` 1 that is
+    dense[offsets[b]:offsets[b + 1]].  Raises ValueError naming the first block that does not end in an end marker.
+
+    Peak device memory: the result (offsets[-1] bytes) and two small arrays, the sizes (int32 [nblocks], also the decoder's
+    lengths) and the offsets (int64 [nblocks + 1]); what the check of the statuses needs is smaller than those two and is
+    released before the result is allocated.  No slots: decompress_blocks_dense() needs nblocks * max(size) bytes of them
+    beside its result.  One host read, which waits for the sizes."""
+    import torch
+    nb = _packed_input(data, in_off, in_len)
+    if nb == 0:
+        return torch.empty(0, dtype=torch.uint8, device=data.device), torch.zeros(1, dtype=torch.int64, device=data.device)
+    size, status = decompressed_sizes_packed(data, in_off, in_len, None, stream=stream)
+    offsets = offsets_from_sizes(size, align, stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        bad = status != STATUS_END_MARKER
+        first = bad.to(torch.uint8).argmax()
+        top = torch.stack([offsets[nb], bad.any().to(torch.int64), first.to(torch.int64), status[first].to(torch.int64)]).cpu()   # the one host read
+        del bad, first
+    total, any_bad, first_bad, its_status = (int(v) for v in top)
+    del status, top
+    if any_bad:
+        raise ValueError(f"decompress_dense: block {first_bad} does not end in an end marker (status 0x{its_status:02x})")
+    dense = torch.empty(total, dtype=torch.uint8, device=data.device)
+    decompress_packed(data, in_off, dense, offsets, in_len=in_len, out_len=size, stream=stream)
+    return dense, offsets
 
 
 # ------------------------------------------------------ incremental interface (lzs.h)

@@ -853,15 +853,47 @@ __device__ __forceinline__ uint4 dec_ring_load16(const uint8_t *ring8, uint32_t 
                       __builtin_amdgcn_alignbyte(v[3], v[2], s), __builtin_amdgcn_alignbyte(v[4], v[3], s));
 }
 
+// PACKED (kernels/decompress_packed.inc; DESIGN.md 3.14): stream b lies at in + in_off[b] -- in_len[b] bytes, or up to
+// in_off[b + 1] without lengths -- and decodes to out + out_off[b] with out_off[b + 1] - out_off[b] bytes of room.
+struct DecPacked {
+    const uint64_t *in_off = nullptr, *out_off = nullptr;
+};
+
+// (PACKED) entry b: where it lies, how long it is, where it goes and its room (a 64-bit difference, clamped).  False: not a
+// block -- offsets that decrease, a length above LZS_BLOCK_MAX -- of which nothing is read or written.
+__device__ __forceinline__ bool dec_packed_entry(const DecPacked &pk, const uint32_t *in_len, uint32_t b, uint64_t &from, uint32_t &n,
+                                                 uint64_t &to, uint32_t &room)
+{
+    from = pk.in_off[b];
+    to = pk.out_off[b];
+    const uint64_t to_end = pk.out_off[b + 1u];
+    bool ok = to_end >= to;
+    uint64_t len;
+    if (in_len) {
+        len = in_len[b];
+    } else {
+        const uint64_t next = pk.in_off[b + 1u];
+        ok = ok && next >= from;
+        len = next - from;
+    }
+    ok = ok && len <= 0xC0000000ull;                               // LZS_BLOCK_MAX
+    const uint64_t space = to_end - to;
+    n = ok ? (uint32_t)len : 0u;
+    room = ok ? (space < 0xFFFFFFFFull ? (uint32_t)space : 0xFFFFFFFFu) : 0u;
+    return ok;
+}
+
 // The same decoder with its flags as masks: the one-word feed with one token a trip or two (the 96-bit form stays above).
-template <bool TWO, bool WIDE, bool CONCAT, bool CHAN = false, bool RUN = false>
+template <bool TWO, bool WIDE, bool CONCAT, bool CHAN = false, bool RUN = false, bool PACKED = false>
 __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
                                       uint32_t *__restrict__ out_len,
                                       const uint8_t *__restrict__ in, size_t in_stride,
                                       const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
-                                      uint32_t nblocks, uint32_t concat_arg, uint32_t per_wave, DecChan ch = DecChan())
+                                      uint32_t nblocks, uint32_t concat_arg, uint32_t per_wave, DecChan ch = DecChan(),
+                                      DecPacked pk = DecPacked())
 {
     static_assert(CHAN || !RUN, "a run is a channel's");
+    static_assert(!PACKED || (!RUN && !CONCAT), "packed streams are single blocks or single packets");
     const uint32_t lane = threadIdx.x;
     const uint32_t g = lane / kDecLanes, j = lane % kDecLanes;
     const uint32_t b = blockIdx.x * per_wave + g;                  // per_wave: kDecGroups, or 1 (see the launcher)
@@ -873,6 +905,12 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint8_t *cst = nullptr;                                        // CHAN: the stream's state slot ...
     uint32_t hlen = 0;                                             // ... and its history's length (> 2047: not a state)
     uint32_t r_at = 0, r_end = 0;                                  // RUN: the run's sorted positions
+    uint64_t pk_from = 0, pk_to = 0;                               // PACKED: the entry's offsets, its length and its room
+    uint32_t pk_n = 0, pk_room = 0;
+    bool pk_block = false;
+    if constexpr (PACKED) {
+        if (b < nblocks) pk_block = dec_packed_entry(pk, in_len, b, pk_from, pk_n, pk_to, pk_room);
+    }
     if constexpr (RUN) {
         if (b < nblocks && g < per_wave && ch.run_key[b] != 0u) {
             r_at = ch.run_at[b];
@@ -884,22 +922,55 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
             }
         }
     } else if constexpr (CHAN) {
-        if (b < nblocks && g < per_wave) {
+        if (b < nblocks && g < per_wave && (!PACKED || pk_block)) {
             cst = ch.states + (size_t)(ch.channel ? ch.channel[b] : b) * kChanStateBytes;
             hlen = *reinterpret_cast<const uint32_t *>(cst);
         }
     }
     // (RUN: `live` is the run's here -- a channel id in range, a state -- and the current packet's in the loop below)
-    bool live = RUN ? (cst != nullptr && hlen <= kWindow) : (b < nblocks && g < per_wave && (!CHAN || hlen <= kWindow));
+    bool live = RUN ? (cst != nullptr && hlen <= kWindow) : (b < nblocks && g < per_wave && (!CHAN || hlen <= kWindow) && (!PACKED || pk_block));
     const bool live_run = live;
     uint32_t bb = live ? b : 0u;
     uint8_t *ring8 = reinterpret_cast<uint8_t *>(L.ring[g]);
     uint8_t *dummy8 = reinterpret_cast<uint8_t *>(&L.dummy[lane]);
-    const uint8_t *src = in + (size_t)bb * in_stride;
-    uint32_t n   = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
-    uint8_t *dst       = out + (size_t)bb * out_stride;
+    const uint8_t *src = PACKED ? in + pk_from : in + (size_t)bb * in_stride;
+    uint32_t n   = live ? (PACKED ? pk_n : (in_len ? in_len[bb] : in_len_uniform)) : 0u;
+    uint8_t *dst       = PACKED ? out + pk_to : out + (size_t)bb * out_stride;
     bool dst16   = ((uintptr_t)dst & 15u) == 0;
-    uint32_t cap = live ? out_cap : 0u;
+    uint32_t cap = live ? (PACKED ? pk_room : out_cap) : 0u;
+    // PACKED: an entry that is not decoded -- not a block, or (CHAN) a slot that is not a state -- has length 0 and is an
+    // ERROR; that is all that is written of it.  Then the wavefront's input extent: the descriptor of the loads below starts
+    // at the lowest first word of the streams that have bytes (pk_lo) and each of them lies pk_rel behind it; where the last of
+    // them ends more than 32 bits from there (pk_fits false) the groups take turns, one a trip of the loop below, each with a
+    // descriptor of its own stream -- slow, and right.
+    uint64_t pk_lo = 0;
+    uint32_t pk_rel = 0, pk_extent = 0;
+    bool pk_fits = true;
+    if constexpr (PACKED) {
+        if (b < nblocks && !live && j == 0u) {
+            out_len[b] = 0;
+            if constexpr (CHAN) { if (ch.status) ch.status[b] = 0x10u; }
+        }
+        const bool act = live && n != 0u;
+        const uint64_t first = (uint64_t)(uintptr_t)src & ~(uint64_t)3;
+        uint64_t lo = ~0ull, hi = 0;
+#pragma unroll
+        for (uint32_t gg = 0; gg < kDecGroups; gg++) {
+            const int at = (int)(gg * kDecLanes);
+            const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)(act ? 1u : 0u), at);
+            const uint64_t f = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(first >> 32), at) << 32) |
+                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at);
+            const uint64_t e = f + (uint32_t)__builtin_amdgcn_readlane((int)(((uint32_t)(uintptr_t)src & 3u) + n), at);   // (3 + LZS_BLOCK_MAX fits)
+            if (a != 0u && f < lo) lo = f;
+            if (a != 0u && e > hi) hi = e;
+        }
+        if (hi == 0) lo = 0;                                       // (no stream has bytes: an empty extent, nothing is read)
+        pk_lo = lo;
+        pk_fits = hi - lo <= 0xFFFF0000ull;
+        pk_rel = act ? (uint32_t)(first - lo) : 0u;
+        pk_extent = (uint32_t)(hi - lo);
+    }
+    const bool live_all = live;
     if constexpr (RUN) {                                           // a run that is not decoded: every packet of it is an ERROR
         if (!live_run)
             for (uint32_t at = r_at + j; at < r_end; at += kDecLanes) {
@@ -928,6 +999,15 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint32_t produced = 0;                                         // (RUN) output of the run so far
     uint32_t pb = b;                                               // the packet
     for (uint32_t k = 0;; k++) {
+    if constexpr (PACKED) {
+        if (k > 0u && (pk_fits || k == kDecGroups)) break;
+        if (!pk_fits) {                                            // (too far apart: group k alone)
+            live = live_all && g == k;
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
+            n = live ? pk_n : 0u;
+            cap = live ? pk_room : 0u;
+        }
+    }
     if constexpr (RUN) {
         const uint32_t at = r_at + k;
         live = live_run && at < r_end;
@@ -955,25 +1035,59 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     const uint32_t b0 = blockIdx.x * per_wave;
     // (RUN: the packets of a trip lie anywhere in the input -- the launcher sees to it that all of it is one 32-bit extent, or
     // gives each wavefront one run)
-    const uint8_t *wave_in = RUN ? (per_wave == 1u ? src : in) : in + (size_t)b0 * in_stride;
-    const uintptr_t in_lo = (uintptr_t)wave_in & ~(uintptr_t)3;
+    const uint8_t *wave_in = PACKED ? nullptr : (RUN ? (per_wave == 1u ? src : in) : in + (size_t)b0 * in_stride);
+    uintptr_t in_lo = (uintptr_t)wave_in & ~(uintptr_t)3;
     const uint32_t rel = live ? (uint32_t)(RUN ? (per_wave == 1u ? (size_t)0 : (size_t)pb * in_stride) : (size_t)(b - b0) * in_stride) : 0u;      // my stream, from wave_in
     uint32_t wave_end = 0;
+    // (PACKED) where my stream's first word lies from in_lo, and the end of the last word that holds a byte of it: a lane loads
+    // nothing outside its own stream's words (see bload)
+    uint32_t pk_at = 0, pk_end = 0;
+    if constexpr (PACKED) {
+        if (pk_fits) {
+            in_lo = (uintptr_t)pk_lo;
+            wave_end = pk_extent;
+            pk_at = pk_rel;
+        } else {                                                   // group k's stream alone
+            const int at = (int)(k * kDecLanes);
+            const uintptr_t first = (uintptr_t)src & ~(uintptr_t)3;
+            in_lo = (uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)first >> 32), at) << 32) |
+                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at));
+            wave_end = (uint32_t)__builtin_amdgcn_readlane((int)(skew + n), at);
+        }
+        pk_end = n != 0u ? (pk_at + skew + n + 3u) & ~3u : 0u;
+    } else {
 #pragma unroll
     for (uint32_t gg = 0; gg < kDecGroups; gg++) {
         const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)(rel + n), (int)(gg * kDecLanes));
         wave_end = e > wave_end ? e : wave_end;
+    }
     }
     // (the descriptor is the same in every lane, and said to be: or the load sits in a loop over the distinct ones)
     const uintptr_t in_lo_u = ((uintptr_t)uniform((uint32_t)((uint64_t)in_lo >> 32)) << 32) | uniform((uint32_t)in_lo);
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void *)in_lo_u, 0, (int)uniform((wave_end + (uint32_t)((uintptr_t)wave_in & 3u) + 3u) & ~3u), 0x00020000);
     const auto bload = [&](uint32_t byte_off) {
+        if constexpr (PACKED) {
+            // sixteen bytes that lie in the lane's own stream's words as one load; what lies past them altogether from an
+            // offset past every extent (zeros, and no access); the piece the stream ends in word by word, where some lane is there
+            const bool whole = byte_off + 16u <= pk_end;
+            u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(whole ? byte_off : 0xFFFFFFF0u), 0, 0);
+            const bool part = !whole && byte_off < pk_end;
+            if (__builtin_amdgcn_ballot_w64(part) != 0ull) {
+                if (part) {
+                    v.x = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)byte_off, 0, 0);
+                    if (byte_off + 4u < pk_end) v.y = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off + 4u), 0, 0);
+                    if (byte_off + 8u < pk_end) v.z = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off + 8u), 0, 0);
+                }
+            }
+            return make_uint4(v.x, v.y, v.z, v.w);
+        } else {
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, 0);
         return make_uint4(v.x, v.y, v.z, v.w);
+        }
     };
     constexpr uint32_t kChunk = 16u * kDecLanes;                    // bytes
-    uint32_t nxt_off = (uint32_t)((uintptr_t)(src - skew) - in_lo) + 16u * j + kChunk;
+    uint32_t nxt_off = (PACKED ? pk_at : (uint32_t)((uintptr_t)(src - skew) - in_lo)) + 16u * j + kChunk;
     uint4 cur = bload(nxt_off - kChunk), nxt = bload(nxt_off);
     const uint32_t glane4 = (lane & ~(kDecLanes - 1u)) << 2;       // byte index of the group's lane 0 for ds_bpermute
     // A lane's four words ROTATE by one with every word its group takes, so that the word to feed next (word wi of the
@@ -1011,9 +1125,20 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint32_t nextw = fetch(wi);
     uint32_t nextw2 = WIDE ? fetch_after(wi) : 0u;                 // (WIDE: the word after it; only used when in the same chunk)
     uint32_t bits_lo = 0;                                          // (WIDE: bits 64..95 of the buffer, left-aligned)
-    uint32_t count = 0, flushed = 0, off = 0;
+    // PACKED: a stream's output starts anywhere, fifteen times in sixteen off a 16-byte boundary, where the drain below would
+    // store byte by byte.  So the drains start at the first boundary of dst, `head` bytes in: every piece is an aligned store
+    // fed from the window at an unaligned position (dec_ring_load16), and the head bytes go out byte by byte with the first
+    // drain, or with the tail if there is none.  (-DLZS_PACKED_BYTE_DRAIN: the strided calls' drain, for the measurement.)
+#ifdef LZS_PACKED_BYTE_DRAIN
+    constexpr bool kPackedHead = false;
+#else
+    constexpr bool kPackedHead = PACKED;
+#endif
+    const uint32_t head = kPackedHead ? (0u - (uint32_t)(uintptr_t)dst) & 15u : 0u;
+    uint32_t head_left = head;
+    uint32_t count = 0, flushed = head, off = 0;
     uint32_t m_ext = 0;                                            // "a length nibble follows", as a mask
-    uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? run_pos : 0u;  // count and flushed modulo kDecRing
+    uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? run_pos : head;  // count and flushed modulo kDecRing
     uint32_t m_done = live ? 0u : ~0u;                             // the stream has stopped, as a mask
     uint32_t m_eos = 0u;                                           // (CHAN) ... at an end marker
     uint32_t m_cut = 0u;                                           // (CHAN) a copy lost bytes to the room: no end marker counts after it
@@ -1229,18 +1354,22 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         m_done |= m_stop | (CONCAT ? 0u : m_endm);
 
         // ---- drain finished output, 16 bytes per lane at a time (the wave goes there when some group is due)
-        const bool due = count - flushed >= kDecDrain;
+        const bool due = kPackedHead ? (count - flushed >= kDecDrain && count >= flushed) : count - flushed >= kDecDrain;
         if (__builtin_amdgcn_ballot_w64(due) != 0ull) {
             if (due) {
+                if constexpr (kPackedHead) {                       // (the first drain: the window has not wrapped yet)
+                    for (uint32_t i = j; i < head_left; i += kDecLanes) dst[i] = ring8[i];
+                    head_left = 0;
+                }
 #pragma unroll
                 for (uint32_t piece = 0; piece < kDecDrainStores; piece++) {
                     const uint32_t p = flushed + kDecPiece * piece + 16u * j;
                     uint32_t fp = fpos + kDecPiece * piece;
                     fp = fp >= kDecRing ? fp - kDecRing : fp;
                     uint4 v;
-                    if constexpr (RUN) v = dec_ring_load16(ring8, fp + 16u * j);
+                    if constexpr (RUN || kPackedHead) v = dec_ring_load16(ring8, fp + 16u * j);
                     else v = *reinterpret_cast<const uint4 *>(ring8 + fp + 16u * j);
-                    if (dst16) {
+                    if (kPackedHead || dst16) {
                         *reinterpret_cast<uint4 *>(dst + p) = v;
                     } else {
                         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -1253,6 +1382,9 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
         }
     }
 
+    if constexpr (kPackedHead) {                                   // (no drain took them: the window has not wrapped)
+        for (uint32_t i = j; i < (head_left < count ? head_left : count); i += kDecLanes) dst[i] = ring8[i];
+    }
     for (uint32_t i = flushed + j; i < count; i += kDecLanes) {
         uint32_t r = fpos + (i - flushed);
         r = r >= kDecRing ? r - kDecRing : r;
@@ -1273,12 +1405,12 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
                 *reinterpret_cast<uint32_t *>(cst) = H;
                 if (ch.status) ch.status[b] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
             }
-        } else if (cst && j == 0u) {                               // not a state: nothing is written, nothing changes
+        } else if (!PACKED && cst && j == 0u) {                    // not a state: nothing is written, nothing changes
             out_len[b] = 0;
             if (ch.status) ch.status[b] = 0x10u;
         }
     }
-    if constexpr (!RUN) break;
+    if constexpr (!RUN && !PACKED) break;
     }
     // (RUN) the run's history goes back once, at its end
     if constexpr (RUN) {

@@ -183,6 +183,18 @@ int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slo
 int lzs_hip_launch_decoded_size(uint32_t *d_size, uint8_t *d_status, const void *d_in, size_t in_stride,
                                 const uint32_t *d_in_len, uint32_t in_len, uint32_t limit, uint32_t nblocks,
                                 void *stream);
+/* The packed calls (lzs_packed.c checks the arguments): stream b lies at d_in + d_in_off[b] -- d_in_len[b] bytes,
+ * or up to d_in_off[b + 1] with d_in_len NULL -- and decodes to d_out + d_out_off[b] with d_out_off[b + 1] - d_out_off[b] bytes
+ * of room.  lzs_hip_launch_scan_sizes: d_offsets[b + 1] = d_offsets[b] + d_size[b] rounded up to `align` (a power of two),
+ * nblocks + 1 entries from 0 -- also for nblocks = 0. */
+int lzs_hip_launch_decoded_size_packed(uint32_t *d_size, uint8_t *d_status, const void *d_in, const uint64_t *d_in_off,
+                                       const uint32_t *d_in_len, uint32_t limit, uint32_t nblocks, void *stream);
+int lzs_hip_launch_decompress_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                     const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream);
+int lzs_hip_launch_decompress_channels_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                              const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                              void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
+int lzs_hip_launch_scan_sizes(uint64_t *d_offsets, const uint32_t *d_size, uint32_t align, uint32_t nblocks, void *stream);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,7 @@ using wgv_text::kWgThreads;
 #ifndef LZS_TU_COMPRESS
 #include "kernels/decompress_blocks.inc"
 #include "kernels/decompress_stream.inc"
+#include "kernels/decompress_packed.inc"
 #endif
 #ifndef LZS_TU_DECOMPRESS
 #include "kernels/compact_resume.inc"
@@ -727,6 +728,34 @@ int lzs_hip_launch_resolve_chunks(void *d_out, uint32_t *d_origin, uint32_t tota
 }
 
 unsigned lzs_hip_dec_segment_bytes(void) { return kDecSegMax; }
+
+// The packed calls (lzs_packed.c checks the arguments): offsets and lengths are on the device, so there is nothing to decide here.
+int lzs_hip_launch_decompress_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                     const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream)
+{
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(lzs_decompress_packed_grp_kernel<false>, dim3((nblocks + kDecGroups - 1) / kDecGroups), dim3(64), 0,
+                       (hipStream_t)stream, (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len,
+                       (const uint32_t *)nullptr, (uint8_t *)nullptr, (uint8_t *)nullptr, nblocks);
+    return (int)hipGetLastError();
+}
+
+int lzs_hip_launch_decompress_channels_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                              const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                              void *d_states, uint8_t *d_status, uint32_t npackets, void *stream)
+{
+    if (npackets == 0) return 0;
+    hipLaunchKernelGGL(lzs_decompress_packed_grp_kernel<true>, dim3((npackets + kDecGroups - 1) / kDecGroups), dim3(64), 0,
+                       (hipStream_t)stream, (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len,
+                       d_channel, (uint8_t *)d_states, d_status, npackets);
+    return (int)hipGetLastError();
+}
+
+int lzs_hip_launch_scan_sizes(uint64_t *d_offsets, const uint32_t *d_size, uint32_t align, uint32_t nblocks, void *stream)
+{
+    hipLaunchKernelGGL(lzs_scan_sizes_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_offsets, d_size, align - 1u, nblocks);
+    return (int)hipGetLastError();
+}
 
 #endif  // !LZS_TU_COMPRESS
 #ifndef LZS_TU_DECOMPRESS

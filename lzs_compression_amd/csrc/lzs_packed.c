@@ -1,0 +1,101 @@
+/*
+ * lzs_packed.c -- the offset-addressed ("packed") calls (include/lzs/lzs_batch.h, lzs_channels.h):
+ * lzs_offsets_from_sizes_device, lzs_decompressed_size_packed_device, lzs_decompress_batch_packed_device,
+ * lzs_decompress_channels_packed_device.  The arguments are checked here; lzs_scan_sizes_kernel, lzs_decoded_size_packed_kernel
+ * (lzs_decoded_size.hip) and lzs_decompress_packed_grp_kernel (kernels/decompress_packed.inc) do the rest.  Offsets and lengths
+ * stay on the device: what they say about a single block is the kernels' to check.
+ */
+#include "lzs_internal.h"
+#include "lzs/lzs_channels.h"
+
+static int offsets_aligned(const char *who, const char *name, const uint64_t *p)
+{
+    if ((uintptr_t)p & 7u) return fail(LZS_E_ARG, "%s: %s is not 8-byte aligned", who, name);
+    return LZS_OK;
+}
+
+int lzs_offsets_from_sizes_device(uint64_t *d_offsets, const uint32_t *d_size, size_t align, size_t nblocks, void *hip_stream)
+{
+    const char *who = "lzs_offsets_from_sizes_device";
+    if (!d_offsets) return fail(LZS_E_ARG, "%s: offsets is NULL", who);
+    if (!d_size && nblocks) return fail(LZS_E_ARG, "%s: size is NULL", who);
+    int rc = offsets_aligned(who, "d_offsets", d_offsets);
+    if (rc != LZS_OK) return rc;
+    if (align == 0 || align > 256u || (align & (align - 1u)) != 0)
+        return fail(LZS_E_ARG, "%s: align %zu is not a power of two from 1 to 256", who, align);
+    if (nblocks > 0x7FFFFFFFu) return fail(LZS_E_ARG, "%s: too many blocks (%zu)", who, nblocks);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_scan_sizes(d_offsets, d_size, (uint32_t)align, (uint32_t)nblocks, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_decompressed_size_packed_device(uint32_t *d_size, uint8_t *d_status, const void *d_in, const uint64_t *d_in_off,
+                                        const uint32_t *d_in_len, size_t limit, size_t nblocks, void *hip_stream)
+{
+    const char *who = "lzs_decompressed_size_packed_device";
+    if (nblocks == 0) return LZS_OK;
+    if (!d_size) return fail(LZS_E_ARG, "%s: size is NULL", who);
+    if (!d_in) return fail(LZS_E_ARG, "%s: input is NULL", who);
+    if (!d_in_off) return fail(LZS_E_ARG, "%s: in_off is NULL", who);
+    int rc = offsets_aligned(who, "d_in_off", d_in_off);
+    if (rc != LZS_OK) return rc;
+    if (d_in_len && (const void *)d_in_len == (const void *)d_size)
+        return fail(LZS_E_ARG, "%s: d_size and d_in_len are the same array", who);
+    if (nblocks > 0x7FFFFFFFu) return fail(LZS_E_ARG, "%s: too many blocks (%zu)", who, nblocks);
+    if (limit > 0xFFFFFFFFu) return fail(LZS_E_ARG, "%s: limit %zu exceeds 0xFFFFFFFF", who, limit);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_decoded_size_packed(d_size, d_status, d_in, d_in_off, d_in_len, (uint32_t)limit, (uint32_t)nblocks,
+                                                     hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+/* what both decoders ask of their arguments */
+static int check_decode(const char *who, const void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len, const void *d_in,
+                        const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks)
+{
+    if (!d_out) return fail(LZS_E_ARG, "%s: output is NULL", who);
+    if (!d_out_off) return fail(LZS_E_ARG, "%s: out_off is NULL", who);
+    if (!d_out_len) return fail(LZS_E_ARG, "%s: out_len is NULL", who);
+    if (!d_in) return fail(LZS_E_ARG, "%s: input is NULL", who);
+    if (!d_in_off) return fail(LZS_E_ARG, "%s: in_off is NULL", who);
+    int rc = offsets_aligned(who, "d_out_off", d_out_off);
+    if (rc != LZS_OK) return rc;
+    rc = offsets_aligned(who, "d_in_off", d_in_off);
+    if (rc != LZS_OK) return rc;
+    if (d_in_len && (const void *)d_in_len == (const void *)d_out_len)
+        return fail(LZS_E_ARG, "%s: d_out_len and d_in_len are the same array", who);
+    if (nblocks > 0x7FFFFFFFu) return fail(LZS_E_ARG, "%s: too many blocks (%zu)", who, nblocks);
+    return LZS_OK;
+}
+
+int lzs_decompress_batch_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                       const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks, void *hip_stream)
+{
+    const char *who = "lzs_decompress_batch_packed_device";
+    if (nblocks == 0) return LZS_OK;
+    int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, nblocks);
+    if (rc != LZS_OK) return rc;
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_decompress_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, (uint32_t)nblocks, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                          const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                          void *d_states, uint8_t *d_status, size_t npackets, void *hip_stream)
+{
+    const char *who = "lzs_decompress_channels_packed_device";
+    if (npackets == 0) return LZS_OK;
+    int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
+    if (rc != LZS_OK) return rc;
+    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
+    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_decompress_channels_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
+                                                            d_status, (uint32_t)npackets, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
