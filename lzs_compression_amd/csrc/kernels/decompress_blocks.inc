@@ -1,408 +1,37 @@
 // kernels/decompress_blocks.inc -- lzs_decompress() per block on the device.
 // Part of lzs_kernels.hip (included there, inside its anonymous namespace); not a translation unit of its own.
 //
-// The product's kernel is the THIRD one in this file, lzs_decompress_blocks_grp_kernel: eight streams per wavefront, eight
-// lanes each, no scalar control flow inside a step (its own header, further down, and DESIGN.md 3.3 say how and what it
-// measures: 144 / 463 / 147 GB/s of output on text / low-entropy / high-entropy blocks).  Its loop exists in two forms:
-// lzs_decompress_blocks_grp_m, the product's since round 5, keeps every flag of a step as a MASK (a compare or a select costs
-// gfx950 twice what an add or a v_bitop3 does); lzs_decompress_blocks_grp, rounds 2-4's compares and selects, stays for A/B
-// builds (-DLZS_DEC_COMPARES) and for the four-lanes-a-stream experiment (-DLZS_DEC_LANES=4).
+// One decoder, lzs_decompress_blocks_grp, behind every block and channel entry point (the kernels at the end of this file and
+// kernels/decompress_packed.inc): EIGHT STREAMS PER WAVEFRONT, 8 lanes each, and no scalar control flow inside a token.
+// DESIGN.md 3.3 says how it came about and what it measures (144 / 463 / 147 GB/s of output on text / low-entropy /
+// high-entropy blocks).
 //
-// The first two -- one wavefront per stream, round 1's decoders -- are compiled only into liblzs_variants.so
-// (LZS_WITH_VARIANTS; LZS_DECODER=v1|v2 selects them there) as independent implementations of the same rules for the
-// cross-checks of tests/test_gpu_parity.py:
-//   lzs_decompress_blocks_kernel      the token parse wave-uniform on the scalar unit, match copies lane-parallel (lane i
-//                                     produces byte i of a copy; overlapping copies replicate with period `off`); a 4 KiB
-//                                     ring holds the output's window and is drained 1 KiB at a time; the compressed input
-//                                     comes through a 1 KiB tile in LDS.  27 GB/s on text: bound by the CU's one scalar unit.
-//   lzs_decompress_blocks_v2_kernel   the same shape with the input read by plain word loads one word ahead and the fields
-//                                     of a match token extracted on the vector unit (one v_readfirstlane per token).
+// A decoder that gives a wavefront to one stream is bound by the CU's one scalar unit (rocprofv3, round 1: 2.1e10 scalar
+// instructions per GiB of text output, 87 % of its issue slots): every token is a trip through wave-uniform branches while
+// 63 of the 64 lanes have nothing to do.  Here a group of 8 lanes owns a stream; its state (bit buffer, counts, offset, "a
+// length nibble follows") is held redundantly in the registers of its lanes, and one trip of the loop decodes one step -- a
+// run of up to 7 literals, a match token, or a length nibble -- for all eight groups at once, with every flag of the step a
+// MASK (reference rules: lzs-decompression.c:189, 200, 217-233, 238-342, 346-406; the stop rules are those of the
+// wave-per-stream decoders, test for test).  A match step copies at most 15 bytes: lane j of the group produces bytes j and
+// j + 8, overlapping copies replicate with period `off` (index mod off from a per-lane table), sources before out[0] read as
+// zero (the window starts as zeros).  Each group has its own 2304-byte output window in LDS (2047 + what waits to be
+// drained), drained 128 bytes at a time with 16-byte stores (the wave branches there only when some group is due); the
+// compressed words come 128 bytes per group at a time, a chunk ahead, and across the group's lanes by ds_bpermute.
+// Measured on 1 GiB (MI355X) when it was new: 60 / 300 / 62 GB/s of output against 27 / 165 / 32 for one wavefront per
+// stream (16 lanes per stream 36, 4 lanes 56).
+//
+// Round 1's two wave-per-stream decoders live in tools/variants/decompress_variants.inc and are compiled only into
+// liblzs_variants.so (LZS_WITH_VARIANTS; LZS_DECODER=v1|v2 selects them there), as independent implementations of the same
+// rules for the cross-checks of tests/test_gpu_parity.py.  The compare-and-select form of this decoder (rounds 2-4) and the
+// four-lanes-a-stream experiment are gone: commit 36cad77 is the last that has them, profiles/r05/abdec_*.txt their numbers.
 // reference lzs-decompression.c:156-412
 // ---------------------------------------------------------------------------------
 #ifdef LZS_WITH_VARIANTS
-struct __attribute__((aligned(16))) DecLds {
-    uint32_t ring[kRingWords];     // output window
-    uint32_t inbuf[kTile / 4];     // compressed input tile
-};
-
-__global__ __launch_bounds__(kWavesPerWG * 64)
-void lzs_decompress_blocks_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
-                                  uint32_t *__restrict__ out_len,
-                                  const uint8_t *__restrict__ in, size_t in_stride,
-                                  const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
-                                  uint32_t nblocks, uint32_t concat)
-{
-    __shared__ DecLds lds[kWavesPerWG];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv   = uniform(threadIdx.x >> 6);   // wave-uniform, and the compiler knows it
-    const uint32_t b    = blockIdx.x * kWavesPerWG + wv;
-    if (b >= nblocks) return;
-
-    DecLds &L = lds[wv];
-    uint8_t *ring8 = reinterpret_cast<uint8_t *>(L.ring);
-    const uint8_t *src = in + (size_t)b * in_stride;
-    const uint32_t n   = in_len ? in_len[b] : in_len_uniform;
-    const bool src16   = ((uintptr_t)src & 15u) == 0;
-    uint8_t *dst       = out + (size_t)b * out_stride;
-    const bool dst16   = ((uintptr_t)dst & 15u) == 0;
-    const uint32_t cap = out_cap;
-
-    uint64_t bits = 0;        // left-aligned bit buffer
-    uint32_t have = 0;        // valid bits in `bits`
-    uint32_t ipos = 0;        // next input byte to feed (multiple of 4)
-    uint32_t itile = 0;       // inbuf holds input [itile-1024, itile)
-    uint32_t count = 0;       // bytes produced
-    uint32_t flushed = 0;     // bytes stored to HBM (multiple of kTile)
-    uint32_t off = 0;
-    bool extended = false;
-
-    for (;;) {
-        // ---- refill (lzs-decompression.c:181-187): top up to > 32 bits while input lasts
-        while (have <= 32 && ipos < n) {
-            if (ipos >= itile) {
-                const uint32_t p = itile + 16 * lane;
-                *reinterpret_cast<uint4 *>(&L.inbuf[(p & (kTile - 1)) >> 2]) = load16(src, p, n, src16);
-                itile += kTile;
-                __builtin_amdgcn_wave_barrier();
-            }
-            uint32_t w = uniform(__builtin_bswap32(L.inbuf[(ipos & (kTile - 1)) >> 2]));
-            const uint32_t nb = n - ipos < 4 ? n - ipos : 4;     // bytes that really exist
-            if (nb < 4) w &= ~0u << (8 * (4 - nb));
-            bits |= (uint64_t)w << (32 - have);
-            have += 8 * nb;
-            ipos += 4;
-        }
-        if (have == 0 || count >= cap) break;                      // :189, :200
-
-        uint32_t copy_len = 0;
-        if (extended) {                                            // :370-406
-            if (have < 4) break;
-            const uint32_t e = (uint32_t)(bits >> 60);
-            bits <<= 4; have -= 4;
-            copy_len = e;
-            if (e != kNibbleMax) extended = false;
-        } else if ((bits >> 63) == 0 && have >= 9) {
-            // a run of literals (:217-233), up to 7 at once: token i of an all-literal run starts
-            // at bit 63 - 9i, so the first set type bit among those tells how long the run is
-            const uint64_t types = bits & 0x8040201008040200ull;
-            uint32_t k = (types ? (uint32_t)__builtin_clzll(types) : 64u) / 9u;
-            k = k < have / 9u ? k : have / 9u;
-            k = k < cap - count ? k : cap - count;
-            if (lane < k) ring8[(count + lane) & kRingMask] = (uint8_t)(bits >> (55u - 9u * lane));
-            count += k;
-            bits <<= 9u * k; have -= 9u * k;
-        } else if (have > 32 && (bits >> 63) != 0) {
-            // a match token whose bits are all certainly there (at most 17 + 4 of more than 32):
-            // same decoding as below without the per-field "enough bits left?" tests
-            const uint32_t top = (uint32_t)(bits >> 43);           // 1 s ooooooo[oooo] cccc ...
-            const bool is_short = (top >> 19) & 1u;
-            const uint32_t o = is_short ? (top >> 12) & 0x7Fu : (top >> 8) & 0x7FFu;
-            const uint32_t used = is_short ? 9u : 13u;
-            if (o == 0) {
-                bits <<= used; have -= used;
-                if (is_short) {                                    // end marker (:255-260 / :564-576)
-                    if (!concat) break;
-                    const uint32_t pad = have & 7u;
-                    bits <<= pad; have -= pad;
-                } else {
-                    off = 0;                                       // long offset 0: no copy (:280)
-                }
-                continue;
-            }
-            const uint32_t code = (is_short ? top >> 8 : top >> 4) & 0xFu;
-            const uint32_t len = code < 0xC ? 2 + (code >> 2) : 5 + (code - 0xC);
-            const uint32_t width = code < 0xC ? 2u : 4u;
-            bits <<= used + width; have -= used + width;
-            off = o;
-            if (len == kTokenMax) extended = true;
-            copy_len = len;
-        } else {
-            const uint32_t is_match = (uint32_t)(bits >> 63);
-            bits <<= 1; have -= 1;
-            if (!is_match) {                                       // literal :217-233
-                if (have < 8) break;
-                const uint32_t byte = (uint32_t)(bits >> 56);
-                bits <<= 8; have -= 8;
-                if (lane == 0) ring8[count & kRingMask] = (uint8_t)byte;
-                count += 1;
-            } else {
-                if (have < 1) break;                               // :238-241
-                const uint32_t is_short = (uint32_t)(bits >> 63);
-                bits <<= 1; have -= 1;
-                if (is_short) {                                    // :248-260
-                    if (have < 7) break;
-                    off = (uint32_t)(bits >> 57);
-                    bits <<= 7; have -= 7;
-                    if (off == 0) {                                // end marker
-                        if (!concat) break;                        // one-shot rule: stop (:255-260)
-                        // file rule (the incremental decoder, :564-576): drop the pad bits up
-                        // to the byte boundary and go on with the next stream
-                        const uint32_t pad = have & 7u;
-                        bits <<= pad; have -= pad;
-                        continue;
-                    }
-                } else {                                           // :272-279
-                    if (have < 11) break;
-                    off = (uint32_t)(bits >> 53);
-                    bits <<= 11; have -= 11;
-                }
-                if (off != 0) {                                    // :280
-                    const uint32_t code = (uint32_t)(bits >> 60);  // :103-120, :325-342
-                    uint32_t len, width;
-                    if (code < 0xC) { len = 2 + (code >> 2); width = 2; }
-                    else            { len = 5 + (code - 0xC); width = 4; }
-                    if (have < width) break;
-                    bits <<= width; have -= width;
-                    if (len == kTokenMax) extended = true;
-                    copy_len = len;
-                }
-            }
-        }
-
-        if (copy_len) {                                            // :346-365, :381-400
-            const uint32_t room = cap - count;
-            const uint32_t m = copy_len < room ? copy_len : room;
-            __builtin_amdgcn_wave_barrier();
-            uint32_t v = 0;
-            if (lane < m) {
-                // overlap replicates with period `off`; m <= 15, so only short offsets wrap
-                // (`off` is wave-uniform: the division is skipped for the common long offsets)
-                const uint32_t k = off > 15u ? lane : lane % off;
-                const uint32_t from = count + k;                   // position + off of the source
-                v = from >= off ? ring8[(from - off) & kRingMask] : 0u;   // before out[0] -> 0
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (lane < m) ring8[(count + lane) & kRingMask] = (uint8_t)v;
-            count += m;
-        }
-
-        // ---- drain whole tiles of finished output
-        while (count - flushed >= kTile) {
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t p = flushed + 16 * lane;
-            const uint4 v = *reinterpret_cast<const uint4 *>(&L.ring[(p & kRingMask) >> 2]);
-            if (dst16) {
-                *reinterpret_cast<uint4 *>(dst + p) = v;
-            } else {
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                for (uint32_t k = 0; k < 16; k++) dst[p + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-            }
-            flushed += kTile;
-        }
-        if (count >= cap) break;                                   // mid-copy stop :361-364
-    }
-
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t i = flushed + lane; i < count; i += 64) dst[i] = ring8[i & kRingMask];
-    if (lane == 0) out_len[b] = count;
-}
-
-// ---------------------------------------------------------------------------------
-// lzs_decompress() per block, second version (round 1's default).  Same rules, same wave-per-stream
-// shape; what changed is where the instructions go.  The first version spent 29 scalar
-// instructions per output byte and saturated the CU's one scalar unit (rocprofv3: 3.1e10 SALU per
-// GiB = 93 % of its issue slots) -- its compressed input went HBM -> LDS tile -> ds_read ->
-// v_readfirstlane, and its conditions were combined as lane masks.  Here the compressed stream is
-// read by plain word loads one word ahead of use (no LDS tile), the token decode is nested single
-// compares, and the fields of a match token are extracted on the (idle) vector unit and come back
-// packed through one v_readfirstlane.
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(kWavesPerWG * 64)
-void lzs_decompress_blocks_v2_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
-                                     uint32_t *__restrict__ out_len,
-                                     const uint8_t *__restrict__ in, size_t in_stride,
-                                     const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
-                                     uint32_t nblocks, uint32_t concat)
-{
-    __shared__ uint32_t rings[kWavesPerWG][kRingWords];           // the OUTPUT's sliding window
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv   = uniform(threadIdx.x >> 6);
-    const uint32_t b    = blockIdx.x * kWavesPerWG + wv;
-    if (b >= nblocks) return;
-
-    uint32_t *ring = rings[wv];
-    uint8_t *ring8 = reinterpret_cast<uint8_t *>(ring);
-    const uint8_t *src = in + (size_t)b * in_stride;
-    const uint32_t n   = uniform(in_len ? in_len[b] : in_len_uniform);
-    uint8_t *dst       = out + (size_t)b * out_stride;
-    const bool dst16   = ((uintptr_t)dst & 15u) == 0;
-    const uint32_t cap = out_cap;
-
-    // ---- the input as aligned words: word j holds stream bytes [4j - skew, 4j - skew + 4)
-    const uint32_t skew = (uint32_t)((uintptr_t)src & 3u);
-    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(src - skew);
-    const uint32_t nwords = n ? (skew + n + 3u) >> 2 : 0u;         // words that hold stream bytes
-    uint64_t bits = 0;        // left-aligned bit buffer
-    uint32_t have = 0;        // valid bits in `bits`
-    uint32_t pos  = 0;        // stream bytes fed so far
-    uint32_t wi   = 0;        // next word to feed
-    uint32_t nextw = 0;       // that word, loaded ahead of use
-    if (nwords) {
-        uint32_t w = __builtin_bswap32(w32[0]) << (8u * skew);
-        const uint32_t avail = 4u - skew < n ? 4u - skew : n;
-        if (avail < 4u) w &= ~0u << (32u - 8u * avail);
-        bits = (uint64_t)w << 32;
-        have = 8u * avail;
-        pos = avail;
-        wi = 1;
-        if (nwords > 1u) nextw = w32[1];
-    }
-    uint32_t count = 0;       // bytes produced
-    uint32_t flushed = 0;     // bytes stored to HBM (multiple of kTile)
-    uint32_t off = 0;
-    uint32_t extended = 0;
-
-    for (;;) {
-        // ---- refill (lzs-decompression.c:181-187).  One word per token is enough: no token path
-        // below takes more than 32 bits except a run of literals, which takes what is there.
-        if (have <= 32u) {
-            if (pos < n) {
-                uint32_t w = __builtin_bswap32(nextw);
-                const uint32_t rem = n - pos;
-                const uint32_t nb = rem < 4u ? rem : 4u;           // bytes that really exist
-                if (rem < 4u) w &= ~0u << (32u - 8u * rem);
-                bits |= (uint64_t)w << (32u - have);
-                have += 8u * nb;
-                pos += nb;
-                wi += 1u;
-                if (wi < nwords) nextw = w32[wi];
-            }
-        }
-        if (have == 0u) break;                                     // :189
-        if (count >= cap) break;                                   // :200, and mid-copy :361-364
-        const uint32_t room = cap - count;
-
-        uint32_t copy_len = 0;
-        const uint32_t top = (uint32_t)(bits >> 32);
-        if (extended) {                                            // :370-406
-            if (have < 4u) break;
-            const uint32_t e = top >> 28;
-            bits <<= 4; have -= 4u;
-            copy_len = e;
-            extended = e == kNibbleMax ? 1u : 0u;
-        } else if ((int32_t)top >= 0) {
-            // a run of literals (:217-233), up to 7 at once: token i of an all-literal run starts
-            // at bit 63 - 9i, so the first set type bit among those tells how long the run is
-            if (have < 9u) break;                                  // type bit, then 8 more or stop (:220-223)
-            // (counted on the vector unit, like the match fields below)
-            const uint32_t th = opaque(top) & 0x80402010u, tl = opaque((uint32_t)bits) & 0x08040200u;
-            const uint32_t lead = th ? (uint32_t)__builtin_clz(th) : (tl ? 32u + (uint32_t)__builtin_clz(tl) : 64u);
-            uint32_t kv = (lead * 57u) >> 9;                       // lead / 9 for lead <= 64
-            const uint32_t fitv = (opaque(have) * 57u) >> 9;       // have / 9 for have <= 64
-            kv = kv < fitv ? kv : fitv;
-            kv = kv < room ? kv : room;
-            const uint32_t k = uniform(kv);
-            if (lane < kv) ring8[(count + lane) & kRingMask] = (uint8_t)(bits >> (55u - 9u * lane));
-            count += k;
-            bits <<= 9u * k; have -= 9u * k;
-        } else {
-            // a match token: 1 s ooooooo[oooo] cccc (:238-342).  Every field is decoded from the
-            // zero-padded buffer without asking whether its bits exist; the ONE test on `need`
-            // covers all the "not enough bits: stop" exits of the reference (:240,250,274,334),
-            // because a token produces nothing before its last field is read, and bits can only
-            // be missing when the input is exhausted (the refill above keeps more than a token's
-            // worth otherwise).
-            // field extraction on the vector unit (the scalar unit is the bottleneck): the values
-            // are the same in every lane and come back through v_readfirstlane
-            const uint32_t t = opaque(top) >> 11;
-            const bool is_short_v = (t >> 19) & 1u;
-            const uint32_t o_v = is_short_v ? (t >> 12) & 0x7Fu : (t >> 8) & 0x7FFu;
-            const uint32_t used_v = is_short_v ? 9u : 13u;
-            const uint32_t code_v = (is_short_v ? t >> 8 : t >> 4) & 0xFu;
-            const uint32_t len_v = code_v < 0xCu ? 2u + (code_v >> 2) : code_v - 7u;
-            const uint32_t width_v = code_v < 0xCu ? 2u : 4u;
-            // packed: o (11) | used (4) << 11 | len (4) << 15 | width (3) << 19 | is_short << 22
-            const uint32_t packed = uniform(o_v | (used_v << 11) | (len_v << 15) | (width_v << 19) | ((is_short_v ? 1u : 0u) << 22));
-            const uint32_t o = packed & 0x7FFu, used = (packed >> 11) & 15u;
-            const bool is_short = (packed >> 22) & 1u;
-            if (o == 0u) {
-                if (have < used) break;
-                bits <<= used; have -= used;
-                if (is_short) {                                    // end marker (:255-260 / :564-576)
-                    if (!concat) break;                            // one-shot rule: stop
-                    // file rule (the incremental decoder): drop the pad bits up to the byte
-                    // boundary and go on with the next stream
-                    const uint32_t pad = have & 7u;
-                    bits <<= pad; have -= pad;
-                } else {
-                    off = 0;                                       // long offset 0: no copy (:280)
-                }
-                continue;
-            }
-            const uint32_t len = (packed >> 15) & 15u, width = (packed >> 19) & 7u;
-            if (have < used + width) break;
-            bits <<= used + width; have -= used + width;
-            off = o;
-            extended = len == kTokenMax ? 1u : 0u;
-            copy_len = len;
-        }
-
-        if (copy_len) {                                            // :346-365, :381-400
-            const uint32_t m = copy_len < room ? copy_len : room;
-            __builtin_amdgcn_wave_barrier();
-            uint32_t v = 0;
-            if (lane < m) {
-                // overlap replicates with period `off`; m <= 15, so only short offsets wrap
-                // (`off` is wave-uniform: the division is skipped for the common long offsets)
-                const uint32_t k = off > 15u ? lane : lane % off;
-                const uint32_t from = count + k;                   // position + off of the source
-                v = from >= off ? ring8[(from - off) & kRingMask] : 0u;   // before out[0] -> 0
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (lane < m) ring8[(count + lane) & kRingMask] = (uint8_t)v;
-            count += m;
-        }
-
-        // ---- drain whole tiles of finished output
-        if (count - flushed >= kTile) {
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t p = flushed + 16 * lane;
-            const uint4 v = *reinterpret_cast<const uint4 *>(&ring[(p & kRingMask) >> 2]);
-            if (dst16) {
-                *reinterpret_cast<uint4 *>(dst + p) = v;
-            } else {
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                for (uint32_t k = 0; k < 16; k++) dst[p + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-            }
-            flushed += kTile;
-        }
-    }
-
-    __builtin_amdgcn_wave_barrier();
-    for (uint32_t i = flushed + lane; i < count; i += 64) dst[i] = ring8[i & kRingMask];
-    if (lane == 0) out_len[b] = count;
-}
-
-#endif  // LZS_WITH_VARIANTS
-
-// ---------------------------------------------------------------------------------
-// lzs_decompress() per block, third version (the default): EIGHT STREAMS PER WAVEFRONT, 8 lanes
-// each, and no scalar control flow inside a token.
-//
-// The wave-per-stream decoders above are bound by the CU's one scalar unit (rocprofv3, round 1:
-// 2.1e10 scalar instructions per GiB of text output, 87 % of its issue slots): every token is a
-// trip through wave-uniform branches while 63 of the 64 lanes have nothing to do.  Here a group
-// of 8 lanes owns a stream; its state (bit buffer, counts, offset, "a length nibble follows")
-// is held redundantly in the registers of its lanes, and one trip of the loop decodes one step
-// -- a run of up to 7 literals, a match token, or a length nibble -- for all eight groups at once,
-// written as selects over the three cases (reference rules: lzs-decompression.c:189, 200, 217-233,
-// 238-342, 346-406; the stop rules are those of the wave-per-stream version, test for test).  A
-// match step copies at most 15 bytes: lane j of the group produces bytes j and j + 8, overlapping
-// copies replicate with period `off` (index mod off from a per-lane table), sources before out[0]
-// read as zero (the window starts as zeros).  Each group has its own 2304-byte output window in LDS
-// (2047 + what waits to be drained), drained 128 bytes at a time with 16-byte stores (the wave
-// branches there only when some group is due); the compressed words come 128 bytes per group at a
-// time, a chunk ahead, and across the group's lanes by ds_bpermute.
-// Measured on 1 GiB (MI355X): 60 / 300 / 62 GB/s of output on text / low-entropy / high-entropy
-// against 27 / 165 / 32 for one wavefront per stream when it was new (16 lanes per stream 36, 4 lanes
-// 56); 130 / 434 / 130 now (DESIGN.md 3.3 has the steps).
-// ---------------------------------------------------------------------------------
-#ifndef LZS_DEC_LANES
-#define LZS_DEC_LANES 8
+#include "decompress_variants.inc"
 #endif
-constexpr uint32_t kDecLanes  = LZS_DEC_LANES;   // lanes per stream: 8 (two bytes of a step per lane) or 4 (four: sixteen streams per wavefront)
+
+constexpr uint32_t kDecLanes  = 8;               // lanes per stream: two bytes of a step per lane
 constexpr uint32_t kDecGroups = 64 / kDecLanes;  // streams per wavefront
-constexpr uint32_t kDecSlots  = 16 / kDecLanes;  // bytes of a step per lane
 #ifndef LZS_DEC_DRAIN
 #define LZS_DEC_DRAIN 128
 #endif
@@ -412,7 +41,6 @@ constexpr uint32_t kDecDrainStores = kDecDrain / kDecPiece;
 // bytes of output window per stream: >= 2047 + kDecDrain + 15, a multiple of kDecPiece (no piece wraps inside itself)
 constexpr uint32_t kDecRing   = (kWindow + kDecDrain + 15u + kDecPiece - 1u) / kDecPiece * kDecPiece;
 static_assert(kDecDrain % kDecPiece == 0, "a drain is whole pieces");
-static_assert(kDecLanes == 8 || kDecLanes == 4, "a step is at most 15 bytes: two bytes a lane with eight lanes, four with four");
 
 struct __attribute__((aligned(16))) DecGroupLds {
     uint32_t ring[kDecGroups][kDecRing / 4];     // output windows
@@ -425,362 +53,6 @@ __device__ __forceinline__ uint32_t ffbh_u32(uint32_t x)      // leading zeros; 
     asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
     return r;
 }
-
-// x mod kDecRing for x < 2 * kDecRing (wrap1) or x < 3 * kDecRing (wrap2): what is too small wraps around to something huge
-__device__ __forceinline__ uint32_t dec_wrap1(uint32_t x) { return min(x, x - kDecRing); }
-__device__ __forceinline__ uint32_t dec_wrap2(uint32_t x) { return min(min(x, x - kDecRing), x - 2u * kDecRing); }
-
-// The fields of a match token 1 s ooooooo[oooo] cccc at the top of `top` (lzs-decompression.c:238-342), all three
-// decoders' way: a short token moved down four bits has its fields where a long one has them (offset 29..19, code
-// 18..15).  short4: 4 for a 7-bit offset, 0 for an 11-bit one -- the token is 13 - short4 bits up to its length code,
-// and that is 2 bits (lengths 2 3 4) below code 12, 4 bits (5 6 7 8) from there.
-__device__ __forceinline__ void dec_match_fields(uint32_t top, uint32_t &short4, uint32_t &o, uint32_t &code, uint32_t &len)
-{
-    short4 = (uint32_t)((int32_t)(top << 1) >> 31) & 4u;
-    const uint32_t norm = (top & 0x3FFFFFFFu) >> short4;
-    o = norm >> 19;
-    code = (norm >> 15) & 0xFu;
-    len = (uint32_t)max((int32_t)(((norm >> 17) & 3u) + 2u), (int32_t)code - 7);      // 2 2 2 2 3 3 3 3 4 4 4 4 5 6 7 8
-}
-
-// How many of the tokens at the top of the 64 bits top : low are literals, one after the other (:217-233): token i of
-// an all-literal run starts at bit 63 - 9i, so the first set type bit among those ends the run.  SHORT: counted in the
-// upper word alone, four at most (where matches dominate, runs are short).  The caller clips to the bits it has.
-template <bool SHORT>
-__device__ __forceinline__ uint32_t dec_literal_run(uint32_t top, uint32_t low)
-{
-    uint32_t lead;
-    if (SHORT) {
-        lead = min(ffbh_u32(top & 0x80402010u), 36u);
-    } else {
-        const uint32_t lead_hi = ffbh_u32(top & 0x80402010u), lead_lo = ffbh_u32(low & 0x08040200u) | 32u;
-        lead = min(min(lead_hi, lead_lo), 64u);                    // (ffbh of 0 is huge: all seven are literals)
-    }
-    return __umul24(lead, 57u) >> 9;                               // lead / 9 for lead <= 64
-}
-
-// TWO: a second token in the same trip where that is possible (see the loop).  Text is mostly short
-// matches (3.4 bytes a token: one token a trip is 3.0 bytes a trip) and gains a quarter by it;
-// high-entropy data (runs of seven literals) and long runs (nibble after nibble) lose 16 - 20 % to
-// the extra instructions -- so the kernel below picks the form per wavefront, by what its streams'
-// lengths say about them, and a wavefront never changes form on the way.
-// WIDE: a 96-bit bit buffer fed with up to TWO words per trip (never across a 128-byte chunk).  A run
-// of seven literals is 63 bits and one word a trip is 32: on high-entropy data the loop was fed,
-// not decoding -- 3.5 literals a trip.  Costs ~25 instructions a trip: the form for streams that
-// are longer than nine tenths of their output.
-template <bool TWO, bool WIDE, bool CONCAT>
-__device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
-                                      uint32_t *__restrict__ out_len,
-                                      const uint8_t *__restrict__ in, size_t in_stride,
-                                      const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
-                                      uint32_t nblocks, uint32_t concat_arg, uint32_t per_wave)
-{
-    constexpr uint32_t concat = CONCAT ? 1u : 0u;                  // (compile time: the file rule's pad bits cost the one-shot rule nothing)
-    const uint32_t lane = threadIdx.x;
-    const uint32_t g = lane / kDecLanes, j = lane % kDecLanes;
-    const uint32_t b = blockIdx.x * per_wave + g;                  // per_wave: kDecGroups, or 1 (see the launcher)
-    // the windows start as zeros: a copy from before out[0] reads a part of its window nothing has been written to
-    // yet (it lies at most 2047 behind and the window is longer than 2047 + a step), which is the zero the rule asks for
-    for (uint32_t i = lane; i < sizeof(L.ring) / 16u; i += 64u) reinterpret_cast<uint4 *>(&L.ring[0][0])[i] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
-
-    const bool live = b < nblocks && g < per_wave;
-    const uint32_t bb = live ? b : 0u;
-    uint8_t *ring8 = reinterpret_cast<uint8_t *>(L.ring[g]);
-    uint8_t *dummy8 = reinterpret_cast<uint8_t *>(&L.dummy[lane]);
-    const uint8_t *src = in + (size_t)bb * in_stride;
-    const uint32_t n   = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
-    uint8_t *dst       = out + (size_t)bb * out_stride;
-    const bool dst16   = ((uintptr_t)dst & 15u) == 0;
-    const uint32_t cap = live ? out_cap : 0u;
-
-    // ---- the input as aligned words: word k holds stream bytes [4k - skew, 4k - skew + 4).  A
-    // group takes 16 x kDecLanes bytes at a time: lane j holds words 4j .. 4j + 3 of the current
-    // chunk (one coalesced load for the group) and of the next one, requested a chunk ahead; the
-    // word the group feeds next comes across the lanes (ds_bpermute), fetched a step before it is
-    // used.  (Sixteen bytes at a time in every lane meant a load every other step somewhere in
-    // the wavefront, and the wave waited ~1 us for each.)  The loads are BUFFER loads bounded by
-    // the end of the last of the wavefront's streams: past it they return zeros instead of
-    // faulting, so the end of a stream is no special case (what lies past it is never fed: `rem`
-    // below), and lanes that do not move on load what they have again -- one load instruction for
-    // the whole wavefront, not waited for until the chunk is needed.
-    const uint32_t skew = (uint32_t)((uintptr_t)src & 3u);
-    const uint32_t b0 = blockIdx.x * per_wave;
-    const uint8_t *wave_in = in + (size_t)b0 * in_stride;
-    const uintptr_t in_lo = (uintptr_t)wave_in & ~(uintptr_t)3;
-    const uint32_t rel = live ? (uint32_t)((size_t)(b - b0) * in_stride) : 0u;      // my stream, from wave_in
-    uint32_t wave_end = 0;
-#pragma unroll
-    for (uint32_t gg = 0; gg < kDecGroups; gg++) {
-        const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)(rel + n), (int)(gg * kDecLanes));
-        wave_end = e > wave_end ? e : wave_end;
-    }
-    // (the descriptor is the same in every lane, and said to be: or the load sits in a loop over the distinct ones)
-    const uintptr_t in_lo_u = ((uintptr_t)uniform((uint32_t)((uint64_t)in_lo >> 32)) << 32) | uniform((uint32_t)in_lo);
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)in_lo_u, 0, (int)uniform((wave_end + (uint32_t)((uintptr_t)wave_in & 3u) + 3u) & ~3u), 0x00020000);
-    const auto bload = [&](uint32_t byte_off) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, 0);
-        return make_uint4(v.x, v.y, v.z, v.w);
-    };
-    constexpr uint32_t kChunk = 16u * kDecLanes;                    // bytes
-    uint32_t nxt_off = (uint32_t)((uintptr_t)(src - skew) - in_lo) + 16u * j + kChunk;
-    uint4 cur = bload(nxt_off - kChunk), nxt = bload(nxt_off);
-    const uint32_t glane4 = (lane & ~(kDecLanes - 1u)) << 2;       // byte index of the group's lane 0 for ds_bpermute
-    // A lane's four words ROTATE by one with every word its group takes, so that the word to feed next (word wi of the
-    // stream) is always in cur.x of lane (wi / 4) mod 8, and the one after it in cur.y of the lane that holds that:
-    // one address and one ds_bpermute a trip, no select on wi as well.  (32 words to a chunk: the next chunk moves
-    // in when the rotation is back at 0.)
-    const auto rotate = [&](uint32_t on) {
-        const uint32_t x0 = cur.x;
-        cur.x = on ? cur.y : cur.x; cur.y = on ? cur.z : cur.y; cur.z = on ? cur.w : cur.z; cur.w = on ? x0 : cur.w;
-    };
-    static_assert(kChunk == 16u * kDecLanes, "a lane holds four words of the chunk");
-    const auto fetch = [&](uint32_t wi_) {
-        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(glane4 + (wi_ & (4u * kDecLanes - 4u))), (int)cur.x);
-    };
-    const auto fetch_after = [&](uint32_t wi_) {
-        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(glane4 + ((wi_ + 1u) & (4u * kDecLanes - 4u))), (int)cur.y);
-    };
-    uint64_t bits = 0;        // left-aligned bit buffer
-    uint32_t have = 0;        // valid bits in it
-    uint32_t left = n;        // bytes of the stream not fed yet
-    uint32_t wi   = 0;        // next word to feed
-    {
-        const uint32_t first = fetch(0);
-        if (n) {
-            uint32_t w = __builtin_bswap32(first) << (8u * skew);
-            const uint32_t avail = 4u - skew < n ? 4u - skew : n;
-            if (avail < 4u) w &= ~0u << (32u - 8u * avail);
-            bits = (uint64_t)w << 32;
-            have = 8u * avail;
-            left = n - avail;
-            wi = 1;
-        }
-    }
-    rotate(wi);
-    uint32_t nextw = fetch(wi);
-    uint32_t nextw2 = WIDE ? fetch_after(wi) : 0u;                 // (WIDE: the word after it; only used when in the same chunk)
-    uint32_t bits_lo = 0;                                          // (WIDE: bits 64..95 of the buffer, left-aligned)
-    uint32_t count = 0, flushed = 0, off = 0, extended = 0;
-    uint32_t cpos = 0, fpos = 0;                                   // count and flushed modulo kDecRing
-    uint32_t done = live ? 0u : 1u;
-    // overlapping copies replicate with period off: byte idx of a step comes from byte idx mod off.  Lane j's
-    // bytes are j and j + 8: a 3-bit entry per off = 0 .. 8 (0 and 8 and more: j itself), a 4-bit one per off = 0 .. 15
-    uint32_t mod_lo = 0; uint64_t mod_hi = 0;
-    uint64_t mod_tab[kDecSlots];                                   // (four lanes: a 4-bit entry per off = 0 .. 15 for each of the lane's four bytes)
-    if (kDecLanes == 8u) {
-#pragma unroll
-        for (uint32_t e = 0; e <= 8u; e++) mod_lo |= ((e == 0u || e == 8u) ? j : j % (e ? e : 1u)) << (3u * e);
-#pragma unroll
-        for (uint32_t e = 0; e < 16u; e++) mod_hi |= (uint64_t)(e == 0u ? j + 8u : (j + 8u) % (e ? e : 1u)) << (4u * e);
-    }
-#pragma unroll
-    for (uint32_t sl = 0; sl < kDecSlots; sl++) {
-        mod_tab[sl] = 0;
-#pragma unroll
-        for (uint32_t e = 0; e < 16u; e++) mod_tab[sl] |= (uint64_t)(e == 0u ? j + kDecLanes * sl : (j + kDecLanes * sl) % (e ? e : 1u)) << (4u * e);
-    }
-
-    for (;;) {
-        if (__builtin_amdgcn_ballot_w64(done == 0u) == 0ull) break;
-        // ---- refill (:181-187): one word per step keeps more than a token's worth in the buffer
-        if (!WIDE) {
-            // (no mask for the stream's last word: what follows the stream in it lies past `have` bits, is never
-            // joined by another word, and every rule below counts bits before it believes them -- see `need`;
-            // a stream that is done may still be fed once or twice: nothing reads its buffer any more)
-            const uint32_t rf = (have <= 32u) & (left != 0u);
-            const uint32_t w = rf ? __builtin_bswap32(nextw) : 0u;
-            const uint32_t nb = rf ? min(left, 4u) : 0u;           // bytes taken
-            bits |= (uint64_t)w << ((32u - have) & 63u);
-            have = (nb << 3) + have;
-            left -= nb;
-            wi   = rf ? wi + 1u : wi;
-            rotate(rf);
-            // the chunk is used up: the next one moves in, the one after is requested
-            const bool roll = rf && (wi & (4u * kDecLanes - 1u)) == 0u;
-            if (__builtin_amdgcn_ballot_w64(roll) != 0ull) {
-                cur.x = roll ? nxt.x : cur.x; cur.y = roll ? nxt.y : cur.y;
-                cur.z = roll ? nxt.z : cur.z; cur.w = roll ? nxt.w : cur.w;
-                nxt_off = roll ? nxt_off + kChunk : nxt_off;
-                nxt = bload(nxt_off);
-            }
-            nextw = fetch(wi);
-        } else {
-            // two words where 64 bits or fewer are left (the second only from the same chunk: its copy
-            // was fetched a trip ago like the first's); the buffer is bits : bits_lo, 96 bits
-            uint32_t took = 0;
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                // (the second only if the first was taken -- its copy is the word AFTER that one -- and lies in the same chunk)
-                const uint32_t same = r == 0 ? 1u : (took & ((wi & (4u * kDecLanes - 1u)) != 0u ? 1u : 0u));
-                const uint32_t rf = (have <= 64u) & (left != 0u) & same;
-                took = rf;
-                const uint32_t w = __builtin_bswap32(r == 0 ? nextw : nextw2);     // (not masked: see above)
-                const uint32_t nb = min(left, 4u);                 // bytes taken
-                // w at bit offset `have` of the 96: into the top 64 (shifted left or right) and what is left below
-                const uint64_t hi = have <= 32u ? (uint64_t)w << ((32u - have) & 63u) : (uint64_t)w >> ((have - 32u) & 63u);
-                const uint32_t lo = have > 32u ? (uint32_t)((uint64_t)w << ((64u - have) & 63u)) : 0u;
-                bits    = rf ? bits | hi : bits;
-                bits_lo = rf ? bits_lo | lo : bits_lo;
-                have = rf ? have + 8u * nb : have;
-                left = rf ? left - nb : left;
-                wi   = rf ? wi + 1u : wi;
-                rotate(rf);
-                const bool roll = rf && (wi & (4u * kDecLanes - 1u)) == 0u;
-                if (__builtin_amdgcn_ballot_w64(roll) != 0ull) {
-                    cur.x = roll ? nxt.x : cur.x; cur.y = roll ? nxt.y : cur.y;
-                    cur.z = roll ? nxt.z : cur.z; cur.w = roll ? nxt.w : cur.w;
-                    nxt_off = roll ? nxt_off + kChunk : nxt_off;
-                    nxt = bload(nxt_off);
-                }
-            }
-            nextw = fetch(wi);
-            nextw2 = fetch_after(wi);
-        }
-        const uint32_t room = cap - count;                         // (meaningless once done: nothing is written then)
-        const uint32_t top = (uint32_t)(bits >> 32), low = (uint32_t)bits;
-
-        // ---- the three kinds of step, side by side (flags are 0 / 1 words: no short-circuit branches)
-        const uint32_t is_ext = extended;
-        const uint32_t is_lit = (is_ext ^ 1u) & ((top >> 31) ^ 1u);
-        const uint32_t is_mat = (is_ext ^ 1u) & (top >> 31);
-        // a length nibble (:370-406)
-        const uint32_t e = top >> 28;
-        // a run of literals (:217-233), up to 7: token i of an all-literal run starts at bit 63 - 9i
-        uint32_t kv = dec_literal_run<TWO>(top, low);              // (TWO: four a trip at most)
-        const uint32_t fit = __umul24(have, 57u) >> 9;             // have / 9 for have <= 96 (what it is beyond does not matter: kv <= 7)
-        kv = kv < fit ? kv : fit;
-        kv = kv < room ? kv : room;
-        // a match token: 1 s ooooooo[oooo] cccc (:238-342)
-        uint32_t short4, o, code, len;
-        dec_match_fields(top, short4, o, code, len);
-        const uint32_t is_short = short4 >> 2;
-        const uint32_t used = 13u - short4;
-        const uint32_t width = code < 0xCu ? 2u : 4u;
-        const uint32_t zero_off = o == 0u ? 1u : 0u;
-        const uint32_t copying = is_mat & (zero_off ^ 1u);        // a match token with a real offset
-        // bits the step needs; short of them it stops for good (:222, 240, 250, 274, 334, 375)
-        const uint32_t need_mat = zero_off ? used : used + width;
-        const uint32_t need = is_ext ? 4u : (is_lit ? 9u : need_mat);
-        // :189 (no bits: every step needs four at least), :200 and mid-copy :361-364 (no room), and the token's own stops
-        const uint32_t stop = ((have < need) | (room == 0u)) ? 1u : 0u;
-        const uint32_t go = (done | stop) ^ 1u;
-        const uint32_t endm = is_mat & zero_off & is_short;       // end marker (:255-260 / file rule :564-576)
-        uint32_t consume = is_lit ? 9u * kv : need;
-        // file rule: after an end marker drop the pad bits up to the byte boundary and go on
-        consume += (endm & concat) ? ((have - used) & 7u) : 0u;
-        const uint32_t copy_len = is_ext ? e : (copying ? len : 0u);
-        const uint32_t off_now = copying ? o : off;
-        // long offset 0: no copy, and the offset register is cleared (:280); an end marker leaves it
-        const uint32_t off_next = (is_mat & zero_off & (is_short ^ 1u)) ? 0u : off_now;
-        const uint32_t ext_next = is_ext ? (e == kNibbleMax ? 1u : 0u) : (copying & (len == kTokenMax ? 1u : 0u));
-        const uint32_t m = copy_len < room ? copy_len : room;
-        const uint32_t nA = go ? (is_lit ? kv : m) : 0u;          // bytes of this step's (first) token
-        // ---- TWO: a second token in the same trip.  Taken when the first is a run of literals or a
-        // whole match without extension, the next token is a match with a real offset whose bits are
-        // all there, both fit the trip's 16 byte slots and the room, and the second copy reads nothing
-        // the first writes (offset >= both lengths together: no replication inside it either).
-        // Otherwise it is simply the next trip's first token: nothing here can stop a stream.
-        uint32_t okB = 0u, nB = 0u, oB = 0u, lenB = 0u, needB = 0u;
-        uint64_t bitsB = 0;
-        if (TWO) {
-            bitsB = bits << (consume & 63u);
-            const uint32_t topB = (uint32_t)(bitsB >> 32);
-            const uint32_t haveB = have - consume;                 // (meaningless unless go)
-            uint32_t short4B, codeB;
-            dec_match_fields(topB, short4B, oB, codeB, lenB);
-            needB = (codeB < 0xCu ? 15u : 17u) - short4B;
-            const uint32_t firstA = (is_lit | (copying & (ext_next ^ 1u))) & go;
-            okB = firstA & (topB >> 31) & (oB != 0u ? 1u : 0u) & (haveB >= needB ? 1u : 0u) &
-                  (oB >= nA + lenB ? 1u : 0u) & (nA + lenB <= 16u ? 1u : 0u) & (nA + lenB <= room ? 1u : 0u) &
-                  (m == copy_len ? 1u : 0u);
-            nB = okB ? lenB : 0u;
-        }
-        const uint32_t nwrite = nA + nB;
-
-        // ---- lane j of the group produces byte j of the step (and byte j + 8 with eight lanes);
-        // overlap replicates with period off: index mod off (off <= 15 matters only), by one reciprocal
-#pragma unroll
-        for (uint32_t sl = 0; sl < kDecSlots; sl++) {
-            // (bytes past the first kDecLanes are rare in text -- matches of 9 and more, nibbles
-            // of 9..15: the wave goes there only when some group has them)
-            if (sl > 0u && __builtin_amdgcn_ballot_w64(nwrite > kDecLanes * sl) == 0ull) break;
-            const uint32_t idx = j + kDecLanes * sl;               // byte of the step
-            // (TWO: a byte past the first token is the second's -- no replication there -- or not written at all)
-            const uint32_t second = TWO ? (idx >= nA ? 1u : 0u) : 0u;
-            // idx mod off from the lane's table (idx itself for off 0 and for off > idx)
-            const uint32_t k1 = kDecLanes == 8u
-                ? (sl == 0u ? (mod_lo >> (3u * (off_now < 8u ? off_now : 8u))) & 7u
-                            : (off_now < 16u ? (uint32_t)(mod_hi >> (4u * (off_now & 15u))) & 15u : idx))
-                : (off_now < 16u ? (uint32_t)(mod_tab[sl] >> (4u * (off_now & 15u))) & 15u : idx);
-            const uint32_t k = second ? idx : k1;
-            const uint32_t oo = second ? oB : off_now;
-            // source: position count + k - off, or the zero byte when that lies before out[0]
-            const uint32_t sp = dec_wrap2(cpos + k + (kDecRing - oo));   // (the sum is < 2 * kDecRing + 15)
-            const uint8_t *from = ring8 + sp;
-            const uint32_t copied = *from;
-            const uint32_t wp = dec_wrap1(cpos + idx);
-            uint8_t *to = idx < nwrite ? ring8 + wp : dummy8;
-            uint32_t val = copied;
-            if (kDecLanes * sl < 7u) {                             // (compile time: this slot can hold a literal of a run)
-                const uint32_t lit = (uint32_t)(bits >> ((55u - 9u * (idx < 7u ? idx : 6u)) & 63u)) & 0xFFu;
-                val = (is_lit & (second ^ 1u)) ? lit : copied;
-            }
-            *to = (uint8_t)val;
-        }
-
-        count    = count + nwrite;
-        cpos     = dec_wrap1(cpos + nwrite);
-        // (two shifts: a run of seven literals and a match are 80 bits together)
-        if (WIDE) {                                                // (never with TWO) 96 bits move up by `consume` < 64
-            const uint32_t cs = consume & 63u;
-            const uint64_t lo64 = (uint64_t)bits_lo << 32;
-            const uint64_t carry = cs ? lo64 >> ((64u - cs) & 63u) : 0ull;
-            bits = (bits << cs) | carry;
-            bits_lo = (uint32_t)((lo64 << cs) >> 32);
-        } else {
-            bits = okB ? bitsB << needB : bits << (consume & 63u);
-        }
-        // (a stream that has stopped writes nothing any more -- nA and okB hang on `go`, `done` is for good -- so what
-        // happens to its buffer, offset and flags from here on is nobody's business: no selects to keep them)
-        have     = have - consume - (okB ? needB : 0u);
-        off      = okB ? oB : off_next;
-        extended = okB ? (lenB == kTokenMax ? 1u : 0u) : ext_next;
-        done    |= stop | (endm & (concat ? 0u : 1u));
-
-        // ---- drain finished output, 16 bytes per lane at a time (the wave goes there when some group is due)
-        const bool due = count - flushed >= kDecDrain;
-        if (__builtin_amdgcn_ballot_w64(due) != 0ull) {
-            if (due) {
-#pragma unroll
-                for (uint32_t piece = 0; piece < kDecDrainStores; piece++) {
-                    const uint32_t q = 16u * (j + kDecLanes * piece);
-                    const uint32_t p = flushed + q;
-                    uint32_t fp = fpos + kDecPiece * piece;
-                    fp = fp >= kDecRing ? fp - kDecRing : fp;
-                    const uint4 v = *reinterpret_cast<const uint4 *>(ring8 + fp + 16u * j);
-                    if (dst16) {
-                        *reinterpret_cast<uint4 *>(dst + p) = v;
-                    } else {
-                        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                        for (uint32_t t = 0; t < 16; t++) dst[p + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
-                    }
-                }
-                flushed += kDecDrain;
-                fpos = fpos + kDecDrain >= kDecRing ? fpos + kDecDrain - kDecRing : fpos + kDecDrain;
-            }
-        }
-    }
-
-    for (uint32_t i = flushed + j; i < count; i += kDecLanes) {
-        uint32_t r = fpos + (i - flushed);
-        r = r >= kDecRing ? r - kDecRing : r;
-        dst[i] = ring8[r];
-    }
-    if (live && j == 0u) out_len[b] = count;
-}
-
 
 // ---- flags as masks (0 or all ones) for the mask form of the decoder below.  What gfx950 charges for an instruction
 // (tools/probes/valu_rates, profiles/r05/valu_rates.txt; two or more wavefronts per SIMD): add, subtract, and / or / xor,
@@ -802,6 +74,10 @@ __device__ __forceinline__ uint32_t twice(uint32_t x) { uint32_t r; asm("v_add_u
 // the 16-bit minimum and maximum (full rate; the operands' upper halves are ignored, the result's is zero on gfx9)
 __device__ __forceinline__ uint32_t min16(uint32_t a, uint32_t b) { uint32_t r; asm("v_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ uint32_t max16i(uint32_t a, uint32_t b) { uint32_t r; asm("v_max_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// x mod kDecRing for x < 2 * kDecRing (wrap1) or x < 3 * kDecRing (wrap2): what is too small wraps around to something huge
+// (in 16 bits: kDecRing and the sums are far below 2^16)
+__device__ __forceinline__ uint32_t dec_wrap1(uint32_t x) { return min16(x, x - kDecRing); }
+__device__ __forceinline__ uint32_t dec_wrap2(uint32_t x) { return min16(min16(x, x - kDecRing), x - 2u * kDecRing); }
 
 typedef __attribute__((address_space(3))) uint8_t dec_lds_u8_t;
 __device__ __forceinline__ uint32_t dec_lds_at(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p; }
@@ -883,9 +159,24 @@ __device__ __forceinline__ bool dec_packed_entry(const DecPacked &pk, const uint
     return ok;
 }
 
-// The same decoder with its flags as masks: the one-word feed with one token a trip or two (the 96-bit form stays above).
+// The decoder.  Its forms, picked per wavefront by what its streams' lengths say about them (the kernels below); a wavefront never
+// changes form on the way:
+// TWO: a second token in the same trip where that is possible.  Text is mostly short matches (3.4 bytes a token: one token a
+// trip is 3.0 bytes a trip) and gains a quarter by it; high-entropy data (runs of seven literals) and long runs (nibble after
+// nibble) lose 16 - 20 % to the extra instructions.  The second token is taken when the first is a run of literals or a whole
+// match without extension, the next token is a match with a real offset whose bits are all there, both fit the trip's 16
+// byte slots and the room, and the second copy reads nothing the first writes (offset >= both lengths together: no
+// replication inside it either).  Otherwise it is simply the next trip's first token: nothing about it can stop a stream.
+// WIDE: a 96-bit bit buffer fed with up to TWO words per trip (never across a 128-byte chunk).  A run of seven literals is 63
+// bits and one word a trip is 32: on high-entropy data the loop was fed, not decoding -- 3.5 literals a trip.  Costs ~25
+// instructions a trip: the form for streams that are longer than nine tenths of their output.
+// The feed never masks the stream's last word: what follows the stream in it lies past `have` bits, is never joined by
+// another word, and every rule of the step counts bits before it believes them (`need`).  A stream that is done may still be
+// fed once or twice: nothing reads its buffer any more.
+// CONCAT: the file rule -- after an end marker the pad bits up to the byte boundary are dropped and the next stream follows
+// (compile time: the pad bits cost the one-shot rule nothing).  CHAN, RUN, PACKED: see DecChan and DecPacked above.
 template <bool TWO, bool WIDE, bool CONCAT, bool CHAN = false, bool RUN = false, bool PACKED = false>
-__device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
+__device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
                                       uint32_t *__restrict__ out_len,
                                       const uint8_t *__restrict__ in, size_t in_stride,
                                       const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
@@ -999,220 +290,187 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
     uint32_t produced = 0;                                         // (RUN) output of the run so far
     uint32_t pb = b;                                               // the packet
     for (uint32_t k = 0;; k++) {
-    if constexpr (PACKED) {
-        if (k > 0u && (pk_fits || k == kDecGroups)) break;
-        if (!pk_fits) {                                            // (too far apart: group k alone)
-            live = live_all && g == k;
-            if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
-            n = live ? pk_n : 0u;
-            cap = live ? pk_room : 0u;
-        }
-    }
-    if constexpr (RUN) {
-        const uint32_t at = r_at + k;
-        live = live_run && at < r_end;
-        if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
-        pb = live ? ch.sidx[at] : 0u;
-        bb = pb;
-        src = in + (size_t)bb * in_stride;
-        n = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
-        dst = out + (size_t)bb * out_stride;
-        dst16 = ((uintptr_t)dst & 15u) == 0;
-        cap = live ? out_cap : 0u;
-    }
-
-    // ---- the input as aligned words: word k holds stream bytes [4k - skew, 4k - skew + 4).  A
-    // group takes 16 x kDecLanes bytes at a time: lane j holds words 4j .. 4j + 3 of the current
-    // chunk (one coalesced load for the group) and of the next one, requested a chunk ahead; the
-    // word the group feeds next comes across the lanes (ds_bpermute), fetched a step before it is
-    // used.  (Sixteen bytes at a time in every lane meant a load every other step somewhere in
-    // the wavefront, and the wave waited ~1 us for each.)  The loads are BUFFER loads bounded by
-    // the end of the last of the wavefront's streams: past it they return zeros instead of
-    // faulting, so the end of a stream is no special case (what lies past it is never fed: `rem`
-    // below), and lanes that do not move on load what they have again -- one load instruction for
-    // the whole wavefront, not waited for until the chunk is needed.
-    const uint32_t skew = (uint32_t)((uintptr_t)src & 3u);
-    const uint32_t b0 = blockIdx.x * per_wave;
-    // (RUN: the packets of a trip lie anywhere in the input -- the launcher sees to it that all of it is one 32-bit extent, or
-    // gives each wavefront one run)
-    const uint8_t *wave_in = PACKED ? nullptr : (RUN ? (per_wave == 1u ? src : in) : in + (size_t)b0 * in_stride);
-    uintptr_t in_lo = (uintptr_t)wave_in & ~(uintptr_t)3;
-    const uint32_t rel = live ? (uint32_t)(RUN ? (per_wave == 1u ? (size_t)0 : (size_t)pb * in_stride) : (size_t)(b - b0) * in_stride) : 0u;      // my stream, from wave_in
-    uint32_t wave_end = 0;
-    // (PACKED) where my stream's first word lies from in_lo, and the end of the last word that holds a byte of it: a lane loads
-    // nothing outside its own stream's words (see bload)
-    uint32_t pk_at = 0, pk_end = 0;
-    if constexpr (PACKED) {
-        if (pk_fits) {
-            in_lo = (uintptr_t)pk_lo;
-            wave_end = pk_extent;
-            pk_at = pk_rel;
-        } else {                                                   // group k's stream alone
-            const int at = (int)(k * kDecLanes);
-            const uintptr_t first = (uintptr_t)src & ~(uintptr_t)3;
-            in_lo = (uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)first >> 32), at) << 32) |
-                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at));
-            wave_end = (uint32_t)__builtin_amdgcn_readlane((int)(skew + n), at);
-        }
-        pk_end = n != 0u ? (pk_at + skew + n + 3u) & ~3u : 0u;
-    } else {
-#pragma unroll
-    for (uint32_t gg = 0; gg < kDecGroups; gg++) {
-        const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)(rel + n), (int)(gg * kDecLanes));
-        wave_end = e > wave_end ? e : wave_end;
-    }
-    }
-    // (the descriptor is the same in every lane, and said to be: or the load sits in a loop over the distinct ones)
-    const uintptr_t in_lo_u = ((uintptr_t)uniform((uint32_t)((uint64_t)in_lo >> 32)) << 32) | uniform((uint32_t)in_lo);
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)in_lo_u, 0, (int)uniform((wave_end + (uint32_t)((uintptr_t)wave_in & 3u) + 3u) & ~3u), 0x00020000);
-    const auto bload = [&](uint32_t byte_off) {
         if constexpr (PACKED) {
-            // sixteen bytes that lie in the lane's own stream's words as one load; what lies past them altogether from an
-            // offset past every extent (zeros, and no access); the piece the stream ends in word by word, where some lane is there
-            const bool whole = byte_off + 16u <= pk_end;
-            u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(whole ? byte_off : 0xFFFFFFF0u), 0, 0);
-            const bool part = !whole && byte_off < pk_end;
-            if (__builtin_amdgcn_ballot_w64(part) != 0ull) {
-                if (part) {
-                    v.x = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)byte_off, 0, 0);
-                    if (byte_off + 4u < pk_end) v.y = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off + 4u), 0, 0);
-                    if (byte_off + 8u < pk_end) v.z = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off + 8u), 0, 0);
+            if (k > 0u && (pk_fits || k == kDecGroups)) break;
+            if (!pk_fits) {                                            // (too far apart: group k alone)
+                live = live_all && g == k;
+                if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
+                n = live ? pk_n : 0u;
+                cap = live ? pk_room : 0u;
+            }
+        }
+        if constexpr (RUN) {
+            const uint32_t at = r_at + k;
+            live = live_run && at < r_end;
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
+            pb = live ? ch.sidx[at] : 0u;
+            bb = pb;
+            src = in + (size_t)bb * in_stride;
+            n = live ? (in_len ? in_len[bb] : in_len_uniform) : 0u;
+            dst = out + (size_t)bb * out_stride;
+            dst16 = ((uintptr_t)dst & 15u) == 0;
+            cap = live ? out_cap : 0u;
+        }
+
+        // ---- the input as aligned words: word k holds stream bytes [4k - skew, 4k - skew + 4).  A
+        // group takes 16 x kDecLanes bytes at a time: lane j holds words 4j .. 4j + 3 of the current
+        // chunk (one coalesced load for the group) and of the next one, requested a chunk ahead; the
+        // word the group feeds next comes across the lanes (ds_bpermute), fetched a step before it is
+        // used.  (Sixteen bytes at a time in every lane meant a load every other step somewhere in
+        // the wavefront, and the wave waited ~1 us for each.)  The loads are BUFFER loads bounded by
+        // the end of the last of the wavefront's streams: past it they return zeros instead of
+        // faulting, so the end of a stream is no special case (what lies past it is never fed: `rem`
+        // below), and lanes that do not move on load what they have again -- one load instruction for
+        // the whole wavefront, not waited for until the chunk is needed.
+        const uint32_t skew = (uint32_t)((uintptr_t)src & 3u);
+        const uint32_t b0 = blockIdx.x * per_wave;
+        // (RUN: the packets of a trip lie anywhere in the input -- the launcher sees to it that all of it is one 32-bit extent, or
+        // gives each wavefront one run)
+        const uint8_t *wave_in = PACKED ? nullptr : (RUN ? (per_wave == 1u ? src : in) : in + (size_t)b0 * in_stride);
+        uintptr_t in_lo = (uintptr_t)wave_in & ~(uintptr_t)3;
+        const uint32_t rel = live ? (uint32_t)(RUN ? (per_wave == 1u ? (size_t)0 : (size_t)pb * in_stride) : (size_t)(b - b0) * in_stride) : 0u;      // my stream, from wave_in
+        uint32_t wave_end = 0;
+        // (PACKED) where my stream's first word lies from in_lo, and the end of the last word that holds a byte of it: a lane loads
+        // nothing outside its own stream's words (see bload)
+        uint32_t pk_at = 0, pk_end = 0;
+        if constexpr (PACKED) {
+            if (pk_fits) {
+                in_lo = (uintptr_t)pk_lo;
+                wave_end = pk_extent;
+                pk_at = pk_rel;
+            } else {                                                   // group k's stream alone
+                const int at = (int)(k * kDecLanes);
+                const uintptr_t first = (uintptr_t)src & ~(uintptr_t)3;
+                in_lo = (uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)first >> 32), at) << 32) |
+                                    (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at));
+                wave_end = (uint32_t)__builtin_amdgcn_readlane((int)(skew + n), at);
+            }
+            pk_end = n != 0u ? (pk_at + skew + n + 3u) & ~3u : 0u;
+        } else {
+#pragma unroll
+        for (uint32_t gg = 0; gg < kDecGroups; gg++) {
+            const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)(rel + n), (int)(gg * kDecLanes));
+            wave_end = e > wave_end ? e : wave_end;
+        }
+        }
+        // (the descriptor is the same in every lane, and said to be: or the load sits in a loop over the distinct ones)
+        const uintptr_t in_lo_u = ((uintptr_t)uniform((uint32_t)((uint64_t)in_lo >> 32)) << 32) | uniform((uint32_t)in_lo);
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)in_lo_u, 0, (int)uniform((wave_end + (uint32_t)((uintptr_t)wave_in & 3u) + 3u) & ~3u), 0x00020000);
+        const auto bload = [&](uint32_t byte_off) {
+            if constexpr (PACKED) {
+                // sixteen bytes that lie in the lane's own stream's words as one load; what lies past them altogether from an
+                // offset past every extent (zeros, and no access); the piece the stream ends in word by word, where some lane is there
+                const bool whole = byte_off + 16u <= pk_end;
+                u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(whole ? byte_off : 0xFFFFFFF0u), 0, 0);
+                const bool part = !whole && byte_off < pk_end;
+                if (__builtin_amdgcn_ballot_w64(part) != 0ull) {
+                    if (part) {
+                        v.x = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)byte_off, 0, 0);
+                        if (byte_off + 4u < pk_end) v.y = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off + 4u), 0, 0);
+                        if (byte_off + 8u < pk_end) v.z = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off + 8u), 0, 0);
+                    }
                 }
-            }
+                return make_uint4(v.x, v.y, v.z, v.w);
+            } else {
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, 0);
             return make_uint4(v.x, v.y, v.z, v.w);
-        } else {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, 0);
-        return make_uint4(v.x, v.y, v.z, v.w);
-        }
-    };
-    constexpr uint32_t kChunk = 16u * kDecLanes;                    // bytes
-    uint32_t nxt_off = (PACKED ? pk_at : (uint32_t)((uintptr_t)(src - skew) - in_lo)) + 16u * j + kChunk;
-    uint4 cur = bload(nxt_off - kChunk), nxt = bload(nxt_off);
-    const uint32_t glane4 = (lane & ~(kDecLanes - 1u)) << 2;       // byte index of the group's lane 0 for ds_bpermute
-    // A lane's four words ROTATE by one with every word its group takes, so that the word to feed next (word wi of the
-    // stream) is always in cur.x of lane (wi / 4) mod 8, and the one after it in cur.y of the lane that holds that:
-    // one address and one ds_bpermute a trip, no select on wi as well.  (32 words to a chunk: the next chunk moves
-    // in when the rotation is back at 0.)
-    const auto rotate = [&](uint32_t on) {
-        const uint32_t x0 = cur.x;
-        cur.x = on ? cur.y : cur.x; cur.y = on ? cur.z : cur.y; cur.z = on ? cur.w : cur.z; cur.w = on ? x0 : cur.w;
-    };
-    static_assert(kChunk == 16u * kDecLanes, "a lane holds four words of the chunk");
-    const auto fetch = [&](uint32_t wi_) {
-        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(glane4 + (wi_ & (4u * kDecLanes - 4u))), (int)cur.x);
-    };
-    const auto fetch_after = [&](uint32_t wi_) {
-        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(glane4 + ((wi_ + 1u) & (4u * kDecLanes - 4u))), (int)cur.y);
-    };
-    uint64_t bits = 0;        // left-aligned bit buffer
-    uint32_t have = 0;        // valid bits in it
-    uint32_t left = n;        // bytes of the stream not fed yet
-    uint32_t wi   = 0;        // next word to feed
-    {
-        const uint32_t first = fetch(0);
-        if (n) {
-            uint32_t w = __builtin_bswap32(first) << (8u * skew);
-            const uint32_t avail = 4u - skew < n ? 4u - skew : n;
-            if (avail < 4u) w &= ~0u << (32u - 8u * avail);
-            bits = (uint64_t)w << 32;
-            have = 8u * avail;
-            left = n - avail;
-            wi = 1;
-        }
-    }
-    rotate(wi);
-    uint32_t nextw = fetch(wi);
-    uint32_t nextw2 = WIDE ? fetch_after(wi) : 0u;                 // (WIDE: the word after it; only used when in the same chunk)
-    uint32_t bits_lo = 0;                                          // (WIDE: bits 64..95 of the buffer, left-aligned)
-    // PACKED: a stream's output starts anywhere, fifteen times in sixteen off a 16-byte boundary, where the drain below would
-    // store byte by byte.  So the drains start at the first boundary of dst, `head` bytes in: every piece is an aligned store
-    // fed from the window at an unaligned position (dec_ring_load16), and the head bytes go out byte by byte with the first
-    // drain, or with the tail if there is none.  (-DLZS_PACKED_BYTE_DRAIN: the strided calls' drain, for the measurement.)
-#ifdef LZS_PACKED_BYTE_DRAIN
-    constexpr bool kPackedHead = false;
-#else
-    constexpr bool kPackedHead = PACKED;
-#endif
-    const uint32_t head = kPackedHead ? (0u - (uint32_t)(uintptr_t)dst) & 15u : 0u;
-    uint32_t head_left = head;
-    uint32_t count = 0, flushed = head, off = 0;
-    uint32_t m_ext = 0;                                            // "a length nibble follows", as a mask
-    uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? run_pos : head;  // count and flushed modulo kDecRing
-    uint32_t m_done = live ? 0u : ~0u;                             // the stream has stopped, as a mask
-    uint32_t m_eos = 0u;                                           // (CHAN) ... at an end marker
-    uint32_t m_cut = 0u;                                           // (CHAN) a copy lost bytes to the room: no end marker counts after it
-    // overlapping copies replicate with period off: byte idx of a step comes from byte idx mod off.  Lane j's
-    // bytes are j and j + 8: a 3-bit entry per off = 0 .. 8 (0 and 8 and more: j itself), a 4-bit one per off = 0 .. 15
-    uint32_t mod_lo = 0; uint64_t mod_hi = 0;
-    uint64_t mod_tab[kDecSlots];                                   // (four lanes: a 4-bit entry per off = 0 .. 15 for each of the lane's four bytes)
-    if (kDecLanes == 8u) {
-#pragma unroll
-        for (uint32_t e = 0; e <= 8u; e++) mod_lo |= ((e == 0u || e == 8u) ? j : j % (e ? e : 1u)) << (3u * e);
-#pragma unroll
-        for (uint32_t e = 0; e < 16u; e++) mod_hi |= (uint64_t)(e == 0u ? j + 8u : (j + 8u) % (e ? e : 1u)) << (4u * e);
-    }
-#pragma unroll
-    for (uint32_t sl = 0; sl < kDecSlots; sl++) {
-        mod_tab[sl] = 0;
-#pragma unroll
-        for (uint32_t e = 0; e < 16u; e++) mod_tab[sl] |= (uint64_t)(e == 0u ? j + kDecLanes * sl : (j + kDecLanes * sl) % (e ? e : 1u)) << (4u * e);
-    }
-
-
-    // per-lane constants of the loop
-    const uint32_t lit_shift = 55u - 9u * (j < 7u ? j : 6u);      // where byte j of a run of literals sits in the bit buffer
-    const uint32_t ring_at = dec_lds_at(ring8), dummy_at = dec_lds_at(dummy8);   // (LDS addresses as numbers: a select between them is one bitop3)
-    static_assert(kDecLanes == 8u, "the mask form is written for eight lanes a stream");
-    for (;;) {
-        if (__builtin_amdgcn_ballot_w64(m_done == 0u) == 0ull) break;
-        // ---- refill (:181-187): one word per step keeps more than a token's worth in the buffer (the last word is not
-        // masked and a stream that is done may still be fed: see lzs_decompress_blocks_grp)
-        if (!WIDE) {
-            const uint32_t nb4 = min(left, 4u);                    // (left may be anything up to LZS_BLOCK_MAX -- no m_nz of it --; this is 0 .. 4)
-            const uint32_t m_rf = m_lt(have, 33u) & m_nz(nb4);
-            const uint32_t nb = nb4 & m_rf;                        // bytes taken
-            const uint32_t w = __builtin_bswap32(nextw) & m_rf;
-            bits |= (uint64_t)w << ((32u - have) & 63u);
-            have = (nb << 3) + have;
-            left -= nb;
-            wi   -= m_rf;                                          // (+ 1 where the mask is -1)
-            const uint32_t x0 = cur.x;
-            cur.x = m_sel(m_rf, cur.y, cur.x); cur.y = m_sel(m_rf, cur.z, cur.y); cur.z = m_sel(m_rf, cur.w, cur.z); cur.w = m_sel(m_rf, x0, cur.w);
-            // the chunk is used up: the next one moves in, the one after is requested
-            const uint32_t not_roll = m_ornot(wi & (4u * kDecLanes - 1u), m_rf);   // 0 where a word was taken and it was the chunk's last
-            if (__builtin_amdgcn_ballot_w64(not_roll == 0u) != 0ull) {
-                const bool roll = not_roll == 0u;
-                cur.x = roll ? nxt.x : cur.x; cur.y = roll ? nxt.y : cur.y;
-                cur.z = roll ? nxt.z : cur.z; cur.w = roll ? nxt.w : cur.w;
-                nxt_off = roll ? nxt_off + kChunk : nxt_off;
-                nxt = bload(nxt_off);
             }
-            nextw = fetch(wi);
-        } else {
-            // two words where 64 bits or fewer are left (the second only from the same chunk: its copy was fetched a trip ago
-            // like the first's); the buffer is bits : bits_lo, 96 bits.  As masks too: a word that is not taken is a word of
-            // zeros OR-ed in, so nothing of the buffer needs a select.
-            uint32_t m_took = 0u;
+        };
+        constexpr uint32_t kChunk = 16u * kDecLanes;                    // bytes
+        uint32_t nxt_off = (PACKED ? pk_at : (uint32_t)((uintptr_t)(src - skew) - in_lo)) + 16u * j + kChunk;
+        uint4 cur = bload(nxt_off - kChunk), nxt = bload(nxt_off);
+        const uint32_t glane4 = (lane & ~(kDecLanes - 1u)) << 2;       // byte index of the group's lane 0 for ds_bpermute
+        // A lane's four words ROTATE by one with every word its group takes, so that the word to feed next (word wi of the
+        // stream) is always in cur.x of lane (wi / 4) mod 8, and the one after it in cur.y of the lane that holds that:
+        // one address and one ds_bpermute a trip, no select on wi as well.  (32 words to a chunk: the next chunk moves
+        // in when the rotation is back at 0.)
+        const auto rotate = [&](uint32_t on) {
+            const uint32_t x0 = cur.x;
+            cur.x = on ? cur.y : cur.x; cur.y = on ? cur.z : cur.y; cur.z = on ? cur.w : cur.z; cur.w = on ? x0 : cur.w;
+        };
+        static_assert(kChunk == 16u * kDecLanes, "a lane holds four words of the chunk");
+        const auto fetch = [&](uint32_t wi_) {
+            return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(glane4 + (wi_ & (4u * kDecLanes - 4u))), (int)cur.x);
+        };
+        const auto fetch_after = [&](uint32_t wi_) {
+            return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(glane4 + ((wi_ + 1u) & (4u * kDecLanes - 4u))), (int)cur.y);
+        };
+        uint64_t bits = 0;        // left-aligned bit buffer
+        uint32_t have = 0;        // valid bits in it
+        uint32_t left = n;        // bytes of the stream not fed yet
+        uint32_t wi   = 0;        // next word to feed
+        {
+            const uint32_t first = fetch(0);
+            if (n) {
+                uint32_t w = __builtin_bswap32(first) << (8u * skew);
+                const uint32_t avail = 4u - skew < n ? 4u - skew : n;
+                if (avail < 4u) w &= ~0u << (32u - 8u * avail);
+                bits = (uint64_t)w << 32;
+                have = 8u * avail;
+                left = n - avail;
+                wi = 1;
+            }
+        }
+        rotate(wi);
+        uint32_t nextw = fetch(wi);
+        uint32_t nextw2 = WIDE ? fetch_after(wi) : 0u;                 // (WIDE: the word after it; only used when in the same chunk)
+        uint32_t bits_lo = 0;                                          // (WIDE: bits 64..95 of the buffer, left-aligned)
+        // PACKED: a stream's output starts anywhere, fifteen times in sixteen off a 16-byte boundary, where the drain below would
+        // store byte by byte.  So the drains start at the first boundary of dst, `head` bytes in: every piece is an aligned store
+        // fed from the window at an unaligned position (dec_ring_load16), and the head bytes go out byte by byte with the first
+        // drain, or with the tail if there is none.  (-DLZS_PACKED_BYTE_DRAIN: the strided calls' drain, for the measurement.)
+#ifdef LZS_PACKED_BYTE_DRAIN
+        constexpr bool kPackedHead = false;
+#else
+        constexpr bool kPackedHead = PACKED;
+#endif
+        const uint32_t head = kPackedHead ? (0u - (uint32_t)(uintptr_t)dst) & 15u : 0u;
+        uint32_t head_left = head;
+        uint32_t count = 0, flushed = head, off = 0;
+        uint32_t m_ext = 0;                                            // "a length nibble follows", as a mask
+        uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? run_pos : head;  // count and flushed modulo kDecRing
+        uint32_t m_done = live ? 0u : ~0u;                             // the stream has stopped, as a mask
+        uint32_t m_eos = 0u;                                           // (CHAN) ... at an end marker
+        uint32_t m_cut = 0u;                                           // (CHAN) a copy lost bytes to the room: no end marker counts after it
+        // overlapping copies replicate with period off: byte idx of a step comes from byte idx mod off.  Lane j's
+        // bytes are j and j + 8: a 3-bit entry per off = 0 .. 8 (0 and 8 and more: j itself), a 4-bit one per off = 0 .. 15
+        uint32_t mod_lo = 0; uint64_t mod_hi = 0;
+        // (mod_tab: what is left of the four-lane tables, read by nothing.  Taking it out leaves every instruction as it is
+        // and moves the order of this set-up's in six kernels, which then have to be measured: profiles/r12/decoder_refactor.txt)
+        uint64_t mod_tab[2];
+        if (kDecLanes == 8u) {
 #pragma unroll
-            for (int r = 0; r < 2; r++) {
-                const uint32_t nb4 = min(left, 4u);                // (left may be anything up to LZS_BLOCK_MAX; this is 0 .. 4)
-                uint32_t m_rf = m_lt(have, 65u) & m_nz(nb4);
-                if (r == 1) m_rf &= m_took & m_nz(wi & (4u * kDecLanes - 1u));   // the second only after the first, and from the same chunk
-                m_took = m_rf;
-                const uint32_t w = __builtin_bswap32(r == 0 ? nextw : nextw2) & m_rf;     // (the stream's last word not masked)
-                const uint32_t nb = nb4 & m_rf;                    // bytes taken
-                // w at bit offset `have` (0 .. 64) of the 96: its part in the upper 64 bits and what falls below them
-                const uint64_t hi = ((uint64_t)w << 32) >> (have & 63u);           // (have = 64: all of it falls below)
-                const uint32_t keep_hi = m_lt(have, 64u);
-                const uint32_t lo = (uint32_t)((uint64_t)w << ((64u - have) & 63u)) & m_lt(32u, have);
-                bits    |= hi & (((uint64_t)keep_hi << 32) | keep_hi);
-                bits_lo |= lo;
-                have += nb << 3;
+            for (uint32_t e = 0; e <= 8u; e++) mod_lo |= ((e == 0u || e == 8u) ? j : j % (e ? e : 1u)) << (3u * e);
+#pragma unroll
+            for (uint32_t e = 0; e < 16u; e++) mod_hi |= (uint64_t)(e == 0u ? j + 8u : (j + 8u) % (e ? e : 1u)) << (4u * e);
+        }
+#pragma unroll
+        for (uint32_t sl = 0; sl < 2u; sl++) {
+            mod_tab[sl] = 0;
+#pragma unroll
+            for (uint32_t e = 0; e < 16u; e++) mod_tab[sl] |= (uint64_t)(e == 0u ? j + kDecLanes * sl : (j + kDecLanes * sl) % (e ? e : 1u)) << (4u * e);
+        }
+
+        // per-lane constants of the loop
+        const uint32_t lit_shift = 55u - 9u * (j < 7u ? j : 6u);      // where byte j of a run of literals sits in the bit buffer
+        const uint32_t ring_at = dec_lds_at(ring8), dummy_at = dec_lds_at(dummy8);   // (LDS addresses as numbers: a select between them is one bitop3)
+        for (;;) {
+            if (__builtin_amdgcn_ballot_w64(m_done == 0u) == 0ull) break;
+            // ---- refill (:181-187): one word per step keeps more than a token's worth in the buffer (the last word is not
+            // masked and a stream that is done may still be fed: see the header)
+            if (!WIDE) {
+                const uint32_t nb4 = min(left, 4u);                    // (left may be anything up to LZS_BLOCK_MAX -- no m_nz of it --; this is 0 .. 4)
+                const uint32_t m_rf = m_lt(have, 33u) & m_nz(nb4);
+                const uint32_t nb = nb4 & m_rf;                        // bytes taken
+                const uint32_t w = __builtin_bswap32(nextw) & m_rf;
+                bits |= (uint64_t)w << ((32u - have) & 63u);
+                have = (nb << 3) + have;
                 left -= nb;
-                wi   -= m_rf;                                      // (+ 1 where the mask is -1)
+                wi   -= m_rf;                                          // (+ 1 where the mask is -1)
                 const uint32_t x0 = cur.x;
                 cur.x = m_sel(m_rf, cur.y, cur.x); cur.y = m_sel(m_rf, cur.z, cur.y); cur.z = m_sel(m_rf, cur.w, cur.z); cur.w = m_sel(m_rf, x0, cur.w);
+                // the chunk is used up: the next one moves in, the one after is requested
                 const uint32_t not_roll = m_ornot(wi & (4u * kDecLanes - 1u), m_rf);   // 0 where a word was taken and it was the chunk's last
                 if (__builtin_amdgcn_ballot_w64(not_roll == 0u) != 0ull) {
                     const bool roll = not_roll == 0u;
@@ -1221,196 +479,229 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp_m(DecGroupLds &L, uint
                     nxt_off = roll ? nxt_off + kChunk : nxt_off;
                     nxt = bload(nxt_off);
                 }
+                nextw = fetch(wi);
+            } else {
+                // two words where 64 bits or fewer are left (the second only from the same chunk: its copy was fetched a trip ago
+                // like the first's); the buffer is bits : bits_lo, 96 bits.  As masks too: a word that is not taken is a word of
+                // zeros OR-ed in, so nothing of the buffer needs a select.
+                uint32_t m_took = 0u;
+#pragma unroll
+                for (int r = 0; r < 2; r++) {
+                    const uint32_t nb4 = min(left, 4u);                // (left may be anything up to LZS_BLOCK_MAX; this is 0 .. 4)
+                    uint32_t m_rf = m_lt(have, 65u) & m_nz(nb4);
+                    if (r == 1) m_rf &= m_took & m_nz(wi & (4u * kDecLanes - 1u));   // the second only after the first, and from the same chunk
+                    m_took = m_rf;
+                    const uint32_t w = __builtin_bswap32(r == 0 ? nextw : nextw2) & m_rf;     // (the stream's last word not masked)
+                    const uint32_t nb = nb4 & m_rf;                    // bytes taken
+                    // w at bit offset `have` (0 .. 64) of the 96: its part in the upper 64 bits and what falls below them
+                    const uint64_t hi = ((uint64_t)w << 32) >> (have & 63u);           // (have = 64: all of it falls below)
+                    const uint32_t keep_hi = m_lt(have, 64u);
+                    const uint32_t lo = (uint32_t)((uint64_t)w << ((64u - have) & 63u)) & m_lt(32u, have);
+                    bits    |= hi & (((uint64_t)keep_hi << 32) | keep_hi);
+                    bits_lo |= lo;
+                    have += nb << 3;
+                    left -= nb;
+                    wi   -= m_rf;                                      // (+ 1 where the mask is -1)
+                    const uint32_t x0 = cur.x;
+                    cur.x = m_sel(m_rf, cur.y, cur.x); cur.y = m_sel(m_rf, cur.z, cur.y); cur.z = m_sel(m_rf, cur.w, cur.z); cur.w = m_sel(m_rf, x0, cur.w);
+                    const uint32_t not_roll = m_ornot(wi & (4u * kDecLanes - 1u), m_rf);   // 0 where a word was taken and it was the chunk's last
+                    if (__builtin_amdgcn_ballot_w64(not_roll == 0u) != 0ull) {
+                        const bool roll = not_roll == 0u;
+                        cur.x = roll ? nxt.x : cur.x; cur.y = roll ? nxt.y : cur.y;
+                        cur.z = roll ? nxt.z : cur.z; cur.w = roll ? nxt.w : cur.w;
+                        nxt_off = roll ? nxt_off + kChunk : nxt_off;
+                        nxt = bload(nxt_off);
+                    }
+                }
+                nextw = fetch(wi);
+                nextw2 = fetch_after(wi);
             }
-            nextw = fetch(wi);
-            nextw2 = fetch_after(wi);
-        }
-        const uint32_t room = min(cap - count, 255u);              // (all that is asked of it: is it 0, is it less than a step)
-        const uint32_t top = (uint32_t)(bits >> 32);
+            const uint32_t room = min(cap - count, 255u);              // (all that is asked of it: is it 0, is it less than a step)
+            const uint32_t top = (uint32_t)(bits >> 32);
 
-        // ---- the three kinds of step, side by side
-        const uint32_t m_t31 = m_sign(top);
-        const uint32_t m_lit = m_nor(m_t31, m_ext);               // a run of literals
-        const uint32_t m_mat = m_andnot(m_t31, m_ext);            // a match token
-        const uint32_t e = top >> 28;                              // a length nibble (:370-406)
-        // a run of literals (:217-233): token i of an all-literal run starts at bit 63 - 9i
-        uint32_t kv;
-        if (TWO) {                                                 // four a trip at most, counted in the upper word
-            kv = min16(ffbh_u32(top & 0x80402010u), 36u) >> 3;     // 0 9 18 27 36 leading zeros: 0 1 2 3 4 literals
-        } else {
-            const uint32_t lead_hi = ffbh_u32(top & 0x80402010u), lead_lo = ffbh_u32((uint32_t)bits & 0x08040200u) | 32u;
-            kv = min16(min16(lead_hi, lead_lo), 63u) >> 3;         // 0 9 .. 54, or none (ffbh of 0 is all ones: 0xFFFF in 16 bits): 0 .. 7 literals
-        }
-        kv = min16(min16(kv, __umul24(have, 57u) >> 9), room);     // no more than the bits that are there (have / 9) and the room
-        // a match token: 1 s ooooooo[oooo] cccc (:238-342)
-        const uint32_t m_short = m_sign(twice(top));
-        const uint32_t short4 = m_short & 4u;
-        const uint32_t norm = (top & 0x3FFFFFFFu) >> short4;
-        const uint32_t o = norm >> 19;
-        const uint32_t code = (norm >> 15) & 0xFu;
-        const uint32_t len = max16i(((norm >> 17) & 3u) + 2u, code - 7u);          // 2 2 2 2 3 3 3 3 4 4 4 4 5 6 7 8
-        const uint32_t used = 13u - short4;
-        const uint32_t width = 4u - (m_lt(code, 12u) & 2u);
-        const uint32_t m_zoff = m_z(o);
-        const uint32_t m_copying = m_andnot(m_mat, m_zoff);       // a match token with a real offset
-        // bits the step needs; short of them it stops for good (:222, 240, 250, 274, 334, 375)
-        const uint32_t need_mat = used + m_andnot(width, m_zoff);
-        const uint32_t need = m_sel(m_ext, 4u, m_sel(m_lit, 9u, need_mat));
-        // :189 (no bits: every step needs four at least), :200 and mid-copy :361-364 (no room), and the token's own stops
-        const uint32_t m_stop = m_lt(have, need) | m_z(room);
-        const uint32_t m_go = m_nor(m_done, m_stop);
-        const uint32_t m_endm = m_mat & m_zoff & m_short;         // end marker (:255-260 / file rule :564-576)
-        // (CHAN) the end marker is reached; it needs no room, so a full output may end at it -- also behind the closing
-        // length nibble 0 of a copy that filled the output.  Not after a copy the room cut short (m_cut): its token was
-        // consumed whole but not all of its bytes were written, so the output is not the packet's
-        if constexpr (CHAN) {
-            const uint32_t m_nib0_end = m_ext & m_z(e) & m_z(((top << 4) >> 23) ^ 0x180u) & ~m_lt(have, 13u);
-            m_eos |= m_andnot((m_endm & ~m_lt(have, 9u)) | m_nib0_end, m_done | m_cut);
-        }
-        uint32_t consume = m_sel(m_lit, (kv << 3) + kv, need);
-        // file rule: after an end marker drop the pad bits up to the byte boundary and go on
-        if (CONCAT) consume += m_endm & ((have - used) & 7u);
-        const uint32_t copy_len = m_sel(m_ext, e, len & m_copying);
-        const uint32_t off_now = m_sel(m_copying, o, off);
-        // long offset 0: no copy, and the offset register is cleared (:280); an end marker leaves it
-        const uint32_t off_next = m_andnot(off_now, m_andnot(m_mat & m_zoff, m_short));
-        const uint32_t m_ext_next = m_sel(m_ext, m_lt(14u, e), m_copying & m_lt(7u, len));
-        const uint32_t m = min16(copy_len, room);
-        if constexpr (CHAN) m_cut |= m_andnot(m_go, m_lit) & m_lt(m, copy_len);   // (a run of literals is cut unread, a copy is not)
-        const uint32_t nA = m_sel(m_lit, kv, m) & m_go;           // bytes of this step's (first) token
-        // ---- TWO: a second token in the same trip (see lzs_decompress_blocks_grp for when; two of its conditions follow
-        // from the others -- a second offset of 0 cannot be >= both lengths together, and a first copy cut by the room
-        // leaves no room for a second)
-        uint32_t m_okB = 0u, nB = 0u, oB = 0u, lenB = 0u, needB = 0u;
-        if (TWO) {
-            const uint32_t topB = (uint32_t)((bits << (consume & 63u)) >> 32);
-            const uint32_t haveB = have - consume;                 // (meaningless unless go)
-            const uint32_t m_shortB = m_sign(twice(topB));
-            const uint32_t short4B = m_shortB & 4u;
-            const uint32_t normB = (topB & 0x3FFFFFFFu) >> short4B;
-            oB = normB >> 19;
-            const uint32_t codeB = (normB >> 15) & 0xFu;
-            lenB = max16i(((normB >> 17) & 3u) + 2u, codeB - 7u);
-            needB = 17u - (m_lt(codeB, 12u) & 2u) - short4B;
-            const uint32_t m_firstA = (m_lit | m_andnot(m_copying, m_ext_next)) & m_go;
-            const uint32_t both = nA + lenB;
+            // ---- the three kinds of step, side by side
+            const uint32_t m_t31 = m_sign(top);
+            const uint32_t m_lit = m_nor(m_t31, m_ext);               // a run of literals
+            const uint32_t m_mat = m_andnot(m_t31, m_ext);            // a match token
+            const uint32_t e = top >> 28;                              // a length nibble (:370-406)
+            // a run of literals (:217-233): token i of an all-literal run starts at bit 63 - 9i
+            uint32_t kv;
+            if (TWO) {                                                 // four a trip at most, counted in the upper word
+                kv = min16(ffbh_u32(top & 0x80402010u), 36u) >> 3;     // 0 9 18 27 36 leading zeros: 0 1 2 3 4 literals
+            } else {
+                const uint32_t lead_hi = ffbh_u32(top & 0x80402010u), lead_lo = ffbh_u32((uint32_t)bits & 0x08040200u) | 32u;
+                kv = min16(min16(lead_hi, lead_lo), 63u) >> 3;         // 0 9 .. 54, or none (ffbh of 0 is all ones: 0xFFFF in 16 bits): 0 .. 7 literals
+            }
+            kv = min16(min16(kv, __umul24(have, 57u) >> 9), room);     // no more than the bits that are there (have / 9) and the room
+            // a match token: 1 s ooooooo[oooo] cccc (:238-342)
+            const uint32_t m_short = m_sign(twice(top));
+            const uint32_t short4 = m_short & 4u;
+            const uint32_t norm = (top & 0x3FFFFFFFu) >> short4;
+            const uint32_t o = norm >> 19;
+            const uint32_t code = (norm >> 15) & 0xFu;
+            const uint32_t len = max16i(((norm >> 17) & 3u) + 2u, code - 7u);          // 2 2 2 2 3 3 3 3 4 4 4 4 5 6 7 8
+            const uint32_t used = 13u - short4;
+            const uint32_t width = 4u - (m_lt(code, 12u) & 2u);
+            const uint32_t m_zoff = m_z(o);
+            const uint32_t m_copying = m_andnot(m_mat, m_zoff);       // a match token with a real offset
+            // bits the step needs; short of them it stops for good (:222, 240, 250, 274, 334, 375)
+            const uint32_t need_mat = used + m_andnot(width, m_zoff);
+            const uint32_t need = m_sel(m_ext, 4u, m_sel(m_lit, 9u, need_mat));
+            // :189 (no bits: every step needs four at least), :200 and mid-copy :361-364 (no room), and the token's own stops
+            const uint32_t m_stop = m_lt(have, need) | m_z(room);
+            const uint32_t m_go = m_nor(m_done, m_stop);
+            const uint32_t m_endm = m_mat & m_zoff & m_short;         // end marker (:255-260 / file rule :564-576)
+            // (CHAN) the end marker is reached; it needs no room, so a full output may end at it -- also behind the closing
+            // length nibble 0 of a copy that filled the output.  Not after a copy the room cut short (m_cut): its token was
+            // consumed whole but not all of its bytes were written, so the output is not the packet's
+            if constexpr (CHAN) {
+                const uint32_t m_nib0_end = m_ext & m_z(e) & m_z(((top << 4) >> 23) ^ 0x180u) & ~m_lt(have, 13u);
+                m_eos |= m_andnot((m_endm & ~m_lt(have, 9u)) | m_nib0_end, m_done | m_cut);
+            }
+            uint32_t consume = m_sel(m_lit, (kv << 3) + kv, need);
+            // file rule: after an end marker drop the pad bits up to the byte boundary and go on
+            if (CONCAT) consume += m_endm & ((have - used) & 7u);
+            const uint32_t copy_len = m_sel(m_ext, e, len & m_copying);
+            const uint32_t off_now = m_sel(m_copying, o, off);
+            // long offset 0: no copy, and the offset register is cleared (:280); an end marker leaves it
+            const uint32_t off_next = m_andnot(off_now, m_andnot(m_mat & m_zoff, m_short));
+            const uint32_t m_ext_next = m_sel(m_ext, m_lt(14u, e), m_copying & m_lt(7u, len));
+            const uint32_t m = min16(copy_len, room);
+            if constexpr (CHAN) m_cut |= m_andnot(m_go, m_lit) & m_lt(m, copy_len);   // (a run of literals is cut unread, a copy is not)
+            const uint32_t nA = m_sel(m_lit, kv, m) & m_go;           // bytes of this step's (first) token
+            // ---- TWO: a second token in the same trip (the header says when; two of its conditions follow
+            // from the others -- a second offset of 0 cannot be >= both lengths together, and a first copy cut by the room
+            // leaves no room for a second)
+            uint32_t m_okB = 0u, nB = 0u, oB = 0u, lenB = 0u, needB = 0u;
+            if (TWO) {
+                const uint32_t topB = (uint32_t)((bits << (consume & 63u)) >> 32);
+                const uint32_t haveB = have - consume;                 // (meaningless unless go)
+                const uint32_t m_shortB = m_sign(twice(topB));
+                const uint32_t short4B = m_shortB & 4u;
+                const uint32_t normB = (topB & 0x3FFFFFFFu) >> short4B;
+                oB = normB >> 19;
+                const uint32_t codeB = (normB >> 15) & 0xFu;
+                lenB = max16i(((normB >> 17) & 3u) + 2u, codeB - 7u);
+                needB = 17u - (m_lt(codeB, 12u) & 2u) - short4B;
+                const uint32_t m_firstA = (m_lit | m_andnot(m_copying, m_ext_next)) & m_go;
+                const uint32_t both = nA + lenB;
 #ifndef LZS_DEC_TWO_MAX
 #define LZS_DEC_TWO_MAX 16
 #endif
-            const uint32_t lim = min16(min16(oB, (uint32_t)LZS_DEC_TWO_MAX), room);      // both <= 16, <= room, <= oB (so oB is not 0)
-            m_okB = m_firstA & m_sign(topB) & m_nor(m_lt(haveB, needB), m_lt(lim, both));
-            nB = lenB & m_okB;
-        }
-        const uint32_t nwrite = nA + nB;
+                const uint32_t lim = min16(min16(oB, (uint32_t)LZS_DEC_TWO_MAX), room);      // both <= 16, <= room, <= oB (so oB is not 0)
+                m_okB = m_firstA & m_sign(topB) & m_nor(m_lt(haveB, needB), m_lt(lim, both));
+                nB = lenB & m_okB;
+            }
+            const uint32_t nwrite = nA + nB;
 
-        // ---- lane j of the group produces byte j of the step, and byte j + 8; overlap replicates with period off
+            // ---- lane j of the group produces byte j of the step, and byte j + 8; overlap replicates with period off
 #pragma unroll
-        for (uint32_t sl = 0; sl < 2u; sl++) {
-            if (sl > 0u && __builtin_amdgcn_ballot_w64(nwrite > 8u) == 0ull) break;
-            const uint32_t idx = j + 8u * sl;                      // byte of the step
-            // idx mod off from the lane's table (idx itself for off 0 and for off > idx)
-            uint32_t k1;
-            if (sl == 0u) { const uint32_t o8 = min16(off_now, 8u); k1 = (mod_lo >> (o8 + o8 + o8)) & 7u; }
-            else          k1 = off_now < 16u ? (uint32_t)(mod_hi >> (4u * (off_now & 15u))) & 15u : idx;
-            uint32_t k = k1, oo = off_now, m_second = 0u;
-            if (TWO) {                                             // a byte past the first token is the second's: no replication there
-                m_second = ~m_lt(idx, nA);
-                k = m_sel(m_second, idx, k1);
-                oo = m_sel(m_second, oB, off_now);
-            }
-            // source: position count + k - off (a part of the window nothing has been written to reads as the zero the rule asks for)
-            const uint32_t sx = cpos + k + (kDecRing - oo);        // < 2 * kDecRing + 15
-            const uint32_t sp = min16(min16(sx, sx - kDecRing), sx - 2u * kDecRing);
-            const uint32_t copied = *dec_lds_byte(ring_at + sp);
-            const uint32_t wx = cpos + idx;
-            const uint32_t wp = min16(wx, wx - kDecRing);
-            dec_lds_u8_t *const to = dec_lds_byte(m_sel(m_lt(idx, nwrite), ring_at + wp, dummy_at));
-            uint32_t val = copied;
-            if (sl == 0u) {                                        // (this slot can hold a literal of a run)
-                const uint32_t lit = (uint32_t)(bits >> lit_shift) & 0xFFu;
-                val = m_sel(m_andnot(m_lit, m_second), lit, copied);
-            }
-            *to = (uint8_t)val;
-        }
-
-        count = count + nwrite;
-        { const uint32_t cx = cpos + nwrite; cpos = min16(cx, cx - kDecRing); }
-        // (a stream that has stopped writes nothing any more, so what happens to its buffer, offset and flags from here on is
-        // nobody's business: no selects to keep them)
-        const uint32_t shift = consume + (needB & m_okB);          // (<= 36 + 17: one shift for both tokens)
-        if (WIDE) {                                                // (never with TWO) 96 bits move up by `consume` < 64
-            const uint32_t cs = consume & 63u;
-            const uint64_t lo64 = (uint64_t)bits_lo << 32;
-            const uint32_t m_cs = m_nz(cs);                        // (a shift by 64 - 0 would be a shift by 0)
-            const uint64_t carry = (lo64 >> ((64u - cs) & 63u)) & (((uint64_t)m_cs << 32) | m_cs);
-            bits = (bits << cs) | carry;
-            bits_lo = (uint32_t)((lo64 << cs) >> 32);
-        } else {
-            bits <<= (shift & 63u);
-        }
-        have  -= shift;
-        off    = TWO ? m_sel(m_okB, oB, off_next) : off_next;
-        m_ext  = TWO ? m_sel(m_okB, m_lt(7u, lenB), m_ext_next) : m_ext_next;
-        m_done |= m_stop | (CONCAT ? 0u : m_endm);
-
-        // ---- drain finished output, 16 bytes per lane at a time (the wave goes there when some group is due)
-        const bool due = kPackedHead ? (count - flushed >= kDecDrain && count >= flushed) : count - flushed >= kDecDrain;
-        if (__builtin_amdgcn_ballot_w64(due) != 0ull) {
-            if (due) {
-                if constexpr (kPackedHead) {                       // (the first drain: the window has not wrapped yet)
-                    for (uint32_t i = j; i < head_left; i += kDecLanes) dst[i] = ring8[i];
-                    head_left = 0;
+            for (uint32_t sl = 0; sl < 2u; sl++) {
+                if (sl > 0u && __builtin_amdgcn_ballot_w64(nwrite > 8u) == 0ull) break;
+                const uint32_t idx = j + 8u * sl;                      // byte of the step
+                // idx mod off from the lane's table (idx itself for off 0 and for off > idx)
+                uint32_t k1;
+                if (sl == 0u) { const uint32_t o8 = min16(off_now, 8u); k1 = (mod_lo >> (o8 + o8 + o8)) & 7u; }
+                else          k1 = off_now < 16u ? (uint32_t)(mod_hi >> (4u * (off_now & 15u))) & 15u : idx;
+                uint32_t k = k1, oo = off_now, m_second = 0u;
+                if (TWO) {                                             // a byte past the first token is the second's: no replication there
+                    m_second = ~m_lt(idx, nA);
+                    k = m_sel(m_second, idx, k1);
+                    oo = m_sel(m_second, oB, off_now);
                 }
-#pragma unroll
-                for (uint32_t piece = 0; piece < kDecDrainStores; piece++) {
-                    const uint32_t p = flushed + kDecPiece * piece + 16u * j;
-                    uint32_t fp = fpos + kDecPiece * piece;
-                    fp = fp >= kDecRing ? fp - kDecRing : fp;
-                    uint4 v;
-                    if constexpr (RUN || kPackedHead) v = dec_ring_load16(ring8, fp + 16u * j);
-                    else v = *reinterpret_cast<const uint4 *>(ring8 + fp + 16u * j);
-                    if (kPackedHead || dst16) {
-                        *reinterpret_cast<uint4 *>(dst + p) = v;
-                    } else {
-                        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                        for (uint32_t t = 0; t < 16; t++) dst[p + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
+                // source: position count + k - off (a part of the window nothing has been written to reads as the zero the rule asks for)
+                const uint32_t sx = cpos + k + (kDecRing - oo);        // < 2 * kDecRing + 15
+                const uint32_t sp = dec_wrap2(sx);
+                const uint32_t copied = *dec_lds_byte(ring_at + sp);
+                const uint32_t wx = cpos + idx;
+                const uint32_t wp = dec_wrap1(wx);
+                dec_lds_u8_t *const to = dec_lds_byte(m_sel(m_lt(idx, nwrite), ring_at + wp, dummy_at));
+                uint32_t val = copied;
+                if (sl == 0u) {                                        // (this slot can hold a literal of a run)
+                    const uint32_t lit = (uint32_t)(bits >> lit_shift) & 0xFFu;
+                    val = m_sel(m_andnot(m_lit, m_second), lit, copied);
+                }
+                *to = (uint8_t)val;
+            }
+
+            count = count + nwrite;
+            cpos = dec_wrap1(cpos + nwrite);
+            // (a stream that has stopped writes nothing any more, so what happens to its buffer, offset and flags from here on is
+            // nobody's business: no selects to keep them)
+            const uint32_t shift = consume + (needB & m_okB);          // (<= 36 + 17: one shift for both tokens)
+            if (WIDE) {                                                // (never with TWO) 96 bits move up by `consume` < 64
+                const uint32_t cs = consume & 63u;
+                const uint64_t lo64 = (uint64_t)bits_lo << 32;
+                const uint32_t m_cs = m_nz(cs);                        // (a shift by 64 - 0 would be a shift by 0)
+                const uint64_t carry = (lo64 >> ((64u - cs) & 63u)) & (((uint64_t)m_cs << 32) | m_cs);
+                bits = (bits << cs) | carry;
+                bits_lo = (uint32_t)((lo64 << cs) >> 32);
+            } else {
+                bits <<= (shift & 63u);
+            }
+            have  -= shift;
+            off    = TWO ? m_sel(m_okB, oB, off_next) : off_next;
+            m_ext  = TWO ? m_sel(m_okB, m_lt(7u, lenB), m_ext_next) : m_ext_next;
+            m_done |= m_stop | (CONCAT ? 0u : m_endm);
+
+            // ---- drain finished output, 16 bytes per lane at a time (the wave goes there when some group is due)
+            const bool due = kPackedHead ? (count - flushed >= kDecDrain && count >= flushed) : count - flushed >= kDecDrain;
+            if (__builtin_amdgcn_ballot_w64(due) != 0ull) {
+                if (due) {
+                    if constexpr (kPackedHead) {                       // (the first drain: the window has not wrapped yet)
+                        for (uint32_t i = j; i < head_left; i += kDecLanes) dst[i] = ring8[i];
+                        head_left = 0;
                     }
+#pragma unroll
+                    for (uint32_t piece = 0; piece < kDecDrainStores; piece++) {
+                        const uint32_t p = flushed + kDecPiece * piece + 16u * j;
+                        uint32_t fp = fpos + kDecPiece * piece;
+                        fp = fp >= kDecRing ? fp - kDecRing : fp;
+                        uint4 v;
+                        if constexpr (RUN || kPackedHead) v = dec_ring_load16(ring8, fp + 16u * j);
+                        else v = *reinterpret_cast<const uint4 *>(ring8 + fp + 16u * j);
+                        if (kPackedHead || dst16) {
+                            *reinterpret_cast<uint4 *>(dst + p) = v;
+                        } else {
+                            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                            for (uint32_t t = 0; t < 16; t++) dst[p + t] = (uint8_t)(w[t >> 2] >> (8 * (t & 3)));
+                        }
+                    }
+                    flushed += kDecDrain;
+                    fpos = fpos + kDecDrain >= kDecRing ? fpos + kDecDrain - kDecRing : fpos + kDecDrain;
                 }
-                flushed += kDecDrain;
-                fpos = fpos + kDecDrain >= kDecRing ? fpos + kDecDrain - kDecRing : fpos + kDecDrain;
             }
         }
-    }
 
-    if constexpr (kPackedHead) {                                   // (no drain took them: the window has not wrapped)
-        for (uint32_t i = j; i < (head_left < count ? head_left : count); i += kDecLanes) dst[i] = ring8[i];
-    }
-    for (uint32_t i = flushed + j; i < count; i += kDecLanes) {
-        uint32_t r = fpos + (i - flushed);
-        r = r >= kDecRing ? r - kDecRing : r;
-        dst[i] = ring8[r];
-    }
-    if (live && j == 0u) out_len[pb] = count;
-    if constexpr (RUN) {
-        if (live && j == 0u && ch.status) ch.status[pb] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
-        produced += live ? count : 0u;
-        run_pos = cpos;
-    } else if constexpr (CHAN) {
-        if (live) {
-            // the new history: hist[0, H) = the last H bytes of history | output (output byte count - H + i is at window
-            // position cpos - H + i), hist[H, 2048) = 0 -- the bytes the compressor writes
-            const uint32_t H = min(hlen + count, kWindow);
-            dec_put_history(cst, ring8, cpos, H, j);
-            if (j == 0u) {
-                *reinterpret_cast<uint32_t *>(cst) = H;
-                if (ch.status) ch.status[b] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
-            }
-        } else if (!PACKED && cst && j == 0u) {                    // not a state: nothing is written, nothing changes
-            out_len[b] = 0;
-            if (ch.status) ch.status[b] = 0x10u;
+        if constexpr (kPackedHead) {                                   // (no drain took them: the window has not wrapped)
+            for (uint32_t i = j; i < (head_left < count ? head_left : count); i += kDecLanes) dst[i] = ring8[i];
         }
-    }
-    if constexpr (!RUN && !PACKED) break;
+        for (uint32_t i = flushed + j; i < count; i += kDecLanes) {
+            uint32_t r = fpos + (i - flushed);
+            r = r >= kDecRing ? r - kDecRing : r;
+            dst[i] = ring8[r];
+        }
+        if (live && j == 0u) out_len[pb] = count;
+        if constexpr (RUN) {
+            if (live && j == 0u && ch.status) ch.status[pb] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
+            produced += live ? count : 0u;
+            run_pos = cpos;
+        } else if constexpr (CHAN) {
+            if (live) {
+                // the new history: hist[0, H) = the last H bytes of history | output (output byte count - H + i is at window
+                // position cpos - H + i), hist[H, 2048) = 0 -- the bytes the compressor writes
+                const uint32_t H = min(hlen + count, kWindow);
+                dec_put_history(cst, ring8, cpos, H, j);
+                if (j == 0u) {
+                    *reinterpret_cast<uint32_t *>(cst) = H;
+                    if (ch.status) ch.status[b] = (uint8_t)(m_eos ? 0x04u : (count >= cap ? 0x08u : 0x03u));
+                }
+            } else if (!PACKED && cst && j == 0u) {                    // not a state: nothing is written, nothing changes
+                out_len[b] = 0;
+                if (ch.status) ch.status[b] = 0x10u;
+            }
+        }
+        if constexpr (!RUN && !PACKED) break;
     }
     // (RUN) the run's history goes back once, at its end
     if constexpr (RUN) {
@@ -1448,15 +739,9 @@ void lzs_decompress_blocks_grp_kernel(uint8_t *__restrict__ out, size_t out_stri
 #ifdef LZS_DEC_ONE_TOKEN
     lzs_decompress_blocks_grp<false, false, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
 #else
-#ifndef LZS_DEC_COMPARES     // (the compare-and-select form: A/B builds, tools/probes/abdec.sh)
-    if (two)       lzs_decompress_blocks_grp_m<true, false, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
-    else if (wide) lzs_decompress_blocks_grp_m<false, true, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
-    else           lzs_decompress_blocks_grp_m<false, false, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
-#else
     if (two)       lzs_decompress_blocks_grp<true, false, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
     else if (wide) lzs_decompress_blocks_grp<false, true, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
     else           lzs_decompress_blocks_grp<false, false, CONCAT>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nblocks, concat, per_wave);
-#endif
 #endif
 }
 
@@ -1483,9 +768,9 @@ void lzs_decompress_channels_grp_kernel(uint8_t *__restrict__ out, size_t out_st
     const bool wide = uniform(10ull * total >= 9ull * full ? 1u : 0u) != 0u;
     DecChan ch;
     ch.states = states; ch.channel = channel; ch.status = status;
-    if (two)       lzs_decompress_blocks_grp_m<true, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
-    else if (wide) lzs_decompress_blocks_grp_m<false, true, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
-    else           lzs_decompress_blocks_grp_m<false, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
+    if (two)       lzs_decompress_blocks_grp<true, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
+    else if (wide) lzs_decompress_blocks_grp<false, true, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
+    else           lzs_decompress_blocks_grp<false, false, false, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, npackets, 0u, per_wave, ch);
 }
 
 // Many packets per channel (include/lzs/lzs_channels.h, lzs_decompress_channels_burst_device; DESIGN.md 3.11): group g of
@@ -1519,7 +804,7 @@ void lzs_decompress_runs_grp_kernel(uint8_t *__restrict__ out, size_t out_stride
     DecChan ch;
     ch.states = states; ch.status = status;
     ch.run_key = run_key; ch.run_at = run_at; ch.run_end = run_end; ch.skey = skey; ch.sidx = sidx; ch.nchannels = nchannels;
-    if (two)       lzs_decompress_blocks_grp_m<true, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
-    else if (wide) lzs_decompress_blocks_grp_m<false, true, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
-    else           lzs_decompress_blocks_grp_m<false, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
+    if (two)       lzs_decompress_blocks_grp<true, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
+    else if (wide) lzs_decompress_blocks_grp<false, true, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
+    else           lzs_decompress_blocks_grp<false, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
 }

@@ -4,7 +4,7 @@
 
 // Packed streams to packed outputs: lzs_decompress_blocks_grp_kernel<false> (CHAN false) and lzs_decompress_channels_grp_kernel
 // (CHAN true) with every stream's place, length and room taken from offset arrays on the device -- the PACKED mode of
-// lzs_decompress_blocks_grp_m.  Eight entries to a wavefront always: whether their input fits one 32-bit extent is only known
+// lzs_decompress_blocks_grp.  Eight entries to a wavefront always: whether their input fits one 32-bit extent is only known
 // here, and the decoder deals with it.
 template <bool CHAN>
 __global__ __launch_bounds__(64)
@@ -34,9 +34,9 @@ void lzs_decompress_packed_grp_kernel(uint8_t *__restrict__ out, const uint64_t 
     const bool wide = uniform(10ull * total >= 9ull * full ? 1u : 0u) != 0u;
     DecChan ch;
     if constexpr (CHAN) { ch.states = states; ch.channel = channel; ch.status = status; }
-    if (two)       lzs_decompress_blocks_grp_m<true, false, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
-    else if (wide) lzs_decompress_blocks_grp_m<false, true, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
-    else           lzs_decompress_blocks_grp_m<false, false, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
+    if (two)       lzs_decompress_blocks_grp<true, false, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
+    else if (wide) lzs_decompress_blocks_grp<false, true, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
+    else           lzs_decompress_blocks_grp<false, false, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
 }
 
 // offsets[0] = 0, offsets[b + 1] = offsets[b] + size[b] rounded up to a multiple of pad + 1 (a power of two): lzs_scan_lengths_kernel

@@ -313,6 +313,37 @@ void lzs_scan_stream_kernel(const uint8_t *__restrict__ in, uint32_t n, uint32_t
 // eighth of the instructions (the walk of one segment is as long as before, ~0.5 ms, but a GiB of
 // text is 2300 wavefronts of them, all resident at once).  Each lane reads its own segment, 16
 // bytes at a time.
+// The scan's token arithmetic, in compares and selects (the walk is one lane a segment and waits for its input, not for the
+// vector unit; the decoders' step, kernels/decompress_blocks.inc, has the same identities as masks).
+// The fields of a match token 1 s ooooooo[oooo] cccc at the top of `top` (lzs-decompression.c:238-342), every
+// decoder's way: a short token moved down four bits has its fields where a long one has them (offset 29..19, code
+// 18..15).  short4: 4 for a 7-bit offset, 0 for an 11-bit one -- the token is 13 - short4 bits up to its length code,
+// and that is 2 bits (lengths 2 3 4) below code 12, 4 bits (5 6 7 8) from there.
+__device__ __forceinline__ void dec_match_fields(uint32_t top, uint32_t &short4, uint32_t &o, uint32_t &code, uint32_t &len)
+{
+    short4 = (uint32_t)((int32_t)(top << 1) >> 31) & 4u;
+    const uint32_t norm = (top & 0x3FFFFFFFu) >> short4;
+    o = norm >> 19;
+    code = (norm >> 15) & 0xFu;
+    len = (uint32_t)max((int32_t)(((norm >> 17) & 3u) + 2u), (int32_t)code - 7);      // 2 2 2 2 3 3 3 3 4 4 4 4 5 6 7 8
+}
+
+// How many of the tokens at the top of the 64 bits top : low are literals, one after the other (:217-233): token i of
+// an all-literal run starts at bit 63 - 9i, so the first set type bit among those ends the run.  SHORT: counted in the
+// upper word alone, four at most (where matches dominate, runs are short).  The caller clips to the bits it has.
+template <bool SHORT>
+__device__ __forceinline__ uint32_t dec_literal_run(uint32_t top, uint32_t low)
+{
+    uint32_t lead;
+    if (SHORT) {
+        lead = min(ffbh_u32(top & 0x80402010u), 36u);
+    } else {
+        const uint32_t lead_hi = ffbh_u32(top & 0x80402010u), lead_lo = ffbh_u32(low & 0x08040200u) | 32u;
+        lead = min(min(lead_hi, lead_lo), 64u);                    // (ffbh of 0 is huge: all seven are literals)
+    }
+    return __umul24(lead, 57u) >> 9;                               // lead / 9 for lead <= 64
+}
+
 constexpr uint32_t kScanWin = 32;                     // words of input a lane of the scan keeps in LDS
 template <uint32_t LANES, bool CONCAT>
 __global__ __launch_bounds__(64)
@@ -695,8 +726,7 @@ void lzs_decode_stream_g8_kernel(uint8_t *__restrict__ out, uint32_t cap_all, ui
             }
             nextw = fetch(wi);
         } else {       // two words where 64 bits or fewer are left, the second only from the same chunk: bits : bits_lo, 96 bits
-#ifndef LZS_DEC_COMPARES
-            // (as masks, like lzs_decompress_blocks_grp_m's: a word that is not taken is a word of zeros OR-ed in)
+            // (as masks, like lzs_decompress_blocks_grp's: a word that is not taken is a word of zeros OR-ed in)
             uint32_t m_took = 0u;
 #pragma unroll
             for (int r = 0; r < 2; r++) {
@@ -725,38 +755,11 @@ void lzs_decode_stream_g8_kernel(uint8_t *__restrict__ out, uint32_t cap_all, ui
                     nxt4 = bload(nxt_off);
                 }
             }
-#else
-            uint32_t took = 0;
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                const uint32_t same = r == 0 ? 1u : (took & ((wi & 31u) != 0u ? 1u : 0u));
-                const uint32_t rf = (have <= 64u) & (left != 0u) & same;
-                took = rf;
-                const uint32_t w = __builtin_bswap32(r == 0 ? nextw : nextw2);
-                const uint32_t nb = min(left, 4u);                 // bytes taken
-                const uint64_t hi = have <= 32u ? (uint64_t)w << ((32u - have) & 63u) : (uint64_t)w >> ((have - 32u) & 63u);
-                const uint32_t lo = have > 32u ? (uint32_t)((uint64_t)w << ((64u - have) & 63u)) : 0u;
-                bits    = rf ? bits | hi : bits;
-                bits_lo = rf ? bits_lo | lo : bits_lo;
-                have = rf ? have + 8u * nb : have;
-                left = rf ? left - nb : left;
-                wi   = rf ? wi + 1u : wi;
-                rotate(rf);
-                const bool roll = rf && (wi & 31u) == 0u;
-                if (__builtin_amdgcn_ballot_w64(roll) != 0ull) {
-                    cur4.x = roll ? nxt4.x : cur4.x; cur4.y = roll ? nxt4.y : cur4.y;
-                    cur4.z = roll ? nxt4.z : cur4.z; cur4.w = roll ? nxt4.w : cur4.w;
-                    nxt_off = roll ? nxt_off + 128u : nxt_off;
-                    nxt4 = bload(nxt_off);
-                }
-            }
-#endif
             nextw = fetch(wi);
             nextw2 = fetch_after(wi);
         }
         const uint32_t top = (uint32_t)(bits >> 32), low = (uint32_t)bits;
-#ifndef LZS_DEC_COMPARES
-        // ---- the step with its flags as masks (lzs_decompress_blocks_grp_m, kernels/decompress_blocks.inc: a compare or a select
+        // ---- the step with its flags as masks (lzs_decompress_blocks_grp, kernels/decompress_blocks.inc: a compare or a select
         // costs the SIMD twice what an add or a v_bitop3 does); the 0 / 1 words the slots below read are made of them at the end
         const uint32_t m_ext = 0u - extended;
         const uint32_t m_t31 = m_sign(top);
@@ -822,58 +825,6 @@ void lzs_decode_stream_g8_kernel(uint8_t *__restrict__ out, uint32_t cap_all, ui
         const uint32_t is_lit = m_lit & 1u;
         const uint32_t ext_next = m_ext_next & 1u;
         const uint32_t endm = m_endm & 1u;
-#else
-        const uint32_t is_ext = extended;
-        const uint32_t is_lit = (is_ext ^ 1u) & ((top >> 31) ^ 1u);
-        const uint32_t is_mat = (is_ext ^ 1u) & (top >> 31);
-        const uint32_t e = top >> 28;                              // a length nibble (:370-406)
-        // a run of literals that start inside this segment
-        uint32_t kv = dec_literal_run<TWO>(top, low);              // (TWO: four a trip at most)
-        const uint32_t fit = __umul24(have, 57u) >> 9;             // have / 9
-        kv = kv < fit ? kv : fit;
-        const uint32_t mine_lit = __umul24(min(kDecEnd - cur + 8u, 72u), 57u) >> 9;     // those that start in this segment: (bits left + 8) / 9, eight and more as eight
-        kv = kv < mine_lit ? kv : mine_lit;
-        // a match token
-        uint32_t short4, o, code, len;
-        dec_match_fields(top, short4, o, code, len);
-        const uint32_t is_short = short4 >> 2;
-        const uint32_t used = 13u - short4;
-        const uint32_t width = code < 0xCu ? 2u : 4u;
-        const uint32_t zero_off = o == 0u ? 1u : 0u;
-        const uint32_t copying = is_mat & (zero_off ^ 1u);
-        const uint32_t need = is_ext ? 4u : (is_lit ? 9u : (zero_off ? used : used + width));
-        // the token's own stops and :189 (no bits: every step needs four at least); the next token belongs to the next
-        // segment; output full (:200)
-        const uint32_t stop = ((have < need) | (cur >= kDecEnd) | (count >= room)) ? 1u : 0u;
-        const uint32_t go = (done | stop) ^ 1u;
-        const uint32_t endm = is_mat & zero_off & is_short;
-        uint32_t consume = is_lit ? 9u * kv : need;
-        consume += (endm & concat) ? ((have - used) & 7u) : 0u;
-        const uint32_t copy_len = is_ext ? e : (copying ? len : 0u);
-        const uint32_t off_now = copying ? o : off;
-        const uint32_t off_next = (is_mat & zero_off & (is_short ^ 1u)) ? 0u : off_now;
-        const uint32_t ext_next = is_ext ? (e == kNibbleMax ? 1u : 0u) : (copying & (len == kTokenMax ? 1u : 0u));
-        const uint32_t nA = go ? (is_lit ? kv : copy_len) : 0u;    // bytes of this step's (first) token
-        // ---- TWO: the next token too, if it is a match with a real offset that starts inside this
-        // segment, its bits are all there, both fit the trip's 16 byte slots, and its copy reads
-        // nothing the first token writes (offset >= both lengths together); else it is the next
-        // trip's first token.  (The output's capacity is checked byte by byte below, as before.)
-        uint32_t okB = 0u, nB = 0u, oB = 0u, lenB = 0u, needB = 0u;
-        uint64_t bitsB = 0;
-        if (TWO) {
-            bitsB = bits << (consume & 63u);
-            const uint32_t topB = (uint32_t)(bitsB >> 32);
-            const uint32_t haveB = have - consume;                 // (meaningless unless go)
-            uint32_t short4B, codeB;
-            dec_match_fields(topB, short4B, oB, codeB, lenB);
-            needB = (codeB < 0xCu ? 15u : 17u) - short4B;
-            const uint32_t firstA = (is_lit | (copying & (ext_next ^ 1u))) & go;
-            okB = firstA & (topB >> 31) & (oB != 0u ? 1u : 0u) & (haveB >= needB ? 1u : 0u) &
-                  (oB >= nA + lenB ? 1u : 0u) & (nA + lenB <= 16u ? 1u : 0u) &
-                  (cur + consume < kDecEnd ? 1u : 0u) & (count + nA < room ? 1u : 0u);
-            nB = okB ? lenB : 0u;
-        }
-#endif
         const uint32_t nwrite = nA + nB;
 
 #pragma unroll
@@ -933,11 +884,7 @@ void lzs_decode_stream_g8_kernel(uint8_t *__restrict__ out, uint32_t cap_all, ui
             bits = (bits << cs) | carry;
             bits_lo = (uint32_t)((lo64 << cs) >> 32);
         } else {
-#ifndef LZS_DEC_COMPARES
             bits <<= ((consume + (okB ? needB : 0u)) & 63u);                         // (at most 36 + 17: one shift for both tokens)
-#else
-            bits = okB ? bitsB << needB : bits << (consume & 63u);                   // (two shifts: up to 80 bits)
-#endif
         }
         // (a segment that has stopped writes nothing any more -- nA and okB hang on `go`, `done` is for good -- so its
         // buffer, position, offset and flags need no selects to stay as they are)

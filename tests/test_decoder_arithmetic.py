@@ -1,6 +1,7 @@
-"""The integer identities the decoders' inner loops rest on (csrc/kernels/decompress_blocks.inc: dec_match_fields,
-dec_literal_run, dec_wrap1 / dec_wrap2, the per-lane tables of idx mod off; decompress_stream.inc: the two-plane
-window, the scan's beat), restated in Python with 32-bit wrap-around and checked exhaustively against the plain
+"""The integer identities the decoders' inner loops rest on (csrc/kernels/decompress_blocks.inc: the match fields and the
+literal-run count of a step, dec_wrap1 / dec_wrap2, the per-lane tables of idx mod off; decompress_stream.inc: the scan's
+dec_match_fields and dec_literal_run -- the same identities in compares and selects --, the two-plane window, the scan's
+beat), restated in Python with 32-bit wrap-around and checked exhaustively against the plain
 form of the rule (lzs-decompression.c:217-233, 238-342).  No GPU: these are the kernels' host-checkable halves."""
 import itertools
 
@@ -27,7 +28,7 @@ def match_fields_plain(top):
 
 
 def match_fields_kernel(top):
-    """dec_match_fields: a short token moved down four bits has its fields where a long one has them."""
+    """The match fields (dec_match_fields, and the step's as masks): a short token moved down four bits has its fields where a long one has them."""
     sign = M32 if (u32(top << 1) >> 31) else 0          # (int32)(top << 1) >> 31
     short4 = sign & 4
     norm = (top & 0x3FFFFFFF) >> short4
@@ -77,6 +78,23 @@ def test_literal_run_counts():
         assert (x * 57) >> 9 == x // 9
     for left9 in range(0, 400):                                              # literals that start inside the segment
         assert (min(left9, 72) * 57) >> 9 == min(left9 // 9, 8)
+
+
+def test_literal_run_counts_by_16_bit_minimum():
+    """The decoders' step counts a run as min16(ffbh(..), 36) >> 3 (four at most, the upper word alone) or
+    min16(min16(hi, lo | 32), 63) >> 3 (seven at most) where the scan multiplies by 57 and shifts by 9: the same count for
+    every number of leading zeros there can be -- 0, 9, .. 63 -- and for none.  (v_min_u16 reads the lower halves of its
+    operands: ffbh's all-ones for "no bit set" is 0xFFFF there.)"""
+    min16 = lambda a, b: min(a & 0xFFFF, b & 0xFFFF)
+    leads_hi = [ffbh(1 << (31 - z)) for z in (0, 9, 18, 27)] + [ffbh(0)]          # type bits of the upper word: 0x80402010
+    leads_lo = [ffbh(1 << (31 - z)) for z in (4, 13, 22)] + [ffbh(0)]             # of the lower word: 0x08040200
+    assert leads_hi[:4] == [0, 9, 18, 27] and leads_lo[:3] == [4, 13, 22]
+    for hi in leads_hi:
+        assert min16(hi, 36) >> 3 == (min(hi, 36) * 57) >> 9 == min(hi, 36) // 9
+        for lo in leads_lo:
+            lead = min(hi, lo | 32, 64)                                          # 0, 9, .. 54, or 64 for none (63 as masks)
+            assert lead in (0, 9, 18, 27, 36, 45, 54, 64)
+            assert min16(min16(hi, lo | 32), 63) >> 3 == (lead * 57) >> 9 == min(lead // 9, 7)
 
 
 def test_ring_positions_by_min():
