@@ -391,7 +391,7 @@ static int host_batch(const char *who, launch_fn launch, uint8_t *out, size_t ou
     staging_t *st = staging_get();
     if (!st) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
 
-#define HIP_TRY(call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto done; } } while (0)
+#define HIP_TRY(call, what) HIP_TRY_OR(done, call, what)
     if (!st->stream) HIP_TRY(lzs_hip_stream_create(&st->stream), "hipStreamCreate");
     stream = st->stream;
     e = staging_reserve(st, BUF_IN, d_in_stride * nblocks, &d_in);

@@ -26,6 +26,9 @@ LZS_HIDDEN extern _Thread_local char tls_error[512];
 LZS_HIDDEN int fail(int code, const char *fmt, ...);
 LZS_HIDDEN int hip_fail(int hip_error, const char *what);
 LZS_HIDDEN int require_device(void);
+/* A HIP call of the shim in a function with `int e, rc`: on an error its message is recorded, rc is the LZS_E_* code and the
+ * function goes on at `label`. */
+#define HIP_TRY_OR(label, call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto label; } } while (0)
 
 /* The development switches of the environment (tools/README.md), read ONCE per process by lzs_env() -- the
  * entry points ask a struct, not getenv().  LZS_DEV_ENV=1 (set before the first call: the test suites do)

@@ -28,7 +28,6 @@ LZS_HIDDEN double now_ms(void)
 
 #define STREAM_SEG_MAX 65536u
 
-
 /* Segment size for a stream of n bytes: 64 KiB for long streams, much smaller for shorter ones so
  * that they too spread over the device -- a workgroup alone on a CU takes 15 us per KiB, and every
  * segment pays for a 2.2 KB warm-up of its chains (HASH and CHAIN only).  Measured in round 3 (text,
@@ -50,6 +49,20 @@ static uint32_t stream_seg(size_t n)
     if (seg < 256u) seg = 256u;
     if (seg > STREAM_SEG_MAX) seg = STREAM_SEG_MAX;
     return (uint32_t)(seg & ~(size_t)63u);
+}
+
+/* How a one-stream call ends, compressing or decompressing: a failed one (rc) gives 0 bytes, says so on stderr (host buffers: the
+ * reference's calls have no other way) and leaves nothing of its own in flight; the thread's staging is trimmed to what it may keep. */
+static size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status)
+{
+    staging_t *st = staging_get();
+    if (rc != LZS_OK) {
+        if (!dev) fprintf(stderr, "liblzs: %s failed: %s\n", who, tls_error);
+        if (st && st->stream) lzs_hip_stream_sync(st->stream);
+    }
+    if (st) staging_trim(st);
+    if (status) *status = rc;
+    return rc != LZS_OK ? 0 : result;
 }
 
 /* in/out on the host (dev == 0: staged through this thread's device buffers) or on the device */
@@ -87,8 +100,7 @@ LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t 
     bitat = nbits + nseg; entry = (uint32_t *)(bitat + nseg); exitp = entry + nseg; openi = exitp + nseg;
     dirty = (uint8_t *)(openi + 2 * (size_t)nseg);
 
-#define HIP_TRY(call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto failed; } } while (0)
-    if (!st->stream) HIP_TRY(lzs_hip_stream_create(&st->stream), "hipStreamCreate");
+    if (!st->stream) HIP_TRY_OR(failed, lzs_hip_stream_create(&st->stream), "hipStreamCreate");
     void *stream = st->stream;
     /* device arrays in one allocation: bit_at, nbits (8 B each), entry, exit, open info (4 + 4 + 8 B), dirty */
     const size_t aux_bytes = (size_t)nseg * (8 + 8 + 4 + 4 + 8 + 1) + 64;
@@ -111,25 +123,25 @@ LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t 
     double t0 = debug ? now_ms() : 0, t1;
     if (!dev) {
         const size_t pre = pc ? pc->prefix_len : 0;
-        if (pre) HIP_TRY(lzs_hip_h2d(d_in, pc->prefix, pre, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
+        if (pre) HIP_TRY_OR(failed, lzs_hip_h2d(d_in, pc->prefix, pre, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
     }
     /* (a caller's device buffer is cleared only as far as it was promised: LZS_COMPRESSED_MAX(n) + 1024) */
-    HIP_TRY(lzs_hip_memset(d_out, 0, dev && worst + 1024 > cap ? cap : worst + 1024, stream), "hipMemset");
+    HIP_TRY_OR(failed, lzs_hip_memset(d_out, 0, dev && worst + 1024 > cap ? cap : worst + 1024, stream), "hipMemset");
     if (debug) { lzs_hip_stream_sync(stream); t1 = now_ms(); fprintf(stderr, "liblzs stream: %zu B, %u segments; H2D + memset %.2f ms\n", n, nseg, t1 - t0); t0 = t1; }
     uint32_t c_first = 0, ext_now = 0;
     uint64_t total = 0;
     if (pc) {
         c_first = pc->c0;
         total = pc->bit0;
-        if (pc->bit0) HIP_TRY(lzs_hip_h2d(d_out, &pc->first, 1, stream), "hipMemcpy H2D");
+        if (pc->bit0) HIP_TRY_OR(failed, lzs_hip_h2d(d_out, &pc->first, 1, stream), "hipMemcpy H2D");
         if (pc->ext_off) {
             /* the piece begins inside a long match: its length nibbles first (d_exit as scratch) */
             uint32_t res[4];
             /* (pc->stop: the data is known to end at n -- the run is closed like in a last piece, only the marker waits) */
-            HIP_TRY(lzs_hip_launch_extend_resume(d_out, pc->bit0, d_in, (uint32_t)n, pc->c0, pc->ext_off, pc->last || pc->stop, d_exit, stream), who);
-            HIP_TRY(lzs_hip_d2h(res, d_exit, sizeof(res), stream), "hipMemcpy D2H");
-            HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+            HIP_TRY_OR(failed, lzs_hip_launch_extend_resume(d_out, pc->bit0, d_in, (uint32_t)n, pc->c0, pc->ext_off, pc->last || pc->stop, d_exit, stream), who);
+            HIP_TRY_OR(failed, lzs_hip_d2h(res, d_exit, sizeof(res), stream), "hipMemcpy D2H");
+            HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
             c_first = res[0];
             ext_now = res[1] ? pc->ext_off : 0;
             total += ((uint64_t)res[3] << 32) | res[2];
@@ -141,12 +153,12 @@ LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t 
     }
     /* (a match still open after the nibbles covers all the data there is: no tokens in this piece) */
     for (uint32_t round = 0, ndirty = ext_now ? 0 : nseg; ndirty; round++) {
-        HIP_TRY(lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_launch_compress_segments(d_slots, slot_stride, d_in, (uint32_t)n, STREAM_SEG, nseg,
+        HIP_TRY_OR(failed, lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_launch_compress_segments(d_slots, slot_stride, d_in, (uint32_t)n, STREAM_SEG, nseg,
                                                  d_entry, d_dirty, d_exit, d_nbits, NULL, NULL, lim, pc ? d_open : NULL, stream), who);
-        HIP_TRY(lzs_hip_d2h(exitp, d_exit, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        HIP_TRY_OR(failed, lzs_hip_d2h(exitp, d_exit, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
         /* a segment is entered where the one before stopped (its own start for segment 0) */
         const uint32_t was = ndirty;
         ndirty = 0;
@@ -158,9 +170,9 @@ LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t 
         if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs stream: round %u compressed %u segments in %.2f ms; %u to redo\n", round, was, t1 - t0, ndirty); t0 = t1; }
     }
     if (!ext_now) {
-        HIP_TRY(lzs_hip_d2h(nbits, d_nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy D2H");
-        if (pc) HIP_TRY(lzs_hip_d2h(openi, d_open, sizeof(uint32_t) * 2 * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        HIP_TRY_OR(failed, lzs_hip_d2h(nbits, d_nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy D2H");
+        if (pc) HIP_TRY_OR(failed, lzs_hip_d2h(openi, d_open, sizeof(uint32_t) * 2 * nseg, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
     }
     if (pc) {
         pc->c_exit = ext_now ? c_first : exitp[nseg - 1];
@@ -179,43 +191,35 @@ LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t 
             const uint32_t off = openi[2 * (k - 1)], start = openi[2 * (k - 1) + 1];
             const uint32_t rest = ((uint32_t)n - start - 8u) % 15u;
             nbits[k - 1] -= 4;
-            HIP_TRY(lzs_hip_h2d(d_nbits, nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
+            HIP_TRY_OR(failed, lzs_hip_h2d(d_nbits, nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
             pc->c_exit = (uint32_t)n - rest;
             pc->ext_exit = off;
         }
     }
     for (uint32_t k = 0; k < nseg; k++) { bitat[k] = total; total += nbits[k]; }
     if (pc) pc->nbits = total;
-    HIP_TRY(lzs_hip_h2d(d_bitat, bitat, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
+    HIP_TRY_OR(failed, lzs_hip_h2d(d_bitat, bitat, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
     if (!ext_now)
-        HIP_TRY(lzs_hip_launch_stitch_segments(d_out, d_slots, slot_stride, d_bitat, d_nbits, nseg, end_marker, stream), who);
+        HIP_TRY_OR(failed, lzs_hip_launch_stitch_segments(d_out, d_slots, slot_stride, d_bitat, d_nbits, nseg, end_marker, stream), who);
     /* segments whose bits did not fit their slot (a match running on for more than ~120 KB past
      * the segment): once more, ORed straight into place */
     uint32_t nbig = 0;
     for (uint32_t k = 0; k < nseg; k++) { dirty[k] = nbits[k] > 8u * (uint64_t)slot_stride; nbig += dirty[k]; }
     if (nbig) {
-        HIP_TRY(lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_launch_compress_segments(d_slots, slot_stride, d_in, (uint32_t)n, STREAM_SEG, nseg,
+        HIP_TRY_OR(failed, lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_launch_compress_segments(d_slots, slot_stride, d_in, (uint32_t)n, STREAM_SEG, nseg,
                                                  d_entry, d_dirty, d_exit, d_nbits, d_out, d_bitat, lim, NULL, stream), who);
     }
     if (debug) { lzs_hip_stream_sync(stream); t1 = now_ms(); fprintf(stderr, "liblzs stream: stitch %.2f ms\n", t1 - t0); t0 = t1; }
     result = end_marker ? (size_t)((total + 9 + 7) / 8)        /* end marker, padded to a byte */
                         : (size_t)((total + 7) / 8);            /* a piece: the last byte may be partial */
     if (result > cap) result = cap;                            /* cut at the capacity, prefix unchanged */
-    if (!dev) HIP_TRY(lzs_hip_d2h(out, d_out, result, stream), "hipMemcpy D2H");
-    HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-#undef HIP_TRY
-    goto done;
+    if (!dev) HIP_TRY_OR(failed, lzs_hip_d2h(out, d_out, result, stream), "hipMemcpy D2H");
+    HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+    return stream_call_ends(result, LZS_OK, dev, who, status);
 
 failed:
-    result = 0;
-    if (rc == LZS_OK) rc = LZS_E_HIP;
-    if (!dev) fprintf(stderr, "liblzs: %s failed: %s\n", who, tls_error);
-    { staging_t *s2 = staging_get(); if (s2 && s2->stream) lzs_hip_stream_sync(s2->stream); }
-done:
-    { staging_t *s2 = staging_get(); if (s2) staging_trim(s2); }
-    if (status) *status = rc;
-    return result;
+    return stream_call_ends(0, rc == LZS_OK ? LZS_E_HIP : rc, dev, who, status);
 }
 
 LZS_HIDDEN size_t stream_compress(uint8_t *out, size_t cap, const uint8_t *in, size_t n, int dev, int *status)
@@ -254,6 +258,183 @@ static uint32_t stream_dec_seg(size_t n)
     return (uint32_t)(seg & ~(size_t)63u);
 }
 
+/* The segments of one stream, or of all the blocks of a batch, as SCAN, DECODE and RESOLVE see them.  One stream needs no
+ * range tables -- segment k is bytes [k seg, (k + 1) seg) of it -- and only its segment 0 is a first segment: one entered in
+ * a state that is given, not taken over from the segment before.  A batch says for every segment where it starts, where its
+ * block's stream ends, where its block's output begins and must end, and whether it is its block's first. */
+typedef struct {
+    const char *label;              /* "stream decode" or "batch decode": the LZS_STREAM_DEBUG lines */
+    size_t   nblocks;               /* 0: one stream */
+    uint32_t seg, nseg;
+    uint32_t *seen, *entry, *exits, *count, *start;      /* host side; exits and count lie one behind the other */
+    uint32_t *base, *end, *floor_, *limit;               /* the range tables, or NULL */
+    uint8_t  *dirty, *ones, *first;                      /* (first: or NULL) */
+    /* device side, in this order; then two counters, dirty, ones */
+    uint32_t *d_entry, *d_exit, *d_count, *d_start, *d_base, *d_end, *d_floor, *d_limit, *d_counters;
+    uint8_t  *d_dirty, *d_ones;
+} seg_table_t;
+
+/* (t->nseg is set; host: 5 words and 2 bytes a segment, with range tables 9 and 3; device: 4 words and 2 bytes, or 8 and 2, and 8 bytes) */
+static void segtab_lay_out(seg_table_t *t, uint32_t *h, uint32_t *d, int ranges)
+{
+    const size_t n = t->nseg;
+    t->seen = h; t->entry = h + n; t->exits = h + 2 * n; t->count = h + 3 * n; t->start = h + 4 * n; h += 5 * n;
+    t->d_entry = d; t->d_exit = d + n; t->d_count = d + 2 * n; t->d_start = d + 3 * n; d += 4 * n;
+    if (ranges) {
+        t->base = h; t->end = h + n; t->floor_ = h + 2 * n; t->limit = h + 3 * n; h += 4 * n;
+        t->d_base = d; t->d_end = d + n; t->d_floor = d + 2 * n; t->d_limit = d + 3 * n; d += 4 * n;
+    }
+    t->dirty = (uint8_t *)h; t->ones = t->dirty + n; t->first = ranges ? t->ones + n : NULL;
+    t->d_counters = d; t->d_dirty = (uint8_t *)(d + 2); t->d_ones = t->d_dirty + n;      /* counters: [0] bytes with an origin, [1] left open */
+}
+
+/* After a SCAN round: every segment is to be entered in the state in which the one before it left (a first segment in its
+ * own), and those for which that is news are walked again.  Host code only.  Returns how many are dirty now; *host_made:
+ * some exits / counts were worked out here, not on the device. */
+static uint32_t settle_entries(seg_table_t *t, int use_ones, int *host_made)
+{
+    const uint32_t seg = t->seg;
+    uint32_t *entry = t->entry, *exits = t->exits, *count = t->count, *seen = t->seen;
+    uint32_t ndirty = 0;
+    int ended = 0, settled = 1;     /* settled: every segment of this stream before k has been walked from its final entry */
+    *host_made = 0;
+    for (uint32_t k = 0; k < t->nseg; k++) {
+        if (t->dirty[k]) seen[k] = entry[k];                    /* exits[k], count[k] belong to this entry */
+        t->dirty[k] = 0;
+        if (t->first ? t->first[k] : k == 0) { ended = 0; settled = 1; continue; }
+        uint32_t want = exits[k - 1];
+        if (want & LZS_SEG_STOP) {
+            /* end marker or end of input before k -- believed only from a settled walk: one that
+             * was entered at a guessed bit reads end markers into the data now and then */
+            if (settled) ended = 1; else want = entry[k];
+        }
+        if (ended) want = LZS_SEG_STOP;
+        if (want != entry[k]) settled = 0;
+        entry[k] = want;
+        /* a segment behind the (current) end of the stream keeps what it reported for its last
+         * entry: the end may turn out to be a misread of a walk that had not fallen in step */
+        if (ended || want == seen[k]) continue;
+        if (use_ones && ((want >> 8) & 1u) && (t->ones[k] == 2 || (t->ones[k] && (want & 3u) == 0))) {
+            /* all 0xFF inside a running extension: nothing but nibbles of 15, one every 4 bits
+             * from the cursor on (which is up to 20 bits in if the match token itself straddles
+             * the border) for as long as they start inside the segment -- provided the last of
+             * them is all ones too, which reaches up to 3 bits into the next segment unless the
+             * cursor is a multiple of 4.  No need to walk it then. */
+            const uint32_t r = want & 0xFFu;
+            const uint32_t nibbles = (seg * 8u - r + 3u) / 4u;
+            exits[k] = (want & ~0xFFu) | (r + 4u * nibbles - seg * 8u);
+            count[k] = 15u * nibbles;
+            seen[k] = want;
+            *host_made = 1;
+            continue;
+        }
+        t->dirty[k] = 1;
+        ndirty++;
+    }
+    return ndirty;
+}
+
+/* The SCAN rounds: every segment entered at its first bit in the normal state (segment 0 of one stream: in `entry0`), then
+ * those whose predecessor left in another state again, until all agree.  `n`: the stream's length (0 with range tables),
+ * `in_extent`: the readable bytes at d_in, `d_marks`: what full walks leave for repeated ones.  LZS_OK or the error reported. */
+static int scan_rounds(seg_table_t *t, void *stream, const char *who, const void *d_in, uint32_t n, uint32_t in_extent,
+                       uint32_t entry0, int concat, uint32_t *d_marks, double *t0)
+{
+    const lzs_env_t env = *lzs_env();
+    const uint32_t nseg = t->nseg;
+    uint32_t *again = NULL;
+    int e = 0, rc = LZS_OK;
+    for (uint32_t k = 0; k < nseg; k++) { t->entry[k] = 0; t->dirty[k] = 1; t->seen[k] = 0xFFFFFFFFu; }
+    t->entry[0] = entry0;
+    for (uint32_t round = 0, ndirty = nseg; ndirty; round++) {
+        HIP_TRY_OR(done, lzs_hip_h2d(t->d_entry, t->entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(done, lzs_hip_h2d(t->d_dirty, t->dirty, nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(done, lzs_hip_launch_scan_stream(d_in, n, nseg, t->d_entry, t->d_dirty, t->d_exit, t->d_count, round == 0 ? t->d_ones : NULL,
+                                                    d_marks, round != 0 && !env.no_marks, t->seg, concat, t->d_base, t->d_end, in_extent, stream), who);
+        /* (exits and count lie one behind the other on both sides: one copy) */
+        HIP_TRY_OR(done, lzs_hip_d2h(t->exits, t->d_exit, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
+        if (round == 0) HIP_TRY_OR(done, lzs_hip_d2h(t->ones, t->d_ones, nseg, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        const uint32_t was = ndirty;
+        int host_made = 0;
+        ndirty = settle_entries(t, !env.no_ones, &host_made);
+        /* what the host worked out itself must survive the next round's copy back */
+        if (ndirty && host_made)
+            HIP_TRY_OR(done, lzs_hip_h2d(t->d_exit, t->exits, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        const double t1 = env.stream_debug ? now_ms() : 0;
+        if (env.stream_debug && t->nblocks) fprintf(stderr, "liblzs %s: %zu blocks, %u segments of %u; round %u in %.2f ms, %u to redo\n", t->label, t->nblocks, nseg, t->seg, round, t1 - *t0, ndirty);
+        else if (env.stream_debug) fprintf(stderr, "liblzs %s: round %u scanned %u of %u segments in %.2f ms; %u to redo\n", t->label, round, was, nseg, t1 - *t0, ndirty);
+        *t0 = t1;
+    }
+    if (env.verify_scan && (again = (uint32_t *)malloc(2 * sizeof(uint32_t) * nseg)) != NULL) {
+        /* development check: every segment walked in full from its final entry must report what
+         * the rounds arrived at (merged walks and the all-0xFF shortcut included) */
+        memset(t->dirty, 1, nseg);
+        HIP_TRY_OR(done, lzs_hip_h2d(t->d_entry, t->entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(done, lzs_hip_h2d(t->d_dirty, t->dirty, nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(done, lzs_hip_launch_scan_stream(d_in, n, nseg, t->d_entry, t->d_dirty, t->d_exit, t->d_count, NULL, NULL, 0, t->seg, concat,
+                                                    t->d_base, t->d_end, in_extent, stream), who);
+        HIP_TRY_OR(done, lzs_hip_d2h(again, t->d_exit, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        for (uint32_t k = 0; k < nseg; k++) {
+            if (t->entry[k] & LZS_SEG_STOP) continue;
+            if (again[k] != t->exits[k] || again[nseg + k] != t->count[k])
+                fprintf(stderr, "liblzs verify: segment %u entry %08x: rounds say exit %08x count %u, a full walk says %08x %u (all-ones %u)\n",
+                        k, t->entry[k], t->exits[k], t->count[k], again[k], again[nseg + k], t->ones[k]);
+        }
+    }
+done:
+    free(again);
+    return rc;
+}
+
+/* RESOLVE for one stream: `left` bytes of d_out[0, total) still carry an origin.  All origins lie in the 2047 bytes in front of
+ * a segment start (the tails).  So: (1) a workgroup per chunk of consecutive segments settles their tails in order, up to
+ * copies of bytes in front of the chunk; (2) rounds of pointer jumping on the tails in front of the chunks alone; (3) one pass
+ * over everything.  (3) alone, repeated, does the job too: (1) and (2) are shortcuts, not conditions. */
+static int resolve_origins(const seg_table_t *t, uint32_t ndec, void *stream, const char *who, void *d_out, uint32_t *d_origin,
+                           uint32_t total, uint32_t left, double *t0)
+{
+    const lzs_env_t env = *lzs_env();
+    const int debug = env.stream_debug;
+    uint32_t *d_left = t->d_counters + 1;
+    int e = 0, rc = LZS_OK;
+    double t1;
+    const int aligned = ((uintptr_t)d_out & 3u) == 0 && ((uintptr_t)d_origin & 15u) == 0;
+    int tails = left && ndec > 1 && aligned && !env.no_tails;
+    const int had_tails = tails;
+    uint32_t stride = 1, round = 1;
+    if (tails && ndec >= 64 && !env.no_chunks) {
+        stride = (ndec + 2047u) / 2048u;                    /* <= 2048 workgroups: all resident at once */
+        if (stride < 16u) stride = 16u;
+        HIP_TRY_OR(failed, lzs_hip_launch_resolve_chunks(d_out, d_origin, total, t->d_start, ndec, stride, round++, stream), who);
+        if (debug) { HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize"); t1 = now_ms(); fprintf(stderr, "liblzs %s: tails by chunks of %u segments in %.2f ms\n", t->label, stride, t1 - *t0); *t0 = t1; }
+    }
+    for (; left && round < 250; round++) {
+        HIP_TRY_OR(failed, lzs_hip_memset(d_left, 0, 4, stream), "hipMemset");
+        if (tails) {
+            /* three rounds to a look at the counter: a round on the tails is 30 - 130 us, the look costs as much */
+            HIP_TRY_OR(failed, lzs_hip_launch_resolve_tails(d_out, d_origin, total, t->d_start, ndec, stride, round, d_left, stream), who);
+            for (int more = 0; more < 2; more++) {
+                round++;
+                HIP_TRY_OR(failed, lzs_hip_memset(d_left, 0, 4, stream), "hipMemset");
+                HIP_TRY_OR(failed, lzs_hip_launch_resolve_tails(d_out, d_origin, total, t->d_start, ndec, stride, round, d_left, stream), who);
+            }
+        } else
+            HIP_TRY_OR(failed, lzs_hip_launch_resolve_stream(d_out, d_origin, total, round, d_left, had_tails, stream), who);
+        HIP_TRY_OR(failed, lzs_hip_d2h(&left, d_left, 4, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs %s: resolve round %u (%s, stride %u) in %.2f ms, %u left\n", t->label, round, tails ? "tails" : "all", stride, t1 - *t0, left); *t0 = t1; }
+        if (tails && !left) {                               /* the tails in front of the chunks are final: now everything */
+            tails = 0;                                      /* else -- a tail byte is one jump from its value, any other */
+            left = 1;                                       /* byte two (the pass stores no marks on what it finishes, so */
+        }                                                   /* a tail byte still shows its origin to whoever comes by) */
+    }
+    if (left) return fail(LZS_E_HIP, "%s: origins did not resolve", who);
+failed:
+    return rc;
+}
+
 /* lzs_decompress() of one long stream by many wavefronts: see lzs_scan_stream_kernel.  Returns
  * SIZE_MAX if this path does not apply (output of 4 GiB or more) and the caller should decode
  * with one wavefront. */
@@ -268,204 +449,73 @@ LZS_HIDDEN size_t stream_decompress(uint8_t *out, size_t cap, const uint8_t *in,
                                 dec_piece_t *dp)
 {
     const char *who = dp ? "lzs_decompress_incremental" : dev ? "lzs_decompress_stream_device" : concat ? "lzs_decompress_concat" : "lzs_decompress";
-    const uint32_t seg = stream_dec_seg(n);
-    const uint32_t nseg = (uint32_t)((n + seg - 1) / seg);
-    size_t result = 0;
+    seg_table_t t = { .label = "stream decode", .seg = stream_dec_seg(n) };
+    const uint32_t nseg = t.nseg = (uint32_t)((n + t.seg - 1) / t.seg);
     int e = 0, rc = LZS_OK;
     void *d_in = NULL, *d_out = NULL, *d_aux = NULL, *d_origin = NULL, *d_marks = NULL;
-    uint32_t *entry = NULL, *exits = NULL, *count = NULL, *start = NULL;
-    uint8_t *dirty = NULL, *ones = NULL;
-    uint32_t *seen = NULL;
     tls_error[0] = 0;
+    /* ---- set-up: the stream on the device, the segment table (the host side in pinned memory: it travels every round) */
     if (require_device() != LZS_OK) goto failed;
     staging_t *st = staging_get();
     if (!st) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
-    /* the tables that travel every round, in pinned memory */
-    seen = (uint32_t *)staging_host_tables(st, ((size_t)nseg + 16u) * (5u * 4u + 2u));
-    if (!seen) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
-    entry = seen + nseg; exits = entry + nseg; count = exits + nseg; start = count + nseg;
-    dirty = (uint8_t *)(start + nseg); ones = dirty + nseg;
-
-#define HIP_TRY(call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto failed; } } while (0)
-    if (!st->stream) HIP_TRY(lzs_hip_stream_create(&st->stream), "hipStreamCreate");
+    void *tables = staging_host_tables(st, ((size_t)nseg + 16u) * (5u * 4u + 2u));
+    if (!tables) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
+    if (!st->stream) HIP_TRY_OR(failed, lzs_hip_stream_create(&st->stream), "hipStreamCreate");
     void *stream = st->stream;
-    const size_t aux_bytes = (size_t)nseg * (4 + 4 + 4 + 4 + 1 + 1) + 128;
     if (dev) d_in = (void *)in; else e = staging_reserve(st, BUF_IN, n + 64, &d_in);
-    if (!e) e = staging_reserve(st, BUF_AUX, aux_bytes, &d_aux);
+    if (!e) e = staging_reserve(st, BUF_AUX, (size_t)nseg * (4 * 4 + 2) + 128, &d_aux);
     if (!e) e = staging_reserve(st, BUF_MARKS, (size_t)nseg * LZS_SCAN_MARK_WORDS * 4u, &d_marks);
     if (e) { fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
-    uint32_t *d_entry = (uint32_t *)d_aux;
-    uint32_t *d_exit = d_entry + nseg;
-    uint32_t *d_count = d_exit + nseg;
-    uint32_t *d_start = d_count + nseg;
-    uint32_t *d_counters = d_start + nseg;                     /* [0] bytes with an origin, [1] left open */
-    uint8_t *d_dirty = (uint8_t *)(d_counters + 2);
-    uint8_t *d_ones = d_dirty + nseg;
-
+    segtab_lay_out(&t, (uint32_t *)tables, (uint32_t *)d_aux, 0);
     const int debug = lzs_env()->stream_debug;
     double t0 = debug ? now_ms() : 0, t1;
     if (!dev) {
         const size_t pre = dp ? dp->prefix_len : 0;
-        if (pre) HIP_TRY(lzs_hip_h2d(d_in, dp->prefix, pre, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
+        if (pre) HIP_TRY_OR(failed, lzs_hip_h2d(d_in, dp->prefix, pre, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
     }
-    /* SCAN rounds: every segment entered at its first bit in the normal state, then corrected */
-    for (uint32_t k = 0; k < nseg; k++) { entry[k] = 0; dirty[k] = 1; seen[k] = 0xFFFFFFFFu; }
-    if (dp) entry[0] = dp->entry0;
-    for (uint32_t round = 0, ndirty = nseg; ndirty; round++) {
-        HIP_TRY(lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_launch_scan_stream(d_in, (uint32_t)n, nseg, d_entry, d_dirty, d_exit, d_count,
-                                           round == 0 ? d_ones : NULL, (uint32_t *)d_marks, round != 0 && !lzs_env()->no_marks, seg, concat, NULL, NULL, (uint32_t)n, stream), who);
-        /* (exits and count lie one behind the other on both sides: one copy) */
-        HIP_TRY(lzs_hip_d2h(exits, d_exit, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        if (round == 0) HIP_TRY(lzs_hip_d2h(ones, d_ones, nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-        const uint32_t was = ndirty;
-        ndirty = 0;
-        if (dirty[0]) seen[0] = entry[0];                       /* exits[k], count[k] belong to this entry */
-        dirty[0] = 0;
-        int ended = 0;
-        int settled = 1;            /* every segment before k has been walked from its final entry */
-        int host_made = 0;          /* exits / counts worked out here, not on the device */
-        for (uint32_t k = 1; k < nseg; k++) {
-            if (dirty[k]) seen[k] = entry[k];
-            uint32_t want = exits[k - 1];
-            if (want & LZS_SEG_STOP) {
-                /* end marker or end of input before k -- believed only from a settled walk: one that
-                 * was entered at a guessed bit reads end markers into the data now and then */
-                if (settled) ended = 1; else want = entry[k];
-            }
-            if (ended) want = LZS_SEG_STOP;
-            if (want != entry[k]) settled = 0;
-            entry[k] = want;
-            dirty[k] = 0;
-            /* a segment behind the (current) end of the stream keeps what it reported for its last
-             * entry: the end may turn out to be a misread of a walk that had not fallen in step */
-            if (ended || want == seen[k]) continue;
-            if (((want >> 8) & 1u) && (ones[k] == 2 || (ones[k] && (want & 3u) == 0)) && !lzs_env()->no_ones) {
-                /* all 0xFF inside a running extension: nothing but nibbles of 15, one every 4 bits
-                 * from the cursor on (which is up to 20 bits in if the match token itself straddles
-                 * the border) for as long as they start inside the segment -- provided the last of
-                 * them is all ones too, which reaches up to 3 bits into the next segment unless the
-                 * cursor is a multiple of 4.  No need to walk it then. */
-                const uint32_t r = want & 0xFFu;
-                const uint32_t nibbles = (seg * 8u - r + 3u) / 4u;
-                exits[k] = (want & ~0xFFu) | (r + 4u * nibbles - seg * 8u);
-                count[k] = 15u * nibbles;
-                seen[k] = want;
-                host_made = 1;
-                continue;
-            }
-            dirty[k] = 1;
-            ndirty++;
-        }
-        /* what the host worked out itself must survive the next round's copy back */
-        if (ndirty && host_made)
-            HIP_TRY(lzs_hip_h2d(d_exit, exits, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs stream decode: round %u scanned %u of %u segments in %.2f ms; %u to redo\n", round, was, nseg, t1 - t0, ndirty); t0 = t1; }
-    }
-    if (lzs_env()->verify_scan) {
-        /* development check: every segment walked in full from its final entry must report what
-         * the rounds arrived at (merged walks and the all-0xFF shortcut included) */
-        uint32_t *ex2 = (uint32_t *)malloc(sizeof(uint32_t) * nseg), *cn2 = (uint32_t *)malloc(sizeof(uint32_t) * nseg);
-        memset(dirty, 1, nseg);
-        HIP_TRY(lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_launch_scan_stream(d_in, (uint32_t)n, nseg, d_entry, d_dirty, d_exit, d_count, NULL, NULL, 0, seg, concat, NULL, NULL, (uint32_t)n, stream), who);
-        HIP_TRY(lzs_hip_d2h(ex2, d_exit, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_d2h(cn2, d_count, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-        for (uint32_t k = 0; k < nseg; k++) {
-            if (entry[k] & LZS_SEG_STOP) break;
-            if (ex2[k] != exits[k] || cn2[k] != count[k])
-                fprintf(stderr, "liblzs verify: segment %u entry %08x: rounds say exit %08x count %u, a full walk says %08x %u (all-ones %u)\n",
-                        k, entry[k], exits[k], count[k], ex2[k], cn2[k], ones[k]);
-        }
-        free(ex2); free(cn2);
-    }
+    /* ---- SCAN */
+    if ((rc = scan_rounds(&t, stream, who, d_in, (uint32_t)n, (uint32_t)n, dp ? dp->entry0 : 0u, concat, (uint32_t *)d_marks, &t0)) != LZS_OK) goto failed;
+    /* ---- placement: where every segment's output begins; how many segments a piece decodes, and in which state it goes on */
     uint64_t total = 0;
     uint32_t ndec = nseg;                                      /* segments to decode */
     const uint32_t before = dp ? dp->hist_len : 0;             /* bytes in front of out[0] that copies may reach */
     for (uint32_t k = 0; k < nseg; k++) {
-        if (dp && ((exits[k] & LZS_SEG_STOP) || (entry[k] & LZS_SEG_STOP) || total + count[k] > cap)) { ndec = k; break; }
-        start[k] = (uint32_t)total + before;
-        if (!(entry[k] & LZS_SEG_STOP)) total += count[k];
+        if (dp && ((t.exits[k] & LZS_SEG_STOP) || (t.entry[k] & LZS_SEG_STOP) || total + t.count[k] > cap)) { ndec = k; break; }
+        t.start[k] = (uint32_t)total + before;
+        if (!(t.entry[k] & LZS_SEG_STOP)) total += t.count[k];
         if (total >= 0xFFFFFF00ull - 0x100000ull) break;
     }
-    if (total >= 0xFFFFFF00ull - 0x100000ull) { result = SIZE_MAX; goto done; }   /* positions are 32-bit here */
-    if (dp) { dp->seg = seg; dp->segs_done = ndec; dp->next_entry = ndec < nseg ? entry[ndec] : exits[nseg - 1]; }
+    if (total >= 0xFFFFFF00ull - 0x100000ull) return stream_call_ends(SIZE_MAX, LZS_OK, dev, who, status);   /* positions are 32-bit here */
+    if (dp) { dp->seg = t.seg; dp->segs_done = ndec; dp->next_entry = ndec < nseg ? t.entry[ndec] : t.exits[nseg - 1]; }
     const uint32_t produce = (uint32_t)(total < cap ? total : cap);
     if (produce) {
+        /* ---- DECODE, behind the history (final bytes: origin "clean" = all ones) */
         if (dev) d_out = out; else e = staging_reserve(st, BUF_OUT, (size_t)before + produce + 64, &d_out);
         if (!e) e = staging_reserve(st, BUF_KEEP, 4 * ((size_t)before + produce) + 64, &d_origin);
         if (e) { fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
-        if (before) {                                          /* the history: final bytes (origin "clean" = all ones) */
-            HIP_TRY(lzs_hip_h2d(d_out, dp->hist, before, stream), "hipMemcpy H2D");
-            HIP_TRY(lzs_hip_memset(d_origin, 0xFF, 4 * (size_t)before, stream), "hipMemset");
+        if (before) {
+            HIP_TRY_OR(failed, lzs_hip_h2d(d_out, dp->hist, before, stream), "hipMemcpy H2D");
+            HIP_TRY_OR(failed, lzs_hip_memset(d_origin, 0xFF, 4 * (size_t)before, stream), "hipMemset");
         }
-        HIP_TRY(lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d(d_start, start, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_memset(d_counters, 0, 8, stream), "hipMemset");
-        HIP_TRY(lzs_hip_launch_decode_stream(d_out, before + produce, (uint32_t *)d_origin, d_counters, d_in, (uint32_t)n, (uint32_t)n,
-                                             ndec, d_entry, d_start, seg, concat, NULL, NULL, NULL, NULL, stream), who);
+        HIP_TRY_OR(failed, lzs_hip_h2d(t.d_entry, t.entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_h2d(t.d_start, t.start, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(failed, lzs_hip_memset(t.d_counters, 0, 8, stream), "hipMemset");
+        HIP_TRY_OR(failed, lzs_hip_launch_decode_stream(d_out, before + produce, (uint32_t *)d_origin, t.d_counters, d_in, (uint32_t)n, (uint32_t)n,
+                                                        ndec, t.d_entry, t.d_start, t.seg, concat, NULL, NULL, NULL, NULL, stream), who);
         uint32_t open[2] = {0, 0};
-        HIP_TRY(lzs_hip_d2h(open, d_counters, 8, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        HIP_TRY_OR(failed, lzs_hip_d2h(open, t.d_counters, 8, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
         if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs stream decode: %u bytes decoded in %.2f ms, %u with an origin in another segment\n", produce, t1 - t0, open[0]); t0 = t1; }
-        uint32_t left = open[0];
-        /* All origins lie in the 2047 bytes in front of a segment start (the tails).  So: (1) a
-         * workgroup per chunk of consecutive segments settles their tails in order, up to copies
-         * of bytes in front of the chunk; (2) rounds of pointer jumping on the tails in front of
-         * the chunks alone; (3) one pass over everything.  (3) alone, repeated, does the job too:
-         * (1) and (2) are shortcuts, not conditions. */
-        const int aligned = ((uintptr_t)d_out & 3u) == 0 && ((uintptr_t)d_origin & 15u) == 0;
-        int tails = left && ndec > 1 && aligned && !lzs_env()->no_tails;
-        const int had_tails = tails;
-        uint32_t stride = 1, round = 1;
-        if (tails && ndec >= 64 && !lzs_env()->no_chunks) {
-            stride = (ndec + 2047u) / 2048u;                    /* <= 2048 workgroups: all resident at once */
-            if (stride < 16u) stride = 16u;
-            HIP_TRY(lzs_hip_launch_resolve_chunks(d_out, (uint32_t *)d_origin, before + produce, d_start, ndec, stride, round++, stream), who);
-            if (debug) { HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize"); t1 = now_ms(); fprintf(stderr, "liblzs stream decode: tails by chunks of %u segments in %.2f ms\n", stride, t1 - t0); t0 = t1; }
-        }
-        for (; left && round < 250; round++) {
-            HIP_TRY(lzs_hip_memset(d_counters + 1, 0, 4, stream), "hipMemset");
-            if (tails) {
-                /* three rounds to a look at the counter: a round on the tails is 30 - 130 us, the look costs as much */
-                HIP_TRY(lzs_hip_launch_resolve_tails(d_out, (uint32_t *)d_origin, before + produce, d_start, ndec, stride, round, d_counters + 1, stream), who);
-                for (int more = 0; more < 2; more++) {
-                    round++;
-                    HIP_TRY(lzs_hip_memset(d_counters + 1, 0, 4, stream), "hipMemset");
-                    HIP_TRY(lzs_hip_launch_resolve_tails(d_out, (uint32_t *)d_origin, before + produce, d_start, ndec, stride, round, d_counters + 1, stream), who);
-                }
-            } else
-                HIP_TRY(lzs_hip_launch_resolve_stream(d_out, (uint32_t *)d_origin, before + produce, round, d_counters + 1, had_tails, stream), who);
-            HIP_TRY(lzs_hip_d2h(&left, d_counters + 1, 4, stream), "hipMemcpy D2H");
-            HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-            if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs stream decode: resolve round %u (%s, stride %u) in %.2f ms, %u left\n", round, tails ? "tails" : "all", stride, t1 - t0, left); t0 = t1; }
-            if (tails && !left) {                               /* the tails in front of the chunks are final: now everything */
-                tails = 0;                                      /* else -- a tail byte is one jump from its value, any other */
-                left = 1;                                       /* byte two (the pass stores no marks on what it finishes, so */
-            }                                                   /* a tail byte still shows its origin to whoever comes by) */
-        }
-        if (left) { fail(LZS_E_HIP, "%s: origins did not resolve", who); goto failed; }
-        if (!dev) HIP_TRY(lzs_hip_d2h(out, (uint8_t *)d_out + before, produce, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        /* ---- RESOLVE, and out */
+        if ((rc = resolve_origins(&t, ndec, stream, who, d_out, (uint32_t *)d_origin, before + produce, open[0], &t0)) != LZS_OK) goto failed;
+        if (!dev) HIP_TRY_OR(failed, lzs_hip_d2h(out, (uint8_t *)d_out + before, produce, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
     }
-    result = produce;
-#undef HIP_TRY
-    goto done;
+    return stream_call_ends(produce, LZS_OK, dev, who, status);
 
 failed:
-    result = 0;
-    if (rc == LZS_OK) rc = LZS_E_HIP;
-    if (!dev) fprintf(stderr, "liblzs: %s failed: %s\n", who, tls_error);
-    { staging_t *s2 = staging_get(); if (s2 && s2->stream) lzs_hip_stream_sync(s2->stream); }
-done:
-    { staging_t *s2 = staging_get(); if (s2) staging_trim(s2); }
-    if (status) *status = rc;
-    return result;
+    return stream_call_ends(0, rc == LZS_OK ? LZS_E_HIP : rc, dev, who, status);
 }
 
 /* A batch of blocks decompressed like one long stream: every block is cut into segments of its
@@ -479,125 +529,72 @@ LZS_HIDDEN int batch_decompress_segments(staging_t *st, void *stream, const char
 {
     int e = 0, rc = LZS_OK;
     size_t total_in = 0;
-    for (size_t b = 0; b < nblocks; b++) total_in += in_len_each ? in_len_each[b] : in_len;
-    const uint32_t seg = stream_dec_seg(total_in / 4);        /* (smaller than for one stream of that size: measured) */
     uint32_t in_extent = 0;                                    /* the readable bytes at d_in: the kernels' loads are bounded by it */
     for (size_t b = 0; b < nblocks; b++) {
-        const size_t to = b * d_in_stride + (in_len_each ? in_len_each[b] : in_len);
-        if (to > in_extent) in_extent = (uint32_t)to;
+        const size_t len = in_len_each ? in_len_each[b] : in_len;
+        total_in += len;
+        if (b * d_in_stride + len > in_extent) in_extent = (uint32_t)(b * d_in_stride + len);
     }
-    uint32_t nseg = 0;
-    for (size_t b = 0; b < nblocks; b++) nseg += ((in_len_each ? in_len_each[b] : in_len) + seg - 1) / seg;
+    seg_table_t t = { .label = "batch decode", .nblocks = nblocks, .seg = stream_dec_seg(total_in / 4) };   /* (smaller than for one stream of that size: measured) */
+    const uint32_t seg = t.seg;
+    for (size_t b = 0; b < nblocks; b++) t.nseg += ((in_len_each ? in_len_each[b] : in_len) + seg - 1) / seg;
+    const uint32_t nseg = t.nseg;
     const uint32_t extent = (uint32_t)(nblocks * d_out_stride);
     memset(out_len, 0, sizeof(uint32_t) * nblocks);
     if (nseg == 0) return LZS_OK;
-    /* host tables: 12 words and 3 bytes per segment */
-    uint32_t *tab = (uint32_t *)malloc((size_t)nseg * (12 * 4 + 4));
-    if (!tab) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
-    uint32_t *entry = tab, *exits = entry + nseg, *count = exits + nseg, *start = count + nseg;
-    uint32_t *base = start + nseg, *end = base + nseg, *floor_ = end + nseg, *limit = floor_ + nseg;
-    uint32_t *seen = limit + nseg, *blk = seen + nseg, *spare = blk + nseg;   /* (spare: two unused rows) */
-    uint8_t *dirty = (uint8_t *)(spare + 2 * (size_t)nseg), *ones = dirty + nseg, *first = ones + nseg;
+    /* host tables: every segment's block, then the segment table -- 10 words and 3 bytes a segment */
+    uint32_t *blk = (uint32_t *)malloc((size_t)nseg * (10 * 4 + 3));
+    if (!blk) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
     void *d_aux = NULL, *d_marks = NULL, *d_origin = NULL;
-#define HIP_TRY(call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto done; } } while (0)
     e = staging_reserve(st, BUF_AUX, (size_t)nseg * (8 * 4 + 2) + 128, &d_aux);
     if (!e) e = staging_reserve(st, BUF_MARKS, (size_t)nseg * LZS_SCAN_MARK_WORDS * 4u, &d_marks);
     if (!e) e = staging_reserve(st, BUF_KEEP, 4 * (size_t)extent + 64, &d_origin);
     if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto done; }
-    uint32_t *d_entry = (uint32_t *)d_aux, *d_exit = d_entry + nseg, *d_count = d_exit + nseg, *d_start = d_count + nseg;
-    uint32_t *d_base = d_start + nseg, *d_end = d_base + nseg, *d_floor = d_end + nseg, *d_limit = d_floor + nseg;
-    uint32_t *d_counters = d_limit + nseg;
-    uint8_t *d_dirty = (uint8_t *)(d_counters + 2), *d_ones = d_dirty + nseg;
-    {
-        uint32_t k = 0;
-        for (size_t b = 0; b < nblocks; b++) {
-            const uint32_t len = in_len_each ? in_len_each[b] : in_len;
-            for (uint32_t at = 0; at < len; at += seg, k++) {
-                base[k] = (uint32_t)(b * d_in_stride) + at;
-                end[k] = (uint32_t)(b * d_in_stride) + len;
-                floor_[k] = (uint32_t)(b * d_out_stride);
-                limit[k] = floor_[k] + cap32;
-                blk[k] = (uint32_t)b;
-                first[k] = at == 0;
-                entry[k] = 0; dirty[k] = 1; seen[k] = 0xFFFFFFFFu;
-            }
+    segtab_lay_out(&t, blk + nseg, (uint32_t *)d_aux, 1);
+    for (size_t b = 0, k = 0; b < nblocks; b++) {
+        const uint32_t len = in_len_each ? in_len_each[b] : in_len;
+        for (uint32_t at = 0; at < len; at += seg, k++) {
+            t.base[k] = (uint32_t)(b * d_in_stride) + at;
+            t.end[k] = (uint32_t)(b * d_in_stride) + len;
+            t.floor_[k] = (uint32_t)(b * d_out_stride);
+            t.limit[k] = t.floor_[k] + cap32;
+            blk[k] = (uint32_t)b;
+            t.first[k] = at == 0;
         }
     }
     const int debug = lzs_env()->stream_debug;
     double t0 = debug ? now_ms() : 0, t1;
-    HIP_TRY(lzs_hip_h2d(d_base, base, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-    HIP_TRY(lzs_hip_h2d(d_end, end, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-    for (uint32_t round = 0, ndirty = nseg; ndirty; round++) {
-        HIP_TRY(lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_launch_scan_stream(d_in, 0, nseg, d_entry, d_dirty, d_exit, d_count, round == 0 ? d_ones : NULL,
-                                           (uint32_t *)d_marks, round != 0, seg, 0, d_base, d_end, in_extent, stream), who);
-        HIP_TRY(lzs_hip_d2h(exits, d_exit, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        if (round == 0) HIP_TRY(lzs_hip_d2h(ones, d_ones, nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_d2h(count, d_count, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-        for (uint32_t k = 0; k < nseg; k++) if (dirty[k]) seen[k] = entry[k];
-        ndirty = 0;
-        int ended = 0, settled = 1;
-        for (uint32_t k = 0; k < nseg; k++) {                  /* as in stream_decompress(), block by block */
-            dirty[k] = 0;
-            if (first[k]) { ended = 0; settled = 1; continue; }
-            uint32_t want = exits[k - 1];
-            if (want & LZS_SEG_STOP) { if (settled) ended = 1; else want = entry[k]; }
-            if (ended) want = LZS_SEG_STOP;
-            if (want != entry[k]) settled = 0;
-            entry[k] = want;
-            if (ended || want == seen[k]) continue;
-            if (((want >> 8) & 1u) && (ones[k] == 2 || (ones[k] && (want & 3u) == 0))) {
-                const uint32_t r = want & 0xFFu;
-                const uint32_t nibbles = (seg * 8u - r + 3u) / 4u;
-                exits[k] = (want & ~0xFFu) | (r + 4u * nibbles - seg * 8u);
-                count[k] = 15u * nibbles;
-                seen[k] = want;
-                continue;
-            }
-            dirty[k] = 1;
-            ndirty++;
-        }
-        if (ndirty) {
-            HIP_TRY(lzs_hip_h2d(d_exit, exits, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-            HIP_TRY(lzs_hip_h2d(d_count, count, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        }
-        if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs batch decode: %zu blocks, %u segments of %u; round %u in %.2f ms, %u to redo\n", nblocks, nseg, seg, round, t1 - t0, ndirty); t0 = t1; }
+    HIP_TRY_OR(done, lzs_hip_h2d(t.d_base, t.base, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");      /* (and end, behind it) */
+    if ((rc = scan_rounds(&t, stream, who, d_in, 0, in_extent, 0, 0, (uint32_t *)d_marks, &t0)) != LZS_OK) goto done;
+    /* placement: every block's segments one behind the other from the block's slot on, cut at the capacity */
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < nseg; k++) {
+        if (t.first[k]) total = 0;
+        t.start[k] = t.floor_[k] + (uint32_t)(total < cap32 ? total : cap32);
+        if (!(t.entry[k] & LZS_SEG_STOP)) total += t.count[k];
+        out_len[blk[k]] = (uint32_t)(total < cap32 ? total : cap32);
     }
-    {
-        uint64_t total = 0;
-        for (uint32_t k = 0; k < nseg; k++) {
-            if (first[k]) total = 0;
-            start[k] = floor_[k] + (uint32_t)(total < cap32 ? total : cap32);
-            if (!(entry[k] & LZS_SEG_STOP)) total += count[k];
-            out_len[blk[k]] = (uint32_t)(total < cap32 ? total : cap32);
-        }
-    }
-    HIP_TRY(lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-    HIP_TRY(lzs_hip_h2d(d_start, start, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-    HIP_TRY(lzs_hip_h2d(d_floor, floor_, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-    HIP_TRY(lzs_hip_h2d(d_limit, limit, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-    HIP_TRY(lzs_hip_memset(d_counters, 0, 8, stream), "hipMemset");
-    HIP_TRY(lzs_hip_memset(d_origin, 0xFF, 4 * (size_t)extent, stream), "hipMemset");      /* everything "clean" */
-    HIP_TRY(lzs_hip_launch_decode_stream(d_out, extent, (uint32_t *)d_origin, d_counters, d_in, 0, in_extent, nseg, d_entry, d_start,
-                                         seg, 0, d_base, d_end, d_floor, d_limit, stream), who);
-    {
-        uint32_t open[2] = {0, 0};
-        HIP_TRY(lzs_hip_d2h(open, d_counters, 8, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-        if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs batch decode: tables + memset + decode in %.2f ms, %u bytes with an origin elsewhere\n", t1 - t0, open[0]); t0 = t1; }
-        /* origins never leave their block: one workgroup per block resolves them to the end */
-        HIP_TRY(lzs_hip_h2d(d_len, out_len, sizeof(uint32_t) * nblocks, stream), "hipMemcpy H2D");
-        if (open[0]) HIP_TRY(lzs_hip_launch_resolve_blocks(d_out, (uint32_t *)d_origin, d_out_stride, d_len, (uint32_t)nblocks, stream), who);
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-        if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs batch decode: resolve in %.2f ms\n", t1 - t0); t0 = t1; }
-    }
-#undef HIP_TRY
+    HIP_TRY_OR(done, lzs_hip_h2d(t.d_entry, t.entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+    HIP_TRY_OR(done, lzs_hip_h2d(t.d_start, t.start, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+    HIP_TRY_OR(done, lzs_hip_h2d(t.d_floor, t.floor_, 2 * sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");   /* (and limit, behind it) */
+    HIP_TRY_OR(done, lzs_hip_memset(t.d_counters, 0, 8, stream), "hipMemset");
+    HIP_TRY_OR(done, lzs_hip_memset(d_origin, 0xFF, 4 * (size_t)extent, stream), "hipMemset");      /* everything "clean" */
+    HIP_TRY_OR(done, lzs_hip_launch_decode_stream(d_out, extent, (uint32_t *)d_origin, t.d_counters, d_in, 0, in_extent, nseg, t.d_entry, t.d_start,
+                                                  seg, 0, t.d_base, t.d_end, t.d_floor, t.d_limit, stream), who);
+    uint32_t open[2] = {0, 0};
+    HIP_TRY_OR(done, lzs_hip_d2h(open, t.d_counters, 8, stream), "hipMemcpy D2H");
+    HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+    if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs batch decode: tables + memset + decode in %.2f ms, %u bytes with an origin elsewhere\n", t1 - t0, open[0]); t0 = t1; }
+    /* origins never leave their block: one workgroup per block resolves them to the end */
+    HIP_TRY_OR(done, lzs_hip_h2d(d_len, out_len, sizeof(uint32_t) * nblocks, stream), "hipMemcpy H2D");
+    if (open[0]) HIP_TRY_OR(done, lzs_hip_launch_resolve_blocks(d_out, (uint32_t *)d_origin, d_out_stride, d_len, (uint32_t)nblocks, stream), who);
+    HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+    if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs batch decode: resolve in %.2f ms\n", t1 - t0); t0 = t1; }
 done:
-    free(tab);
+    free(blk);
     return rc;
 }
+
 
 int lzs_decompress_stream_device(void *d_out, size_t out_cap, size_t *out_len, const void *d_in, size_t in_len)
 {
@@ -612,4 +609,3 @@ int lzs_decompress_stream_device(void *d_out, size_t out_cap, size_t *out_len, c
     *out_len = got;
     return rc;
 }
-

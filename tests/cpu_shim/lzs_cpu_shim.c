@@ -13,8 +13,9 @@
  *     with the kernels' contracts: fixed-stride slots, lengths cut at the capacity, nothing past a slot touched;
  *   * the segment launches of lzs_stream.c's compress side (segments, stitch, extend-resume) and the incremental
  *     decoder's launch (decode-resume) are restated here from the kernels' documented contracts, serially;
- *   * the many-wavefront decompression launches (scan / decode / resolve) return hipErrorNotSupported: the harness runs
- *     with LZS_ONE_WAVE=1, which keeps those calls on the one-wavefront route, as tools/README.md says.
+ *   * the many-wavefront decompression's SCAN and DECODE launches are restated the same way (san_driver's case "streamdec"
+ *     drives the host's scan rounds, settle rule and placement through them; the other cases run with LZS_ONE_WAVE=1);
+ *     decoded serially nothing is left to resolve, so the resolve launches return hipErrorNotSupported.
  * Nothing here is the product, nothing in the product links this.
  */
 #include <pthread.h>
@@ -117,9 +118,6 @@ int lzs_hip_launch_decompress(void *d_out, size_t out_stride, uint32_t out_cap, 
     }
     return launched();
 }
-int lzs_hip_launch_decompress_concat(void *a, size_t b, uint32_t c, uint32_t *d, const void *e, size_t f, const uint32_t *g, uint32_t h, uint32_t i, void *j)
-{ (void)a; (void)b; (void)c; (void)d; (void)e; (void)f; (void)g; (void)h; (void)i; (void)j; return E_NOT_SUPPORTED; }
-
 int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots, size_t slot_stride, const uint32_t *d_len, uint32_t nblocks, void *stream)
 {
     (void)stream;
@@ -321,13 +319,142 @@ int lzs_hip_launch_decode_resume(lzs_dec_resume_t *st, const void *d_in, uint32_
     return launched();
 }
 
-/* ---- the many-wavefront decompression: not modelled (LZS_ONE_WAVE=1 keeps the harness off it) */
-int lzs_hip_launch_scan_stream(const void *a, uint32_t b, uint32_t c, const uint32_t *d, const uint8_t *e, uint32_t *f, uint32_t *g, uint8_t *h,
-                               uint32_t *i, int j, uint32_t k, int l, const uint32_t *m, const uint32_t *n, uint32_t o, void *p)
-{ (void)a; (void)b; (void)c; (void)d; (void)e; (void)f; (void)g; (void)h; (void)i; (void)j; (void)k; (void)l; (void)m; (void)n; (void)o; (void)p; return E_NOT_SUPPORTED; }
-int lzs_hip_launch_decode_stream(void *a, uint32_t b, uint32_t *c, uint32_t *d, const void *e, uint32_t f, uint32_t g, uint32_t h, const uint32_t *i,
-                                 const uint32_t *j, uint32_t k, int l, const uint32_t *m, const uint32_t *n, const uint32_t *o, const uint32_t *p, void *q)
-{ (void)a; (void)b; (void)c; (void)d; (void)e; (void)f; (void)g; (void)h; (void)i; (void)j; (void)k; (void)l; (void)m; (void)n; (void)o; (void)p; (void)q; return E_NOT_SUPPORTED; }
+/* ---- the many-wavefront decompression (csrc/kernels/decompress_stream.inc): SCAN and DECODE restated serially, one segment
+ * after the other.  A segment is a token walk: from the state word `entry` (bits 0..7 the cursor in bits past the segment
+ * start, bit 8 an extension running, bits 9..19 its offset) for as long as tokens START inside the segment's `seg_bits`
+ * bits; the stream the segment belongs to ends at in[n] (a token may read on past the segment's end up to there).  It leaves
+ * in a state word of the same form, counted from the next segment's start -- or LZS_SEG_STOP if the stream ended: an end
+ * marker (unless `concat`: then on from the next whole byte), no bits left, a token that lacks some of its bits.  The offset
+ * is part of the state only while an extension runs.  With a sink the bytes are produced too: byte i of the segment goes to
+ * out[start + i] if that lies below `cap`, a copy from before out[floor] yields zeros, and the walk also stops once
+ * start + count reaches cap. */
+typedef struct { uint8_t *out; uint32_t *origin; uint32_t start, floor, cap; } seg_sink_t;
+static uint32_t peek_at(const uint8_t *in, uint64_t at, uint64_t end, unsigned w)   /* MSB first; bits past the end read as 0 */
+{
+    uint32_t v = 0;
+    for (unsigned i = 0; i < w; i++) v = (v << 1) | (at + i < end ? (in[(at + i) >> 3] >> (7u - ((at + i) & 7u))) & 1u : 0u);
+    return v;
+}
+static void seg_produce(const seg_sink_t *sink, uint32_t *count, int copy, uint32_t off_or_value, uint32_t len)
+{
+    for (uint32_t i = 0; i < len; i++, (*count)++) {
+        if (!sink) continue;
+        const uint64_t g = (uint64_t)sink->start + *count;
+        if (g >= sink->cap) continue;                               /* (counted, not stored: the walk stops before the next token) */
+        sink->out[g] = !copy ? (uint8_t)off_or_value : g >= (uint64_t)off_or_value + sink->floor ? sink->out[g - off_or_value] : 0;
+        if (sink->origin) sink->origin[g] = 0xFFFFFFFFu;            /* serial: every source is final, every byte "clean" */
+    }
+}
+static void segment_walk(const uint8_t *in, uint32_t n, uint32_t sbase, uint64_t seg_bits, uint32_t entry, int concat,
+                         uint32_t *exit_state, uint32_t *count_out, const seg_sink_t *sink)
+{
+    const uint64_t first = 8u * (uint64_t)sbase, end = 8u * (uint64_t)n;
+    uint64_t at = first + (entry & 0xFFu);
+    uint32_t count = 0, off = (entry >> 9) & 0x7FFu, state = LZS_SEG_STOP;
+    int extended = (int)((entry >> 8) & 1u);
+    while (at < end) {
+        if (at - first >= seg_bits) {                               /* the next token belongs to the next segment */
+            state = (uint32_t)(at - first - seg_bits) | ((uint32_t)extended << 8) | ((extended ? off : 0u) << 9);
+            break;
+        }
+        if (sink && (uint64_t)sink->start + count >= sink->cap) break;
+        const uint64_t have = end - at;
+        if (extended) {
+            if (have < 4) break;
+            const uint32_t e = peek_at(in, at, end, 4);
+            at += 4;
+            seg_produce(sink, &count, 1, off, e);
+            if (e != 15u) extended = 0;
+        } else if (peek_at(in, at, end, 1) == 0) {
+            if (have < 9) break;
+            seg_produce(sink, &count, 0, peek_at(in, at + 1, end, 8), 1);
+            at += 9;
+        } else {
+            const int is_short = (int)peek_at(in, at + 1, end, 1);
+            const unsigned used = is_short ? 9u : 13u;
+            if (have < used) break;
+            const uint32_t o = peek_at(in, at + 2, end, used - 2u);
+            if (o == 0) {
+                at += used;
+                if (!is_short) { off = 0; continue; }               /* long offset 0: 13 bits, no copy */
+                if (!concat) break;                                 /* end marker */
+                at += (end - at) & 7u;                              /* concatenated streams: on from the next whole byte */
+                continue;
+            }
+            const uint32_t code = peek_at(in, at + used, end, 4);
+            const unsigned width = code < 0xCu ? 2u : 4u;
+            const uint32_t len = code < 0xCu ? 2u + (code >> 2) : code - 7u;
+            if (have < used + width) break;
+            at += used + width;
+            off = o; extended = len == 8u;
+            seg_produce(sink, &count, 1, off, len);
+        }
+    }
+    if (exit_state) *exit_state = state;
+    if (count_out) *count_out = count;
+}
+
+/* lzs_scan_stream_kernel's contract: the dirty segments (all if d_dirty is NULL) report exit state and byte count, the others
+ * keep what they have; the round that passes d_all_ones gets lzs_all_ones_kernel's flags for every segment -- 0, or 1: the
+ * whole segment is 0xFF bytes (and lies inside its stream), or 2: and so are the first three bits after it.  d_marks and
+ * `compare` are the device's shortcut for repeated walks (same results) and are ignored here. */
+static unsigned g_scan_launches;
+unsigned lzs_shim_scan_launches(void) { return __atomic_load_n(&g_scan_launches, __ATOMIC_RELAXED); }   /* (a test can tell which route a call took) */
+int lzs_hip_launch_scan_stream(const void *d_in, uint32_t n, uint32_t nseg, const uint32_t *d_entry, const uint8_t *d_dirty, uint32_t *d_exit,
+                               uint32_t *d_count, uint8_t *d_all_ones, uint32_t *d_marks, int compare, uint32_t seg, int concat,
+                               const uint32_t *d_seg_base, const uint32_t *d_seg_end, uint32_t in_extent, void *stream)
+{
+    (void)d_marks; (void)compare; (void)in_extent; (void)stream;
+    __atomic_add_fetch(&g_scan_launches, 1, __ATOMIC_RELAXED);
+    const uint8_t *in = (const uint8_t *)d_in;
+    for (uint32_t k = 0; k < nseg; k++) {
+        const uint32_t sbase = d_seg_base ? d_seg_base[k] : k * seg, end = d_seg_end ? d_seg_end[k] : n;
+        if (d_all_ones) {
+            int ones = (uint64_t)sbase + seg <= end;
+            for (uint32_t i = 0; i < seg && ones; i++) ones = in[sbase + i] == 0xFFu;
+            d_all_ones[k] = !ones ? 0 : (sbase + seg < end && (in[sbase + seg] & 0xE0u) == 0xE0u) ? 2 : 1;
+        }
+        if (d_dirty && !d_dirty[k]) continue;
+        segment_walk(in, end, sbase, 8u * (uint64_t)seg, d_entry[k], concat, &d_exit[k], &d_count[k], NULL);
+    }
+    return launched();
+}
+
+/* lzs_decode_stream_kernel's contract, in order: segment k (unless its entry says the stream has ended before it) decodes to
+ * d_out + d_out_start[k], below `cap` (d_out_limit[k] with the tables), copies from before d_out_floor[k] yielding zeros.
+ * Serial, so every copy finds its source final: all origins are left clean and the counters (d_tainted) stay as the host
+ * cleared them -- the host's resolve rounds are therefore never reached here, and the resolve launches below stay
+ * unsupported (that loop is covered on the GPU, tests/test_gpu_parity.py:
+ * test_stream_decompress_resolve_shortcuts_agree_with_plain_rounds). */
+int lzs_hip_launch_decode_stream(void *d_out, uint32_t cap, uint32_t *d_origin, uint32_t *d_tainted, const void *d_in, uint32_t n,
+                                 uint32_t in_extent, uint32_t nseg, const uint32_t *d_entry, const uint32_t *d_out_start, uint32_t seg,
+                                 int concat, const uint32_t *d_seg_base, const uint32_t *d_seg_end, const uint32_t *d_out_floor,
+                                 const uint32_t *d_out_limit, void *stream)
+{
+    (void)d_tainted; (void)in_extent; (void)stream;
+    for (uint32_t k = 0; k < nseg; k++) {
+        if (d_entry[k] & LZS_SEG_STOP) continue;
+        const seg_sink_t sink = { (uint8_t *)d_out, d_origin, d_out_start[k], d_out_floor ? d_out_floor[k] : 0u, d_out_limit ? d_out_limit[k] : cap };
+        segment_walk((const uint8_t *)d_in, d_seg_end ? d_seg_end[k] : n, d_seg_base ? d_seg_base[k] : k * seg, 8u * (uint64_t)seg,
+                     d_entry[k], concat, NULL, NULL, &sink);
+    }
+    return launched();
+}
+/* The block decoder in its concatenated-streams form (the one-wavefront route of lzs_decompress_concat()): block b is one walk
+ * over the whole block that goes on after end markers, cut at the capacity. */
+int lzs_hip_launch_decompress_concat(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len, const void *d_in, size_t in_stride,
+                                     const uint32_t *d_in_len, uint32_t in_len, uint32_t nblocks, void *stream)
+{
+    (void)stream;
+    for (uint32_t b = 0; b < nblocks; b++) {
+        const seg_sink_t sink = { (uint8_t *)d_out + (size_t)b * out_stride, NULL, 0, 0, out_cap };
+        uint32_t count = 0;
+        segment_walk((const uint8_t *)d_in + (size_t)b * in_stride, d_in_len ? d_in_len[b] : in_len, 0, UINT64_MAX, 0, 1, NULL, &count, &sink);
+        d_out_len[b] = count < out_cap ? count : out_cap;
+    }
+    return launched();
+}
+
 int lzs_hip_launch_resolve_blocks(void *a, uint32_t *b, size_t c, const uint32_t *d, uint32_t e, void *f)
 { (void)a; (void)b; (void)c; (void)d; (void)e; (void)f; return E_NOT_SUPPORTED; }
 int lzs_hip_launch_resolve_stream(void *a, uint32_t *b, uint32_t c, uint32_t d, uint32_t *e, int f, void *g)

@@ -7,7 +7,9 @@
  *   degrade path (LZS_STAGING_FAIL_MB); one stream in segments with dirty-segment re-entry (runs and periods spanning
  *   many segments, cut capacities); the incremental interface in random pieces both ways on BOTH routes (device route:
  *   segments / stitch / extend-resume / decode-resume; host route: lzs_hostcodec.c) with 1-12 bytes of room for the
- *   low-memory block; the one-shot calls on both routes.
+ *   low-memory block; the one-shot calls on both routes; decompression by many wavefronts ("streamdec": the scan rounds with
+ *   their settle rule and all-0xFF shortcut, placement, one stream / concatenated streams / batches by segments / pieces of
+ *   the incremental interface, each compared with the same call by one wavefront).
  * Every result is compared with the oracle.  Exit code 0 = all cases passed (the sanitizers make it non-zero themselves).
  * TEST INFRASTRUCTURE ONLY.
  */
@@ -201,7 +203,7 @@ static size_t encode_pieces(const uint8_t *d, size_t n, uint8_t *out, size_t out
     return made;
 }
 
-static size_t decode_pieces(const uint8_t *s, size_t n, uint8_t *out, size_t out_cap, uint32_t in_lo, uint32_t in_hi, uint32_t out_lo, uint32_t out_hi)
+static size_t decode_pieces(const uint8_t *s, size_t n, uint8_t *out, size_t out_cap, uint32_t in_lo, uint32_t in_hi, uint32_t out_lo, uint32_t out_hi, uint8_t *status)
 {
     LzsDecompressParameters_t *p = (LzsDecompressParameters_t *)malloc(sizeof *p);
     lzs_decompress_init(p);
@@ -218,6 +220,7 @@ static size_t decode_pieces(const uint8_t *s, size_t n, uint8_t *out, size_t out
         if (!pending && pos >= n && (p->status & LZS_D_STATUS_INPUT_STARVED)) break;
         if (++calls > 4000000) { CHECK(0, "incremental decompression: no progress"); break; }
     }
+    if (status) *status = p->status;
     free(p);
     return made;
 }
@@ -242,7 +245,7 @@ static void incremental(void)
                 if (ranges[k][0] == 1 && n > 100000) continue;      /* (tiny pieces of the long cases: time) */
                 const size_t g = encode_pieces(cases[ci].d, n, got, cap, ranges[k][0], ranges[k][1], ranges[k][2], ranges[k][3], 0);
                 CHECK(g == w && memcmp(got, want, w) == 0, "%s route: incremental compression of case %u in pieces of %u..%u differs (%zu / %zu)", routes[ri], ci, ranges[k][0], ranges[k][1], g, w);
-                const size_t b = decode_pieces(want, w, back, n + 64, ranges[k][0], ranges[k][1], ranges[k][2], 3 * ranges[k][3]);
+                const size_t b = decode_pieces(want, w, back, n + 64, ranges[k][0], ranges[k][1], ranges[k][2], 3 * ranges[k][3], NULL);
                 CHECK(b == n && memcmp(back, cases[ci].d, n) == 0, "%s route: incremental decompression of case %u in pieces of %u..%u differs (%zu / %zu)", routes[ri], ci, ranges[k][0], ranges[k][1], b, n);
             }
             if (n <= 90000) {                                       /* the low-memory block: 1-12 bytes of room, random pieces */
@@ -256,6 +259,237 @@ static void incremental(void)
     }
     unsetenv("LZS_ROUTE");
     free(t); free(low); free(mix);
+}
+
+/* ---------------------------------------------------------------- decompression by many wavefronts: scan rounds, settle rule, placement
+ * (lzs_stream.c's stream_decompress() and batch_decompress_segments() over the shim's serial SCAN and DECODE).  Every call is
+ * made under LZS_ONE_WAVE=1 first -- the one-wavefront route, the oracle behind it -- and then by many wavefronts in segments
+ * of 256, 512 and 2048 bytes, plain, with LZS_NO_ONES=1 and with LZS_NO_MARKS=1: bytes, lengths and status must not differ. */
+unsigned lzs_shim_scan_launches(void);
+typedef size_t (*dec_fn)(uint8_t *, size_t, const uint8_t *, size_t);
+static const char *const sd_segs[3] = { "256", "512", "2048" };
+static const char *const sd_switches[3] = { NULL, "LZS_NO_ONES", "LZS_NO_MARKS" };
+#define SD_EACH_FORM(si, wi) for (unsigned si = 0; si < 3; si++) for (unsigned wi = 0; wi < 3; wi++)
+static void sd_form(unsigned si, unsigned wi, int on)
+{
+    if (on) { unsetenv("LZS_ONE_WAVE"); setenv("LZS_DEC_SEG", sd_segs[si], 1); if (sd_switches[wi]) setenv(sd_switches[wi], "1", 1); }
+    else { setenv("LZS_ONE_WAVE", "1", 1); unsetenv("LZS_DEC_SEG"); if (sd_switches[wi]) unsetenv(sd_switches[wi]); }
+}
+
+static void sd_call(const char *what, dec_fn fn, const char *name, const uint8_t *s, size_t n, size_t cap)
+{
+    uint8_t *want = (uint8_t *)malloc(cap + 8), *got = (uint8_t *)malloc(cap + 8);
+    const size_t w = fn(want, cap, s, n);
+    const int w_failed = lzs_last_error()[0] != 0;
+    SD_EACH_FORM(si, wi) {
+        sd_form(si, wi, 1);
+        memset(got, 0x5A, cap + 8);
+        const unsigned scans = lzs_shim_scan_launches();
+        const size_t g = fn(got, cap, s, n);
+        CHECK(g == w && memcmp(got, want, w) == 0 && (lzs_last_error()[0] != 0) == w_failed,
+              "%s: %s of %zu bytes into %zu, segments of %s, %s: %zu bytes, one wavefront %zu (%s)", what, name, n, cap, sd_segs[si],
+              sd_switches[wi] ? sd_switches[wi] : "plain", g, w, lzs_last_error());
+        CHECK(got[g <= cap ? g : cap] == 0x5A && got[cap] == 0x5A, "%s: %s of %zu bytes into %zu: a byte past the result touched", what, name, n, cap);
+        CHECK(!n || !cap || lzs_shim_scan_launches() > scans, "%s: %s of %zu bytes did not go by segments", what, name, n);
+        sd_form(si, wi, 0);
+    }
+    free(want); free(got);
+}
+
+/* a stream whole, into less room than it fills, cut short at random bytes, and with garbage after its end marker; `full`: its size */
+static void sd_stream(const char *what, const uint8_t *s, size_t n, size_t full, int variants)
+{
+    const dec_fn fns[2] = { lzs_decompress, lzs_decompress_concat };
+    const char *names[2] = { "lzs_decompress", "lzs_decompress_concat" };
+    uint8_t *junk = (uint8_t *)malloc(n + 700);
+    memcpy(junk, s, n);
+    for (size_t i = n; i < n + 700; i++) junk[i] = (uint8_t)rnd();
+    for (unsigned f = 0; f < 2; f++) {
+        sd_call(what, fns[f], names[f], s, n, full + 3);
+        if (full) sd_call(what, fns[f], names[f], s, n, rnd_in(1, (uint32_t)full));
+        if (!variants) continue;
+        for (int k = 0; k < 2 && n > 1; k++) sd_call(what, fns[f], names[f], s, rnd_in(1, (uint32_t)n - 1), full + 3);
+        sd_call(what, fns[f], names[f], junk, n + 700, full + 3);
+        sd_call(what, fns[f], names[f], junk, n + rnd_in(1, 700), full + 6000);
+    }
+    free(junk);
+}
+
+static void sd_put(uint8_t *buf, uint64_t *at, uint32_t value, unsigned width)     /* MSB first into zeroed memory */
+{
+    for (unsigned i = 0; i < width; i++, (*at)++)
+        if ((value >> (width - 1u - i)) & 1u) buf[*at >> 3] |= (uint8_t)(0x80u >> (*at & 7u));
+}
+
+/* A stream made by hand: `q` literals (0..3), a match at offset 1 with as many nibbles of 15 as bring its closing nibble `c` to
+ * the border of every segment size at byte 4096 -- the nibble ends there (q = 3) or has its last 1, 2, 3 bits behind it
+ * (q = 0, 1, 2: the token before the nibbles is 9 q + 13 bits) --, then `tail` literals and the end marker.  *full: its size. */
+static uint8_t *sd_run_to_border(unsigned q, unsigned c, const uint8_t *tail, size_t ntail, size_t *n, size_t *full)
+{
+    uint8_t *s = (uint8_t *)calloc(4096 + (9 * ntail + 9) / 8 + 8, 1);
+    const unsigned inside = 4u - (q + 1u) % 4u, nibbles = (8u * 4096u - inside - 9u * q - 13u) / 4u;
+    uint64_t at = 0;
+    for (unsigned i = 0; i < q; i++) sd_put(s, &at, "xyA"[3 - q + i], 9);
+    sd_put(s, &at, (3u << 7) | 1u, 9); sd_put(s, &at, 15, 4);                    /* offset 1, length 8 and more */
+    for (unsigned i = 0; i < nibbles; i++) sd_put(s, &at, 15, 4);
+    CHECK(at + inside == 8u * 4096u, "the closing nibble starts at bit %llu", (unsigned long long)at);
+    sd_put(s, &at, c, 4);
+    for (size_t i = 0; i < ntail; i++) sd_put(s, &at, tail[i], 9);
+    sd_put(s, &at, 0x180u, 9);
+    *n = (size_t)((at + 7) / 8);
+    *full = q + 8 + 15 * (size_t)nibbles + c + ntail;
+    return s;
+}
+
+typedef struct { uint8_t *s; size_t n, full; } sd_block_t;
+static sd_block_t sd_compressed(const uint8_t *d, size_t n)
+{
+    sd_block_t b = { (uint8_t *)malloc(LZS_COMPRESSED_MAX(n) + 8), 0, n };
+    b.n = lzs_oracle_compress(b.s, LZS_COMPRESSED_MAX(n), d, n);
+    return b;
+}
+
+/* ragged batches that go by segments (host_batch()'s conditions: a capacity, >= 4096 bytes in all, >= 1024 a block on average) */
+static void sd_batches(const uint8_t *text, const sd_block_t *run, const sd_block_t *edge, unsigned nedge)
+{
+    for (int pass = 0; pass < 4; pass++) {
+        const uint32_t nb = pass == 0 ? 4 : pass == 1 ? 64 : rnd_in(5, 63);
+        sd_block_t *blk = (sd_block_t *)calloc(nb, sizeof *blk);
+        uint32_t *lens = (uint32_t *)calloc(nb, 4);
+        size_t in_stride = 16, total = 0;
+        for (uint32_t b = 0; b < nb; b++) {
+            /* 0 the long run, 1 empty, 2 cut short, 3 a run closed across a border (the batch of 64 has them all), else text */
+            const int every = nb == 64 && b >= 4 && b < 4 + nedge;
+            const uint32_t kind = b < 4 ? b : every ? 3 : rnd() % 8u;
+            if (kind == 0) { blk[b] = *run; lens[b] = (uint32_t)run->n; }
+            else if (kind == 3) { blk[b] = edge[every ? b - 4 : rnd() % nedge]; lens[b] = (uint32_t)blk[b].n; }
+            else if (kind != 1) {
+                const uint32_t len = rnd_in(3000, 40000);
+                blk[b] = sd_compressed(text + rnd_in(0, 200000), len);
+                lens[b] = kind == 2 ? rnd_in(1, (uint32_t)blk[b].n - 1) : (uint32_t)blk[b].n;
+            }
+            if (lens[b] > in_stride) in_stride = lens[b];
+            total += lens[b];
+        }
+        CHECK(total >= 4096 && total / nb >= 1024, "batch of %u blocks, %zu bytes: too small to go by segments", nb, total);
+        in_stride += rnd_in(0, 40);
+        uint8_t *in = (uint8_t *)malloc(nb * in_stride);
+        memset(in, 0xEE, nb * in_stride);
+        for (uint32_t b = 0; b < nb; b++) if (lens[b]) memcpy(in + b * in_stride, blk[b].s, lens[b]);
+        for (int small = 0; small < 2; small++) {
+            const size_t cap = small ? 9000 : 130000, ostride = cap + 7;        /* (room for every block; less than many blocks give) */
+            uint8_t *want = (uint8_t *)malloc(nb * ostride), *got = (uint8_t *)malloc(nb * ostride);
+            uint32_t *want_len = (uint32_t *)calloc(nb, 4), *got_len = (uint32_t *)calloc(nb, 4);
+            const int want_rc = lzs_decompress_batch(want, ostride, cap, want_len, in, in_stride, lens, 0, nb);
+            CHECK(want_rc == 0, "lzs_decompress_batch, one wavefront a block: %s", lzs_last_error());
+            for (uint32_t b = 0; b < nb; b++) if (lens[b] == blk[b].n && blk[b].s) CHECK(want_len[b] == (blk[b].full < cap ? blk[b].full : cap), "block %u: %u bytes", b, want_len[b]);
+            SD_EACH_FORM(si, wi) {
+                const int sync = pass == 2 && !small && si == 0;       /* one batch also from "device" memory */
+                sd_form(si, wi, 1);
+                for (int dev = 0; dev <= sync; dev++) {
+                    memset(got, 0x5A, nb * ostride);
+                    memset(got_len, 0xFF, 4 * nb);
+                    const unsigned scans = lzs_shim_scan_launches();
+                    const int rc = dev ? lzs_decompress_batch_device_sync(got, ostride, cap, got_len, in, in_stride, lens, 0, nb)
+                                       : lzs_decompress_batch(got, ostride, cap, got_len, in, in_stride, lens, 0, nb);
+                    CHECK(rc == want_rc && lzs_shim_scan_launches() > scans, "batch of %u%s, segments of %s, %s: status %d, %s", nb, dev ? " (device)" : "",
+                          sd_segs[si], sd_switches[wi] ? sd_switches[wi] : "plain", rc, lzs_shim_scan_launches() > scans ? lzs_last_error() : "not by segments");
+                    for (uint32_t b = 0; b < nb; b++) {
+                        const int same = got_len[b] == want_len[b] && memcmp(got + b * ostride, want + b * ostride, want_len[b]) == 0;
+                        /* (the device form writes in place: only the byte past the capacity is surely nobody's) */
+                        const int clean = got[b * ostride + cap] == 0x5A && (dev || want_len[b] == cap || got[b * ostride + want_len[b]] == 0x5A);
+                        if (!same || !clean) { CHECK(0, "batch of %u%s, capacity %zu, segments of %s, %s: block %u (%u bytes in): %u bytes out, one wavefront %u%s", nb, dev ? " (device)" : "",
+                                                     cap, sd_segs[si], sd_switches[wi] ? sd_switches[wi] : "plain", b, lens[b], got_len[b], want_len[b], clean ? "" : "; a byte past the result touched"); break; }
+                    }
+                }
+                sd_form(si, wi, 0);
+            }
+            free(want); free(got); free(want_len); free(got_len);
+        }
+        for (uint32_t b = 0; b < nb; b++) {
+            int own = blk[b].s != run->s;
+            for (unsigned i = 0; i < nedge; i++) own &= blk[b].s != edge[i].s;
+            if (own) free(blk[b].s);
+        }
+        free(blk); free(lens); free(in);
+    }
+}
+
+static void streamdec(void)
+{
+    setenv("LZS_ROUTE", "device", 1);
+    setenv("LZS_FORCE_STREAM", "1", 1);
+    uint8_t *cls[3] = { sample(0, 420000, 21), sample(1, 420000, 22), sample(2, 420000, 23) };
+    const uint32_t longest[3] = { 340000, 400000, 170000 };         /* (up to ~200 KB of stream) */
+    for (unsigned c = 0; c < 3; c++) {
+        const size_t lengths[] = { 0, 1, rnd_in(2, 3000), rnd_in(3000, 60000), rnd_in(longest[c] / 2, longest[c]) };
+        for (unsigned i = 0; i < sizeof lengths / sizeof lengths[0]; i++) {
+            sd_block_t b = sd_compressed(cls[c] + rnd_in(0, 20000), lengths[i]);
+            char what[64];
+            snprintf(what, sizeof what, "class %u, %zu bytes", c, lengths[i]);
+            sd_stream(what, b.s, b.n, b.full, 1);
+            if (i == 0) sd_call(what, lzs_decompress, "lzs_decompress", b.s, 0, 8);         /* no input at all */
+            /* streams of one segment exactly, a byte less, a byte more (cut short: what their tokens give is the one wavefront's to say) */
+            if (i == 4) for (unsigned k = 0; k < 9; k++) sd_stream(what, b.s, (256u << (k / 3 == 2 ? 3 : k / 3)) + k % 3 - 1, b.full, 0);
+            free(b.s);
+        }
+    }
+    /* a long run: nibbles of 15 for segments on end (all 0xFF inside an extension, the host's shortcut) */
+    uint8_t *runs = (uint8_t *)malloc(70000 + 30000);
+    memset(runs, 'A', 70000); memcpy(runs + 70000, cls[0] + 1000, 30000);
+    sd_block_t run = sd_compressed(runs, 70000), run_text = sd_compressed(runs, 100000), border, border_text;
+    border.s = sd_run_to_border(3, 6, NULL, 0, &border.n, &border.full);
+    border_text.s = sd_run_to_border(3, 6, cls[0] + 5000, 700, &border_text.n, &border_text.full);
+    sd_stream("a run of 70000", run.s, run.n, run.full, 1);
+    sd_stream("a run of 70000, then text", run_text.s, run_text.n, run_text.full, 1);
+    sd_stream("a run ending at a segment border", border.s, border.n, border.full, 1);
+    sd_stream("a run ending at a segment border, then literals", border_text.s, border_text.n, border_text.full, 1);
+    {   /* (the hand-made streams decode to what they were made for) */
+        uint8_t *back = (uint8_t *)malloc(border_text.full + 8);
+        const size_t g = lzs_oracle_decompress(back, border_text.full + 8, border_text.s, border_text.n);
+        CHECK(g == border_text.full && back[2] == 'A' && back[g - 701] == 'A' && memcmp(back + g - 700, cls[0] + 5000, 700) == 0, "the hand-made run decodes to %zu bytes", g);
+        free(back);
+    }
+    /* (the closing nibble across the border, in every phase: whether the last nibble that starts in an all-0xFF segment is one of 15
+     * is the shortcut's fine print) */
+    static const unsigned closing[5] = { 0, 7, 8, 12, 14 };
+    sd_block_t edge[20];
+    for (unsigned q = 0; q < 4; q++)
+        for (unsigned ci = 0; ci < 5; ci++) {
+            sd_block_t *b = &edge[5 * q + ci];
+            char what[64];
+            snprintf(what, sizeof what, "a run closed by nibble %u, %u bits before a border", closing[ci], 4u - (q + 1u) % 4u);
+            b->s = sd_run_to_border(q, closing[ci], cls[0] + 100 * ci, 300 + q, &b->n, &b->full);
+            sd_stream(what, b->s, b->n, b->full, 0);
+        }
+    sd_batches(cls[0], &run, edge, 20);
+    for (unsigned i = 0; i < 20; i++) free(edge[i].s);
+    /* the incremental interface in pieces above INC_DEC_HOST_MAX: stream_decompress() with a prefix, an entry state, a history */
+    memset(runs, 'A', 100000); memcpy(runs, cls[0], 15000); memcpy(runs + 85000, cls[0] + 15000, 15000);
+    const sd_block_t pieces[2] = { sd_compressed(cls[0] + 777, 340000), sd_compressed(runs, 100000) };
+    for (unsigned c = 0; c < 2; c++) {
+        const size_t n = pieces[c].full;
+        uint8_t *want = (uint8_t *)malloc(n + 64), *got = (uint8_t *)malloc(n + 64);
+        uint8_t want_status = 0, status = 0;
+        const uint32_t in_lo = c ? 17000 : 66000, in_hi = c ? 20000 : 120000;     /* (the run's stream is short: pieces from INC_DEC_STREAM_MIN on) */
+        const uint64_t seed = rng_state;
+        const size_t w = decode_pieces(pieces[c].s, pieces[c].n, want, n + 64, in_lo, in_hi, 4096, 200000, &want_status);
+        CHECK(w == n, "incremental decompression, one wavefront: %zu of %zu bytes", w, n);
+        SD_EACH_FORM(si, wi) {
+            sd_form(si, wi, 1);
+            rng_state = seed;
+            const unsigned scans = lzs_shim_scan_launches();
+            const size_t g = decode_pieces(pieces[c].s, pieces[c].n, got, n + 64, in_lo, in_hi, 4096, 200000, &status);
+            CHECK(g == w && memcmp(got, want, w) == 0 && status == want_status && lzs_shim_scan_launches() > scans,
+                  "incremental decompression of case %u, segments of %s, %s: %zu bytes, status %02x; one wavefront %zu, %02x", c, sd_segs[si],
+                  sd_switches[wi] ? sd_switches[wi] : "plain", g, status, w, want_status);
+            sd_form(si, wi, 0);
+        }
+        free(want); free(got); free(pieces[c].s);
+    }
+    free(run.s); free(run_text.s); free(border.s); free(border_text.s); free(runs);
+    for (unsigned c = 0; c < 3; c++) free(cls[c]);
+    unsetenv("LZS_ROUTE"); unsetenv("LZS_FORCE_STREAM");
 }
 
 /* ---------------------------------------------------------------- what a thread keeps, and giving it back
@@ -328,13 +562,14 @@ static void canary(void)
 int main(int argc, char **argv)
 {
     setenv("LZS_DEV_ENV", "1", 1);          /* the switches are read afresh on every call: this program flips them */
-    setenv("LZS_ONE_WAVE", "1", 1);         /* decompression stays off the many-wavefront launches (not modelled by the shim) */
+    setenv("LZS_ONE_WAVE", "1", 1);         /* decompression by one wavefront a stream, the oracle behind it ("streamdec" lifts this call by call) */
     const char *only = argc > 1 ? argv[1] : "";
     char info[256];
     if (lzs_backend_info(info, sizeof info) != 0 || !strstr(info, "cpu shim")) { fprintf(stderr, "not linked with the cpu shim: %s\n", info); return 2; }
     if (!*only || !strcmp(only, "ragged")) ragged_batches();
     if (!*only || !strcmp(only, "streams")) one_shot_streams();
     if (!*only || !strcmp(only, "incremental")) incremental();
+    if (!*only || !strcmp(only, "streamdec")) streamdec();
     if (!*only || !strcmp(only, "pipeline")) pipeline();
     if (!*only || !strcmp(only, "release")) release_cache();
     if (!strcmp(only, "canary")) canary();

@@ -1012,6 +1012,31 @@ def test_small_batches_decompressed_in_segments():
             assert got[i] == O.decompress(st, cap), (cap, i)
 
 
+def test_batch_in_segments_is_the_same_without_the_scan_shortcuts(monkeypatch):
+    """The scan rounds of a batch by segments are those of one stream: the all-0xFF shortcut (LZS_NO_ONES=1 turns it off)
+    and the merge marks of repeated walks (LZS_NO_MARKS=1) are shortcuts there too, not conditions.  Eight blocks of
+    16 KiB -- two runs of one byte value, two of text, two of random bytes, two runs cut short -- in 256-byte segments:
+    lengths and bytes as the oracle gives them, whichever shortcut is off."""
+    n = 16384
+    rng = np.random.default_rng(33)
+    text = bytes(workload.fill("text", 1).reshape(-1))
+    plains = [bytes(n), b"\x90" * n, text[:n], text[n:2 * n]] + [bytes(rng.integers(0, 256, n, dtype=np.uint8)) for _ in range(2)]
+    streams = [O.compress(p) for p in plains]
+    assert all(len(s) > 512 and s[256:512] == b"\xff" * 256 for s in streams[:2])       # (a whole segment of nibbles of 15)
+    streams += [streams[0][:len(streams[0]) * 2 // 3], streams[1][:len(streams[1]) // 2]]
+    want = [O.decompress(s, n + 5) for s in streams]
+    assert want[:6] == plains
+    monkeypatch.setenv("LZS_DEC_SEG", "256")
+    for switch in (None, "LZS_NO_ONES", "LZS_NO_MARKS"):
+        if switch:
+            monkeypatch.setenv(switch, "1")
+        got = _gpu_decompress_many(streams, n + 5)
+        if switch:
+            monkeypatch.delenv(switch)
+        assert [len(g) for g in got] == [len(w) for w in want], switch
+        assert got == want, switch
+
+
 def test_long_match_ending_at_a_segment_border_of_all_ones():
     """A long run is thousands of 1111 nibbles; a segment that is nothing but 0xFF inside a running
     extension is not walked, its exit is worked out by the host -- which is only right if the last

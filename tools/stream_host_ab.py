@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Wall time per call of the many-wavefront decompression's host paths, this build against another build of liblzs.so.
+
+    python tools/stream_host_ab.py --other path/to/other/liblzs.so [--reps 10] [--shapes dec-1m,dec-64m,dev-1g,batch-256] [--out FILE]
+
+Shapes (text): dec-1m / dec-64m  lzs_decompress of a stream that decodes to 1 / 64 MiB, host buffers;
+               dev-1g            lzs_decompress_stream_device of 1 GiB;
+               batch-256         lzs_decompress_batch of 256 blocks of 64 KiB, host buffers (goes by segments).
+Every shape gets two worker processes -- one per build, chosen by LZS_LIBRARY, each with its data made, checked and three calls
+warm -- and the two are timed in turn, one call each, `--reps` times: what one build sees of the machine the other sees too.
+The verdict per shape: this build's median is no more than the other's median plus the other's own spread (max - min).
+Exit code 1 if a shape misses that."""
+import argparse
+import ctypes
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+SHAPES = {"dec-1m": 16, "dec-64m": 1024, "dev-1g": 16384, "batch-256": 256}       # 64 KiB blocks of text
+
+
+def worker(shape):
+    """Prepare, check, warm up; then one timed call per line read from stdin, its milliseconds on stdout."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import lzs_compression_amd as lzs
+    from lzs_compression_amd import workload
+    L = lzs.lib()
+    x = workload.fill("text", SHAPES[shape])
+    if shape == "batch-256":
+        comp, lens = lzs.compress_batch(x)
+        out, out_len = np.zeros_like(x), np.zeros(len(x), dtype=np.uint32)
+
+        def call():
+            assert L.lzs_decompress_batch(out.ctypes.data, out.shape[1], out.shape[1], out_len.ctypes.data, comp.ctypes.data,
+                                          comp.shape[1], lens.ctypes.data, comp.shape[1], len(x)) == 0
+        check = lambda: bool((out_len == x.shape[1]).all()) and np.array_equal(out, x)
+    elif shape == "dev-1g":
+        import torch
+        plain = torch.from_numpy(x.reshape(-1)).cuda()
+        buf, nbytes = lzs.compress_stream(plain)
+        comp, out, got = buf[:nbytes].clone(), torch.empty(plain.numel() + 64, dtype=torch.uint8, device="cuda"), ctypes.c_size_t(0)
+        torch.cuda.synchronize()
+
+        def call():
+            assert L.lzs_decompress_stream_device(out.data_ptr(), out.numel(), ctypes.byref(got), comp.data_ptr(), comp.numel()) == 0
+        check = lambda: got.value == plain.numel() and bool(torch.equal(out[:got.value], plain))
+    else:
+        import torch
+        buf, nbytes = lzs.compress_stream(torch.from_numpy(x.reshape(-1)).cuda())
+        comp = buf[:nbytes].cpu().numpy().copy()
+        out, got = np.zeros(x.size + 64, dtype=np.uint8), [0]
+
+        def call():
+            got[0] = L.lzs_decompress(out.ctypes.data, out.size, comp.ctypes.data, comp.size)
+        check = lambda: got[0] == x.size and np.array_equal(out[:x.size], x.reshape(-1))
+    for _ in range(3):
+        call()
+    assert check(), f"{shape}: wrong result"
+    print("ready", flush=True)
+    for line in sys.stdin:
+        if line.strip() != "go":
+            break
+        t = time.perf_counter()
+        call()
+        print(f"{(time.perf_counter() - t) * 1e3:.4f}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--other", help="the liblzs.so to compare with")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--out", help="also write the report here")
+    ap.add_argument("--worker", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.worker:
+        return worker(a.worker)
+    assert a.other and os.path.exists(a.other), "--other: the build to compare with"
+    lines, failed = [], False
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"# tools/stream_host_ab.py: this build against {os.path.basename(os.path.dirname(os.path.abspath(a.other)))}/{os.path.basename(a.other)}; "
+        f"{a.reps} calls each, in turn, after 3 warm calls; ms a call")
+    table = []
+    for shape in a.shapes.split(","):
+        procs = {}
+        for who, so in (("other", os.path.abspath(a.other)), ("this", None)):
+            env = {k: v for k, v in os.environ.items() if k != "LZS_LIBRARY"}
+            if so:
+                env["LZS_LIBRARY"] = so
+            procs[who] = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", shape], env=env, text=True,
+                                          stdin=subprocess.PIPE, stdout=subprocess.PIPE)
+        times = {"other": [], "this": []}
+        try:
+            for who, p in procs.items():
+                line = p.stdout.readline().strip()
+                assert line == "ready", f"{shape}: the worker of {who} build said {line!r}"
+            for _ in range(a.reps):
+                for who, p in procs.items():
+                    p.stdin.write("go\n")
+                    p.stdin.flush()
+                    times[who].append(float(p.stdout.readline()))
+        finally:
+            for p in procs.values():
+                p.stdin.close()
+                p.wait(timeout=120)
+        for who in ("other", "this"):
+            say(f"{shape:10} {who:5} " + " ".join(f"{t:9.3f}" for t in times[who]))
+        med = {w: statistics.median(times[w]) for w in times}
+        spread = max(times["other"]) - min(times["other"])
+        ok = med["this"] <= med["other"] + spread
+        failed |= not ok
+        table.append(f"{shape:10} {med['other']:12.3f} {min(times['other']):9.3f} {max(times['other']):9.3f} {med['this']:12.3f} {min(times['this']):9.3f} "
+                     f"{max(times['this']):9.3f}   {'ok' if ok else 'SLOWER'} (this <= {med['other'] + spread:.3f})")
+    say("")
+    say(f"{'shape':10} {'other median':>12} {'min':>9} {'max':>9} {'this median':>12} {'min':>9} {'max':>9}   this median <= other median + (other max - min)")
+    for row in table:
+        say(row)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
