@@ -59,8 +59,10 @@ int lzs_backend_info(char *buf, size_t cap)
 }
 
 /* ------------------------------------------------------------------ device batches */
+/* (positions are 32-bit on the device) */
+static uint32_t clamp32(size_t out_cap) { return out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap; }
 
-static int check_batch(const char *who, const void *out_len, const void *in, size_t in_len,
+static int check_batch(const char *who, const void *out, size_t out_cap, const void *out_len, const void *in, size_t in_len,
                        size_t nblocks)
 {
     if (nblocks == 0) return LZS_OK;
@@ -68,21 +70,51 @@ static int check_batch(const char *who, const void *out_len, const void *in, siz
     if (!in && in_len) return fail(LZS_E_ARG, "%s: input is NULL", who);
     if (in_len > LZS_BLOCK_MAX) return fail(LZS_E_ARG, "%s: block of %zu bytes exceeds LZS_BLOCK_MAX", who, in_len);
     if (nblocks > 0x7FFFFFFFu) return fail(LZS_E_ARG, "%s: too many blocks (%zu)", who, nblocks);
+    if (!out && out_cap) return fail(LZS_E_ARG, "%s: output is NULL", who);
     return LZS_OK;
+}
+
+/* the bytes of a batch's input in all, and its longest block */
+static size_t batch_input(const uint32_t *in_len_each, size_t in_len, size_t nblocks, size_t *longest)
+{
+    size_t total = in_len_each ? 0 : in_len * nblocks;
+    *longest = in_len_each ? 0 : in_len;
+    for (size_t b = 0; in_len_each && b < nblocks; b++) {
+        total += in_len_each[b];
+        if (in_len_each[b] > *longest) *longest = in_len_each[b];
+    }
+    return total;
+}
+
+/* A small batch of blocks to decompress does not fill the device with one wavefront per block
+ * (a wavefront takes 9 ms for a 64 KiB block, whatever the batch): then the blocks are cut
+ * into segments for many wavefronts, like one long stream.  Everything else is a large batch's to try:
+ * copy in, run and copy back overlapped, chunk by chunk (lzs_pipeline.c). */
+LZS_HIDDEN batch_route_t host_batch_route(launch_fn launch, uint32_t cap32, size_t nblocks, size_t d_in_stride, size_t d_out_stride,
+                                          size_t total_in, const lzs_env_t *env)
+{
+    const unsigned long long seg_extent = env->batch_seg_mb > 0 ? (unsigned long long)env->batch_seg_mb << 20 : BATCH_SEG_MAX_EXTENT;
+    if (launch != lzs_hip_launch_decompress || !cap32 || env->one_wave || nblocks > BATCH_SEG_MAX_BLOCKS ||
+        (unsigned long long)nblocks * d_out_stride > seg_extent) return ROUTE_PIPELINE;
+    /* A batch small enough for the segments whose INPUT is not theirs -- under STREAM_DEC_MIN bytes in all or 1024 a block on
+     * average, say 1000 slots of 64 KiB whose streams are 500 bytes each -- goes one after the other and is NOT offered to
+     * the pipeline, although it may be large enough for it.  That is what two copies of this rule used to do between them;
+     * nobody has measured whether it is right. */
+    if (total_in >= STREAM_DEC_MIN && total_in / nblocks >= 1024u &&
+        (unsigned long long)nblocks * d_in_stride < 0xF0000000ull) return ROUTE_SEGMENTS;      /* segment tables hold 32-bit input offsets */
+    return ROUTE_SERIAL;
 }
 
 static int device_batch(const char *who, launch_fn launch, void *d_out, size_t out_stride,
                         size_t out_cap, uint32_t *d_out_len, const void *d_in, size_t in_stride,
                         const uint32_t *d_in_len, size_t in_len, size_t nblocks, void *stream)
 {
-    int rc = check_batch(who, d_out_len, d_in, in_len, nblocks);
+    int rc = check_batch(who, d_out, out_cap, d_out_len, d_in, in_len, nblocks);
     if (rc != LZS_OK || nblocks == 0) return rc;
-    if (!d_out && out_cap) return fail(LZS_E_ARG, "%s: output is NULL", who);
     /* the lengths written are not the lengths read: a compress launch leaves every block's class in d_out_len[] before any
      * workgroup reads d_in_len[] */
     if (d_in_len && (const void *)d_in_len == (const void *)d_out_len) return fail(LZS_E_ARG, "%s: d_out_len and d_in_len are the same array", who);
-    uint32_t cap32 = out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap;
-    int e = launch(d_out, out_stride, cap32, d_out_len, d_in, in_stride, d_in_len,
+    int e = launch(d_out, out_stride, clamp32(out_cap), d_out_len, d_in, in_stride, d_in_len,
                    (uint32_t)in_len, (uint32_t)nblocks, stream);
     return e ? hip_fail(e, who) : LZS_OK;
 }
@@ -108,28 +140,24 @@ int lzs_decompress_batch_device_sync(void *d_out, size_t out_stride, size_t out_
                                      size_t in_len, size_t nblocks)
 {
     const char *who = "lzs_decompress_batch_device_sync";
-    int rc = check_batch(who, out_len, d_in, in_len, nblocks);
+    int rc = check_batch(who, d_out, out_cap, out_len, d_in, in_len, nblocks);
     if (rc != LZS_OK || nblocks == 0) return rc;
-    if (!d_out && out_cap) return fail(LZS_E_ARG, "%s: output is NULL", who);
-    size_t total_in = 0, longest = 0;
-    for (size_t b = 0; b < nblocks; b++) {
-        const size_t len = in_len_each ? in_len_each[b] : in_len;
-        total_in += len;
-        if (len > longest) longest = len;
-    }
+    size_t longest = 0;
+    const size_t total_in = batch_input(in_len_each, in_len, nblocks, &longest);
     if (longest > LZS_BLOCK_MAX) return fail(LZS_E_ARG, "%s: block exceeds LZS_BLOCK_MAX", who);
     if ((rc = require_device()) != LZS_OK) return rc;
     staging_t *st = staging_get();
     if (!st) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
     int e = 0;
     if (!st->stream && (e = lzs_hip_stream_create(&st->stream))) return hip_fail(e, "hipStreamCreate");
-    const uint32_t cap32 = out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap;
+    const uint32_t cap32 = clamp32(out_cap);
     void *d_len = NULL, *d_in_len = NULL;
     if ((e = staging_reserve(st, BUF_LEN, sizeof(uint32_t) * nblocks, &d_len)))
         return fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e));
-    if (cap32 && nblocks <= BATCH_SEG_MAX_BLOCKS && total_in >= STREAM_DEC_MIN && total_in / nblocks >= 1024u &&
-        (unsigned long long)nblocks * out_stride <= BATCH_SEG_MAX_EXTENT && (unsigned long long)nblocks * in_stride < 0xF0000000ull &&
-        cap32 <= out_stride) {
+    /* (the blocks are where they are: the route is asked with the caller's strides, and the segments write in place.  There
+     * is nothing to copy, so nothing to overlap: every answer but ROUTE_SEGMENTS is one launch here) */
+    if (cap32 <= out_stride &&
+        host_batch_route(lzs_hip_launch_decompress, cap32, nblocks, in_stride, out_stride, total_in, lzs_env()) == ROUTE_SEGMENTS) {
         rc = batch_decompress_segments(st, st->stream, who, d_out, out_stride, cap32, out_len, (uint32_t *)d_len, d_in, in_stride,
                                        in_len_each, (uint32_t)in_len, nblocks);
     } else {
@@ -183,7 +211,7 @@ static void staging_destroy(void *p)
     if (st->host_tab) lzs_hip_host_free(st->host_tab);
     for (int i = 0; i < PIPE_STREAMS; i++) if (st->pipe_stream[i]) lzs_hip_stream_destroy(st->pipe_stream[i]);
     for (int i = 0; i < PIPE_EVENTS; i++) if (st->pipe_event[i]) lzs_hip_event_destroy(st->pipe_event[i]);
-    for (int i = 0; i < 6; i++) if (st->pin[i]) lzs_hip_host_free(st->pin[i]);
+    for (int i = 0; i < PIN_COUNT; i++) if (st->pin[i]) lzs_hip_host_free(st->pin[i]);
     hostcodec_free(st->hostcodec);
     free(st);
 }
@@ -213,22 +241,34 @@ LZS_HIDDEN staging_t *staging_get(void)
     return st;
 }
 
+/* Grow-only: a buffer smaller than `bytes` is given back and made anew, of whole 64 KiB; 0, or the allocator's error and
+ * no buffer. */
+static int grow(void **p, size_t *cap, size_t bytes, int (*alloc)(void **, size_t), int (*release)(void *))
+{
+    if (*cap >= bytes) return 0;
+    if (*p) { release(*p); *p = NULL; *cap = 0; }
+    const size_t want = (bytes + 65535u) & ~(size_t)65535u;
+    const int e = alloc(p, want);
+    if (e) { *p = NULL; return e; }
+    *cap = want;
+    return 0;
+}
+
+static int device_malloc(void **p, size_t want)
+{
+    /* (tests: LZS_STAGING_FAIL_MB=n makes a reservation above n MiB fail the way a full device fails it -- by a real
+     * hipMalloc that cannot succeed, so that the runtime's sticky last error is set as it would be) */
+    const int fail_mb = lzs_env()->staging_fail_mb;
+    if (fail_mb > 0 && want > ((size_t)fail_mb << 20)) want = (size_t)1 << 60;
+    return lzs_hip_malloc(p, want);
+}
+
 /* 0 on success, else a hipError_t */
 LZS_HIDDEN int staging_reserve(staging_t *st, int which, size_t bytes, void **out)
 {
-    if (st->cap[which] < bytes) {
-        if (st->buf[which]) { lzs_hip_free(st->buf[which]); st->buf[which] = NULL; st->cap[which] = 0; }
-        size_t want = (bytes + 65535u) & ~(size_t)65535u;
-        /* (tests: LZS_STAGING_FAIL_MB=n makes a reservation above n MiB fail the way a full device fails it -- by a real
-         * hipMalloc that cannot succeed, so that the runtime's sticky last error is set as it would be) */
-        const int fail_mb = lzs_env()->staging_fail_mb;
-        if (fail_mb > 0 && want > ((size_t)fail_mb << 20)) want = (size_t)1 << 60;
-        int e = lzs_hip_malloc(&st->buf[which], want);
-        if (e) { st->buf[which] = NULL; return e; }
-        st->cap[which] = want;
-    }
+    const int e = grow(&st->buf[which], &st->cap[which], bytes, device_malloc, lzs_hip_free);
     *out = st->buf[which];
-    return 0;
+    return e;
 }
 
 /* ---- the environment, once per process (lzs_internal.h) */
@@ -302,28 +342,18 @@ static size_t keep_max(void)
 
 LZS_HIDDEN int staging_pin_reserve(staging_t *st, int which, size_t bytes, uint8_t **out)
 {
-    if (st->pin_cap[which] < bytes) {
-        if (st->pin[which]) { lzs_hip_host_free(st->pin[which]); st->pin[which] = NULL; st->pin_cap[which] = 0; }
-        const size_t want = (bytes + 65535u) & ~(size_t)65535u;
-        /* Pieces only the copy engines and the host touch are non-coherent (56 against 35-39 GB/s on a quiet device); the
-         * piece a KERNEL writes (PIN_LENGTHS: lzs_hip_words_to_host) is coherent host memory -- HIP does not promise that a
-         * kernel's stores to non-coherent host memory are visible to the host at an event. */
-        const int e = which == PIN_LENGTHS ? lzs_hip_host_malloc(&st->pin[which], want) : lzs_hip_host_malloc_staging(&st->pin[which], want);
-        if (e) { st->pin[which] = NULL; return e; }
-        st->pin_cap[which] = want;
-    }
+    /* Pieces only the copy engines and the host touch are non-coherent (56 against 35-39 GB/s on a quiet device); the
+     * piece a KERNEL writes (PIN_LENGTHS: lzs_hip_words_to_host) is coherent host memory -- HIP does not promise that a
+     * kernel's stores to non-coherent host memory are visible to the host at an event. */
+    const int e = grow(&st->pin[which], &st->pin_cap[which], bytes, which == PIN_LENGTHS ? lzs_hip_host_malloc : lzs_hip_host_malloc_staging,
+                       lzs_hip_host_free);
     *out = (uint8_t *)st->pin[which];
-    return 0;
+    return e;
 }
 
 LZS_HIDDEN void *staging_host_tables(staging_t *st, size_t bytes)
 {
-    if (st->host_tab_cap < bytes) {
-        if (st->host_tab) { lzs_hip_host_free(st->host_tab); st->host_tab = NULL; st->host_tab_cap = 0; }
-        const size_t want = (bytes + 65535u) & ~(size_t)65535u;
-        if (lzs_hip_host_malloc(&st->host_tab, want)) { st->host_tab = NULL; return NULL; }
-        st->host_tab_cap = want;
-    }
+    grow(&st->host_tab, &st->host_tab_cap, bytes, lzs_hip_host_malloc, lzs_hip_host_free);
     return st->host_tab;
 }
 
@@ -338,78 +368,42 @@ LZS_HIDDEN void staging_trim(staging_t *st)
         sum -= st->cap[big];
         lzs_hip_free(st->buf[big]); st->buf[big] = NULL; st->cap[big] = 0;
     }
-    /* the pinned pieces of the overlapped host batches (up to 6 x 46 MiB x the group) and the tables of the stream paths
+    /* the pinned pieces of the overlapped host batches (PIN_COUNT of them, up to 46 MiB each) and the tables of the stream paths
      * follow the same limit, on the host's side */
     size_t pinned = st->host_tab_cap;
-    for (int i = 0; i < 6; i++) pinned += st->pin_cap[i];
+    for (int i = 0; i < PIN_COUNT; i++) pinned += st->pin_cap[i];
     if (pinned > limit) {
-        for (int i = 0; i < 6; i++) if (st->pin[i]) { lzs_hip_host_free(st->pin[i]); st->pin[i] = NULL; st->pin_cap[i] = 0; }
+        for (int i = 0; i < PIN_COUNT; i++) if (st->pin[i]) { lzs_hip_host_free(st->pin[i]); st->pin[i] = NULL; st->pin_cap[i] = 0; }
         if (st->host_tab) { lzs_hip_host_free(st->host_tab); st->host_tab = NULL; st->host_tab_cap = 0; }
     }
 }
 
 /* -------------------------------------------------------------------- host batches */
-int lzs_hip_launch_decompress(void *, size_t, uint32_t, uint32_t *, const void *, size_t, const uint32_t *, uint32_t, uint32_t, void *);
-
 /* Stage host buffers through this thread's device memory.  Blocks are packed on the device
  * with 16-byte-aligned strides so the kernels take their aligned paths, whatever the
- * caller's strides are. */
-static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+ * caller's strides are.  This is the one-after-the-other route: copy in, run, copy out on the thread's one stream. */
 
-static int host_batch(const char *who, launch_fn launch, uint8_t *out, size_t out_stride,
-                      size_t out_cap, uint32_t *out_len, const uint8_t *in, size_t in_stride,
-                      const uint32_t *in_len_each, size_t in_len, size_t nblocks)
+/* LZS_STREAM_DEBUG: what the stage that ends here took */
+static void stage_done(const char *who, size_t nblocks, void *stream, const char *name, double *t0)
 {
-    int rc = check_batch(who, out_len, in, in_len, nblocks);
-    if (rc != LZS_OK || nblocks == 0) return rc;
-    if (!out && out_cap) return fail(LZS_E_ARG, "%s: output is NULL", who);
-    if (in_len_each) {
-        in_len = 0;
-        for (size_t b = 0; b < nblocks; b++) {
-            if (in_len_each[b] > in_len) in_len = in_len_each[b];
-        }
-        if (in_len > LZS_BLOCK_MAX) return fail(LZS_E_ARG, "%s: block exceeds LZS_BLOCK_MAX", who);
-    }
-    if ((rc = require_device()) != LZS_OK) return rc;
+    if (!lzs_env()->stream_debug) return;
+    lzs_hip_stream_sync(stream);
+    const double t1 = now_ms();
+    fprintf(stderr, "liblzs %s (%zu blocks): %s %.2f ms\n", who, nblocks, name, t1 - *t0);
+    *t0 = t1;
+}
 
-    const uint32_t cap32 = out_cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : (uint32_t)out_cap;
-    /* a large batch: copy in, run and copy back overlapped, chunk by chunk (lzs_pipeline.c) */
-    const unsigned long long seg_extent = lzs_env()->batch_seg_mb > 0 ? (unsigned long long)lzs_env()->batch_seg_mb << 20 : BATCH_SEG_MAX_EXTENT;
-    const int by_segments = launch == lzs_hip_launch_decompress && cap32 && !lzs_env()->one_wave && nblocks <= BATCH_SEG_MAX_BLOCKS &&
-                            (unsigned long long)nblocks * round_up(cap32, 16) <= seg_extent;
-    if (!by_segments) {
-        int taken = 0;
-        rc = host_batch_pipelined(who, launch, out, out_stride, cap32, out_len, in, in_stride, in_len_each, in_len, nblocks, &taken);
-        if (taken || rc != LZS_OK) return rc;
-    }
-    const size_t d_in_stride = round_up(in_len ? in_len : 1, 16);
-    const size_t d_out_stride = round_up(cap32 ? cap32 : 1, 16);
-    void *stream = NULL, *d_in = NULL, *d_out = NULL, *d_len = NULL, *d_in_len = NULL;
-    uint8_t *bounce[2] = {NULL, NULL};
-    int e = 0;
-    rc = LZS_OK;
-    staging_t *st = staging_get();
-    if (!st) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
-
-#define HIP_TRY(call, what) HIP_TRY_OR(done, call, what)
-    if (!st->stream) HIP_TRY(lzs_hip_stream_create(&st->stream), "hipStreamCreate");
-    stream = st->stream;
-    e = staging_reserve(st, BUF_IN, d_in_stride * nblocks, &d_in);
-    if (!e) e = staging_reserve(st, BUF_OUT, d_out_stride * nblocks, &d_out);
-    if (!e) e = staging_reserve(st, BUF_LEN, sizeof(uint32_t) * nblocks, &d_len);
-    if (!e && in_len_each) e = staging_reserve(st, BUF_INLEN, sizeof(uint32_t) * nblocks, &d_in_len);
-    if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto done; }
-
-    const int debug = lzs_env()->stream_debug;
-    double t0 = debug ? now_ms() : 0, t1;
-#define STAGE(name) do { if (debug) { lzs_hip_stream_sync(stream); t1 = now_ms(); fprintf(stderr, "liblzs %s (%zu blocks): %s %.2f ms\n", who, nblocks, name, t1 - t0); t0 = t1; } } while (0)
+static int copy_blocks_in(const char *who, staging_t *st, void *stream, void *d_in, size_t d_in_stride, const uint8_t *in,
+                          size_t in_stride, const uint32_t *in_len_each, size_t in_len, size_t nblocks)
+{
+    int e = 0, rc = LZS_OK;
+    uint8_t *bounce = NULL;
     if (in_stride == d_in_stride && !in_len_each) {
-        HIP_TRY(lzs_hip_h2d(d_in, in, d_in_stride * (nblocks - 1) + in_len, stream), "hipMemcpy H2D");
+        HIP_TRY_OR(done, lzs_hip_h2d(d_in, in, d_in_stride * (nblocks - 1) + in_len, stream), "hipMemcpy H2D");
     } else if (nblocks < 16) {
         for (size_t b = 0; b < nblocks; b++) {
-            size_t len_b = in_len_each ? in_len_each[b] : in_len;
-            HIP_TRY(lzs_hip_h2d((uint8_t *)d_in + b * d_in_stride, in + b * in_stride, len_b, stream),
-                    "hipMemcpy H2D");
+            const size_t len_b = in_len_each ? in_len_each[b] : in_len;
+            HIP_TRY_OR(done, lzs_hip_h2d((uint8_t *)d_in + b * d_in_stride, in + b * in_stride, len_b, stream), "hipMemcpy H2D");
         }
     } else {
         /* ragged or strided blocks: laid out at the device stride by the CPU, 32 MiB at a time
@@ -420,104 +414,129 @@ static int host_batch(const char *who, launch_fn launch, uint8_t *out, size_t ou
          * directly; plain memory only if there is no pinned memory to be had) */
         const size_t lay = (nblocks < per ? nblocks : per) * d_in_stride;
         uint8_t *piece_in = NULL;
-        if (staging_pin_reserve(st, 0, lay, &piece_in)) {
-            bounce[0] = (uint8_t *)malloc(lay);
-            if (!bounce[0]) { rc = fail(LZS_E_NOMEM, "%s: out of host memory", who); goto done; }
-            piece_in = bounce[0];
+        if (staging_pin_reserve(st, PIN_IN0, lay, &piece_in)) {
+            piece_in = bounce = (uint8_t *)malloc(lay);
+            if (!bounce) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
         }
         for (size_t b0 = 0; b0 < nblocks; b0 += per) {
             const size_t nb = nblocks - b0 < per ? nblocks - b0 : per;
-            for (size_t b = 0; b < nb; b++)
-                memcpy(piece_in + b * d_in_stride, in + (b0 + b) * in_stride, in_len_each ? in_len_each[b0 + b] : in_len);
-            HIP_TRY(lzs_hip_h2d((uint8_t *)d_in + b0 * d_in_stride, piece_in, nb * d_in_stride, stream), "hipMemcpy H2D");
-            HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+            lay_blocks_in(piece_in, d_in_stride, in, in_stride, in_len_each, in_len, b0, nb);
+            HIP_TRY_OR(done, lzs_hip_h2d((uint8_t *)d_in + b0 * d_in_stride, piece_in, nb * d_in_stride, stream), "hipMemcpy H2D");
+            HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
         }
-        free(bounce[0]); bounce[0] = NULL;
     }
-    if (in_len_each)
-        HIP_TRY(lzs_hip_h2d(d_in_len, in_len_each, sizeof(uint32_t) * nblocks, stream), "hipMemcpy H2D");
+done:
+    free(bounce);
+    return rc;
+}
 
-    STAGE("copy in");
-    /* A small batch of blocks to decompress does not fill the device with one wavefront per block
-     * (a wavefront takes 9 ms for a 64 KiB block, whatever the batch): then the blocks are cut
-     * into segments for many wavefronts, like one long stream. */
-    int segmented = 0;
-    if (launch == lzs_hip_launch_decompress && cap32 && !lzs_env()->one_wave) {
-        size_t total_in = 0;
-        for (size_t b = 0; b < nblocks; b++) total_in += in_len_each ? in_len_each[b] : in_len;
-        if (nblocks <= BATCH_SEG_MAX_BLOCKS && total_in >= STREAM_DEC_MIN && total_in / nblocks >= 1024u &&
-            (unsigned long long)nblocks * d_out_stride <= seg_extent &&
-            (unsigned long long)nblocks * d_in_stride < 0xF0000000ull) {      /* segment tables hold 32-bit input offsets */
-            rc = batch_decompress_segments(st, stream, who, d_out, d_out_stride, cap32, out_len, (uint32_t *)d_len, d_in, d_in_stride,
-                                           in_len_each, (uint32_t)in_len, nblocks);
-            if (rc != LZS_OK) goto done;
-            segmented = 1;
-        }
-    }
-    if (!segmented) {
-        HIP_TRY(launch(d_out, d_out_stride, cap32, (uint32_t *)d_len, d_in, d_in_stride,
-                       (const uint32_t *)d_in_len, (uint32_t)in_len, (uint32_t)nblocks, stream), who);
-        HIP_TRY(lzs_hip_d2h(out_len, d_len, sizeof(uint32_t) * nblocks, stream), "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-    }
-    STAGE("kernel + lengths");
-    /* copy back only what each block produced: nothing past out_len[b] is touched */
+/* copy back only what each block produced: nothing past out_len[b] is touched */
+static int copy_blocks_out(const char *who, staging_t *st, void *stream, uint8_t *out, size_t out_stride, const uint32_t *out_len,
+                           const void *d_out, size_t d_out_stride, const void *d_len, size_t nblocks)
+{
+    int e = 0, rc = LZS_OK;
+    uint8_t *bounce[2] = {NULL, NULL};
     if (nblocks < 16) {
         for (size_t b = 0; b < nblocks; b++)
-            HIP_TRY(lzs_hip_d2h(out + b * out_stride, (uint8_t *)d_out + b * d_out_stride, out_len[b], stream),
-                    "hipMemcpy D2H");
-        HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-    } else {
-        /* Thousands of small copies cost more than the data: the results are gathered into one
-         * dense string on the device, come back in pieces of 32 MiB, and are laid out by the CPU.
-         * (Full blocks at the device's own stride need neither: one copy.) */
-        size_t total = 0, full = 0;
-        for (size_t b = 0; b < nblocks; b++) { total += out_len[b]; full += (b + 1 < nblocks) && out_len[b] == out_stride; }
-        if (out_stride == d_out_stride && full == nblocks - 1) {
-            HIP_TRY(lzs_hip_d2h(out, d_out, total, stream), "hipMemcpy D2H");
-            HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-            goto done;
-        }
-        void *d_dense = NULL, *d_offs = NULL;
-        e = staging_reserve(st, BUF_KEEP, total + 64, &d_dense);
-        if (!e) e = staging_reserve(st, BUF_AUX, sizeof(uint64_t) * (nblocks + 1), &d_offs);
-        if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto done; }
-        HIP_TRY(lzs_hip_launch_compact(d_dense, (uint64_t *)d_offs, d_out, d_out_stride, (const uint32_t *)d_len,
-                                       (uint32_t)nblocks, stream), who);
-        const size_t piece = (size_t)32 << 20;
-        /* (pinned pieces of the thread, as on the way in) */
-        uint8_t *piece_out[2] = {NULL, NULL};
-        if (staging_pin_reserve(st, 2, total < piece ? total + 1 : piece, &piece_out[0]) ||
-            (total > piece && staging_pin_reserve(st, 3, piece, &piece_out[1]))) {
-            bounce[0] = (uint8_t *)malloc(total < piece ? total + 1 : piece);
-            bounce[1] = total > piece ? (uint8_t *)malloc(piece) : NULL;
-            if (!bounce[0] || (total > piece && !bounce[1])) { rc = fail(LZS_E_NOMEM, "%s: out of host memory", who); goto done; }
-            piece_out[0] = bounce[0]; piece_out[1] = bounce[1];
-        }
-        size_t b = 0, within = 0;                              /* next block to lay out, bytes of it already done */
-        for (size_t at = 0, k = 0; at < total || k == 0; k++) {
-            const size_t len = total - at < piece ? total - at : piece;
-            HIP_TRY(lzs_hip_d2h(piece_out[k & 1], (uint8_t *)d_dense + at, len, stream), "hipMemcpy D2H");
-            HIP_TRY(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-            const uint8_t *src = piece_out[k & 1];
-            size_t left = len;
-            while (left) {
-                while (b < nblocks && within == out_len[b]) { b++; within = 0; }
-                const size_t m = out_len[b] - within < left ? out_len[b] - within : left;
-                memcpy(out + b * out_stride + within, src, m);
-                src += m; left -= m; within += m;
-            }
-            at += len;
-            if (len == 0) break;
-        }
+            HIP_TRY_OR(done, lzs_hip_d2h(out + b * out_stride, (const uint8_t *)d_out + b * d_out_stride, out_len[b], stream), "hipMemcpy D2H");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        return rc;
     }
-    STAGE("copy out + layout");
-#undef HIP_TRY
-#undef STAGE
-
+    /* Thousands of small copies cost more than the data: the results are gathered into one
+     * dense string on the device, come back in pieces of 32 MiB, and are laid out by the CPU.
+     * (Full blocks at the device's own stride need neither: one copy.) */
+    size_t total = 0, full = 0;
+    for (size_t b = 0; b < nblocks; b++) { total += out_len[b]; full += (b + 1 < nblocks) && out_len[b] == out_stride; }
+    if (out_stride == d_out_stride && full == nblocks - 1) {
+        HIP_TRY_OR(done, lzs_hip_d2h(out, d_out, total, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        return rc;
+    }
+    void *d_dense = NULL, *d_offs = NULL;
+    e = staging_reserve(st, BUF_KEEP, total + 64, &d_dense);
+    if (!e) e = staging_reserve(st, BUF_AUX, sizeof(uint64_t) * (nblocks + 1), &d_offs);
+    if (e) return fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e));
+    HIP_TRY_OR(done, lzs_hip_launch_compact(d_dense, (uint64_t *)d_offs, d_out, d_out_stride, (const uint32_t *)d_len,
+                                            (uint32_t)nblocks, stream), who);
+    const size_t piece = (size_t)32 << 20;
+    /* (pinned pieces of the thread, as on the way in) */
+    uint8_t *piece_out[2] = {NULL, NULL};
+    if (staging_pin_reserve(st, PIN_OUT0, total < piece ? total + 1 : piece, &piece_out[0]) ||
+        (total > piece && staging_pin_reserve(st, PIN_OUT1, piece, &piece_out[1]))) {
+        piece_out[0] = bounce[0] = (uint8_t *)malloc(total < piece ? total + 1 : piece);
+        piece_out[1] = bounce[1] = total > piece ? (uint8_t *)malloc(piece) : NULL;
+        if (!bounce[0] || (total > piece && !bounce[1])) { rc = fail(LZS_E_NOMEM, "%s: out of host memory", who); goto done; }
+    }
+    size_t b = 0, within = 0;                              /* next block to lay out, bytes of it already done */
+    for (size_t at = 0, k = 0; at < total || k == 0; k++) {
+        const size_t len = total - at < piece ? total - at : piece;
+        HIP_TRY_OR(done, lzs_hip_d2h(piece_out[k & 1], (const uint8_t *)d_dense + at, len, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        const uint8_t *src = piece_out[k & 1];
+        size_t left = len;
+        while (left) {
+            while (b < nblocks && within == out_len[b]) { b++; within = 0; }
+            const size_t m = out_len[b] - within < left ? out_len[b] - within : left;
+            memcpy(out + b * out_stride + within, src, m);
+            src += m; left -= m; within += m;
+        }
+        at += len;
+        if (len == 0) break;
+    }
 done:
-    if (rc != LZS_OK && stream) lzs_hip_stream_sync(stream);   /* nothing of ours may still be in flight */
     free(bounce[0]); free(bounce[1]);
+    return rc;
+}
+
+static int host_batch(const char *who, launch_fn launch, uint8_t *out, size_t out_stride,
+                      size_t out_cap, uint32_t *out_len, const uint8_t *in, size_t in_stride,
+                      const uint32_t *in_len_each, size_t in_len, size_t nblocks)
+{
+    int rc = check_batch(who, out, out_cap, out_len, in, in_len, nblocks);
+    if (rc != LZS_OK || nblocks == 0) return rc;
+    const size_t total_in = batch_input(in_len_each, in_len, nblocks, &in_len);        /* (in_len: the longest block from here on) */
+    if (in_len > LZS_BLOCK_MAX) return fail(LZS_E_ARG, "%s: block exceeds LZS_BLOCK_MAX", who);
+    if ((rc = require_device()) != LZS_OK) return rc;
+
+    const uint32_t cap32 = clamp32(out_cap);
+    const size_t d_in_stride = round16(in_len ? in_len : 1), d_out_stride = round16(cap32 ? cap32 : 1);
+    const batch_route_t route = host_batch_route(launch, cap32, nblocks, d_in_stride, d_out_stride, total_in, lzs_env());
+    if (route == ROUTE_PIPELINE) {
+        int taken = 0;
+        rc = host_batch_pipelined(who, launch, out, out_stride, cap32, out_len, in, in_stride, in_len_each, in_len, nblocks, &taken);
+        if (taken || rc != LZS_OK) return rc;
+    }
+    staging_t *st = staging_get();
+    if (!st) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
+    void *d_in = NULL, *d_out = NULL, *d_len = NULL, *d_in_len = NULL;
+    int e = 0;
+    if (!st->stream) HIP_TRY_OR(done, lzs_hip_stream_create(&st->stream), "hipStreamCreate");
+    void *const stream = st->stream;
+    e = staging_reserve(st, BUF_IN, d_in_stride * nblocks, &d_in);
+    if (!e) e = staging_reserve(st, BUF_OUT, d_out_stride * nblocks, &d_out);
+    if (!e) e = staging_reserve(st, BUF_LEN, sizeof(uint32_t) * nblocks, &d_len);
+    if (!e && in_len_each) e = staging_reserve(st, BUF_INLEN, sizeof(uint32_t) * nblocks, &d_in_len);
+    if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto done; }
+
+    double t0 = lzs_env()->stream_debug ? now_ms() : 0;
+    if ((rc = copy_blocks_in(who, st, stream, d_in, d_in_stride, in, in_stride, in_len_each, in_len, nblocks)) != LZS_OK) goto done;
+    if (in_len_each) HIP_TRY_OR(done, lzs_hip_h2d(d_in_len, in_len_each, sizeof(uint32_t) * nblocks, stream), "hipMemcpy H2D");
+    stage_done(who, nblocks, stream, "copy in", &t0);
+    if (route == ROUTE_SEGMENTS) {
+        rc = batch_decompress_segments(st, stream, who, d_out, d_out_stride, cap32, out_len, (uint32_t *)d_len, d_in, d_in_stride,
+                                       in_len_each, (uint32_t)in_len, nblocks);
+        if (rc != LZS_OK) goto done;
+    } else {
+        HIP_TRY_OR(done, launch(d_out, d_out_stride, cap32, (uint32_t *)d_len, d_in, d_in_stride,
+                                (const uint32_t *)d_in_len, (uint32_t)in_len, (uint32_t)nblocks, stream), who);
+        HIP_TRY_OR(done, lzs_hip_d2h(out_len, d_len, sizeof(uint32_t) * nblocks, stream), "hipMemcpy D2H");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+    }
+    stage_done(who, nblocks, stream, "kernel + lengths", &t0);
+    if ((rc = copy_blocks_out(who, st, stream, out, out_stride, out_len, d_out, d_out_stride, d_len, nblocks)) != LZS_OK) goto done;
+    stage_done(who, nblocks, stream, "copy out + layout", &t0);
+done:
+    if (rc != LZS_OK && st->stream) lzs_hip_stream_sync(st->stream);   /* nothing of ours may still be in flight */
     staging_trim(st);
     return rc;
 }
@@ -632,6 +651,12 @@ static int small_call_on_host(const char *who, size_t n, size_t crossover)
     return 1;
 }
 
+/* this one-shot decompress goes by many wavefronts (lzs_stream.c) */
+static int by_many_wavefronts(const uint8_t *out, size_t cap, const uint8_t *in, size_t n)
+{
+    return (n > STREAM_DEC_MIN || (n && lzs_env()->force_stream)) && n <= LZS_BLOCK_MAX && out && in && cap && !lzs_env()->one_wave;
+}
+
 size_t lzs_compress(uint8_t *a_pOutData, size_t a_outBufferSize, const uint8_t *a_pInData, size_t a_inLen)
 {
     if ((a_pOutData || !a_outBufferSize) && (a_pInData || !a_inLen)) {
@@ -670,8 +695,7 @@ size_t lzs_decompress(uint8_t *a_pOutData, size_t a_outBufferSize, const uint8_t
         tls_error[0] = 0;
         return long_decompress(a_pOutData, a_outBufferSize, a_pInData, a_inLen);
     }
-    if ((a_inLen > STREAM_DEC_MIN || (a_inLen && lzs_env()->force_stream)) && a_inLen <= LZS_BLOCK_MAX &&
-        a_pOutData && a_pInData && a_outBufferSize && !lzs_env()->one_wave) {
+    if (by_many_wavefronts(a_pOutData, a_outBufferSize, a_pInData, a_inLen)) {
         const size_t got = stream_decompress(a_pOutData, a_outBufferSize, a_pInData, a_inLen, 0, NULL, 0, NULL);
         if (got != SIZE_MAX) return got;
     }
@@ -680,8 +704,7 @@ size_t lzs_decompress(uint8_t *a_pOutData, size_t a_outBufferSize, const uint8_t
 
 size_t lzs_decompress_concat(uint8_t *out, size_t out_cap, const uint8_t *in, size_t in_len)
 {
-    if ((in_len > STREAM_DEC_MIN || (in_len && lzs_env()->force_stream)) && in_len <= LZS_BLOCK_MAX &&
-        out && in && out_cap && !lzs_env()->one_wave) {
+    if (by_many_wavefronts(out, out_cap, in, in_len)) {
         const size_t got = stream_decompress(out, out_cap, in, in_len, 0, NULL, 1, NULL);
         if (got != SIZE_MAX) return got;
     }

@@ -1,6 +1,8 @@
 /*
  * lzs_internal.h -- what the host-side translation units of liblzs share (not installed).
- *   lzs_host.c         errors, device batches, per-thread staging, host batches, the one-shot calls
+ *   lzs_host.c         errors, device batches, per-thread staging, host batches (their route, and the one-after-the-other
+ *                      route: copy in, run, copy out), the one-shot calls
+ *   lzs_pipeline.c     large host batches with the three stages overlapped: the plan, the ring, a function per stage
  *   lzs_stream.c       one stream (or a small batch) spread over the device: segments + stitch,
  *                      scan / decode / resolve
  *   lzs_incremental.c  the reference's incremental interface on top of both
@@ -29,6 +31,9 @@ LZS_HIDDEN int require_device(void);
 /* A HIP call of the shim in a function with `int e, rc`: on an error its message is recorded, rc is the LZS_E_* code and the
  * function goes on at `label`. */
 #define HIP_TRY_OR(label, call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto label; } } while (0)
+/* ... in a function with NOTHING TO UNDO (the stages of lzs_pipeline.c: all they touch belongs to the run, which
+ * host_batch_pipelined() cleans up): it returns the LZS_E_* code at once.  A function that owns something takes HIP_TRY_OR. */
+#define HIP_TRY_RET(call, what) do { const int e_ = (call); if (e_) return hip_fail(e_, what); } while (0)
 
 /* The development switches of the environment (tools/README.md), read ONCE per process by lzs_env() -- the
  * entry points ask a struct, not getenv().  LZS_DEV_ENV=1 (set before the first call: the test suites do)
@@ -52,11 +57,14 @@ typedef struct {
 } lzs_env_t;
 LZS_HIDDEN const lzs_env_t *lzs_env(void);
 
-#define PIPE_STREAMS 12
-#define PIPE_EVENTS  24
+#define PIPE_STREAMS 4               /* copy in, copy out, two run streams (lzs_pipeline.c) */
+#define PIPE_EVENTS  14              /* lzs_pipeline.c: EV_COUNT */
 
 /* per-thread staging (lzs_host.c): one HIP stream and grow-only device buffers per host thread */
 enum { BUF_IN, BUF_OUT, BUF_LEN, BUF_INLEN, BUF_AUX, BUF_KEEP, BUF_MARKS, BUF_COUNT };
+/* the thread's pinned pieces: lzs_pipeline.c fills PIN_IN0 + (k & 1) and drains PIN_OUT0 + k % 3 for chunk k; the
+ * one-after-the-other route of host_batch() lays ragged blocks out in PIN_IN0 (in) and PIN_OUT0, PIN_OUT1 (out) */
+enum { PIN_IN0, PIN_IN1, PIN_OUT0, PIN_OUT1, PIN_OUT2, PIN_LENGTHS, PIN_COUNT };
 typedef struct {
     void  *stream;
     void  *buf[BUF_COUNT];
@@ -67,24 +75,41 @@ typedef struct {
     /* the overlapped host-buffer batches (lzs_pipeline.c): copy-in, two compute and copy-out streams, events, pinned pieces */
     void  *pipe_stream[PIPE_STREAMS];
     void  *pipe_event[PIPE_EVENTS];
-    void  *pin[6];
-    size_t pin_cap[6];
+    void  *pin[PIN_COUNT];
+    size_t pin_cap[PIN_COUNT];
     void  *hostcodec;               /* the host route's match-finder tables (lzs_hostcodec.c), made on first use */
 } staging_t;
 LZS_HIDDEN staging_t *staging_get(void);
 LZS_HIDDEN int staging_reserve(staging_t *st, int which, size_t bytes, void **out);   /* 0 or a hipError_t */
 LZS_HIDDEN void staging_trim(staging_t *st);
 LZS_HIDDEN void *staging_host_tables(staging_t *st, size_t bytes);   /* grow-only, pinned; NULL: out of memory */
-/* one of the thread's six pinned pieces (hipHostMallocNonCoherent: only the copy engines and the host touch them -- except
- * PIN_LENGTHS, which a kernel writes and which is coherent), grown to `bytes` if it is smaller; 0 or a HIP error.
- * lzs_pipeline.c: 0, 1 in, 2..4 out, 5 lengths; the one-after-the-other route of host_batch() lays ragged blocks out in
- * 0 (in) and 2, 3 (out). */
-#define PIN_LENGTHS 5
+/* one of the thread's pinned pieces (hipHostMallocNonCoherent: only the copy engines and the host touch them -- except
+ * PIN_LENGTHS, which a kernel writes and which is coherent), grown to `bytes` if it is smaller; 0 or a HIP error. */
 LZS_HIDDEN int staging_pin_reserve(staging_t *st, int which, size_t bytes, uint8_t **out);
 LZS_HIDDEN double now_ms(void);
 
-/* host-buffer batches with the three stages overlapped (lzs_pipeline.c); LZS_E_* or LZS_OK, *taken = 0: not this batch's route */
+/* ---- host-buffer batches (lzs_host.c, lzs_pipeline.c).  `launch` names the operation: lzs_hip_launch_compress or
+ * lzs_hip_launch_decompress (the one-shot calls also pass lzs_hip_launch_decompress_concat, one block). */
 typedef int (*launch_fn)(void *, size_t, uint32_t, uint32_t *, const void *, size_t, const uint32_t *, uint32_t, uint32_t, void *);
+static inline size_t round16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+/* blocks b0 .. b0 + nb - 1 of the caller's array laid out in `piece` at the device stride */
+static inline void lay_blocks_in(uint8_t *piece, size_t d_in_stride, const uint8_t *in, size_t in_stride, const uint32_t *in_len_each,
+                                 size_t in_len, size_t b0, size_t nb)
+{
+    for (size_t b = 0; b < nb; b++)
+        memcpy(piece + b * d_in_stride, in + (b0 + b) * in_stride, in_len_each ? in_len_each[b0 + b] : in_len);
+}
+/* The way a batch goes, decided from its sizes alone (no device, no staging): decompressed in segments by many wavefronts
+ * (lzs_stream.c), offered to the overlapped pipeline first -- pipe_plan() says whether that takes it --, or copied in, run and
+ * copied back one after the other.  The strides are those of the blocks in DEVICE memory. */
+typedef enum { ROUTE_SERIAL, ROUTE_SEGMENTS, ROUTE_PIPELINE } batch_route_t;
+LZS_HIDDEN batch_route_t host_batch_route(launch_fn launch, uint32_t cap32, size_t nblocks, size_t d_in_stride, size_t d_out_stride,
+                                          size_t total_in, const lzs_env_t *env);
+/* the overlapped route's plan: K chunks of `chunk` blocks, G chunks a launch, J launches, a ring of `slots` launches' worth of
+ * device memory, `threads` host threads; taken = 0: not this batch's route.  `in_len` is the longest block. */
+typedef struct { int taken, threads; size_t chunk, K, G, J, slots; } pipe_plan_t;
+LZS_HIDDEN pipe_plan_t pipe_plan(launch_fn launch, uint32_t cap32, size_t nblocks, size_t in_len, const lzs_env_t *env);
+/* LZS_E_* or LZS_OK, *taken = 0: not this batch's route */
 LZS_HIDDEN int host_batch_pipelined(const char *who, launch_fn launch, uint8_t *out, size_t out_stride, uint32_t cap32, uint32_t *out_len,
                                     const uint8_t *in, size_t in_stride, const uint32_t *in_len_each, size_t in_len, size_t nblocks,
                                     int *taken);

@@ -36,8 +36,6 @@
 #include "lzs_internal.h"
 
 #define PIPE_MAX_THREADS 8
-#define PIPE_IN(k)   ((k) & 1)
-#define PIPE_OUT(k)  (2 + (k) % 3)
 #define PIPE_RUN     2              /* run streams: with the two copy streams that is four streams, what the runtime gives
                                      * hardware queues of their own (with twelve streams a 46 MB copy-out stood in line
                                      * behind another stream's 9 ms kernel) */
@@ -54,16 +52,31 @@ enum { EV_IN = 0,                   /* [2] H2D of chunk k has left pinned piece 
        EV_OUT = 8,                  /* [3] D2H of chunk k is in pinned piece k % 3 */
        EV_OUTS = 11,                /* [PIPE_SLOTS] every chunk of launch j has been copied out of its dense piece */
        EV_COUNT = 14 };
+_Static_assert(2 + PIPE_RUN == PIPE_STREAMS && EV_COUNT == PIPE_EVENTS, "staging_t holds the pipeline's streams and events");
 
+/* one batch on its way through the pipeline */
 typedef struct {
-    /* the batch */
+    const char *who; launch_fn launch; staging_t *st; uint32_t cap32;
     uint8_t *out; size_t out_stride; uint32_t *out_len;
     const uint8_t *in; size_t in_stride; const uint32_t *in_len_each; size_t in_len;
-    size_t d_in_stride, nblocks, chunk;
-    /* this round's work: chunk numbers, or -1 */
+    pipe_plan_t pl;                                     /* chunk, K chunks, G a launch, J launches */
+    size_t nblocks, d_in_stride, d_out_stride;
+    size_t group, dense_piece, len_piece;               /* blocks per launch; bytes of a launch's dense piece and lengths */
+    /* device memory: a ring of PIPE_SLOTS launches' worth of blocks, slots, lengths and dense bytes; the pinned pieces */
+    void *d_in, *d_out, *d_len, *d_in_len, *d_dense, *d_offs;
+    uint8_t *pin_in[2], *pin_out[3], *pin_len;
+    uint64_t *doff[3];                                  /* where a chunk's blocks begin in its pinned piece (chunk + 1 entries) */
+    /* The four hands of the pipeline, each a counter of what it has done: chunks filled + copied in, launches queued,
+     * chunks whose copy out is queued, chunks drained. */
+    size_t n_fill, n_run, n_fin, n_drain, n_done;       /* (n_done: launches the host has seen finished) */
+    size_t j_known;                                     /* the launch whose lengths the host has read */
+    uint64_t chunk_at[PIPE_GROUP_MAX + 1];              /* of that launch: where its chunks begin in the dense piece */
+    int progressed;                                     /* this turn of the loop */
+    int debug, trace;                                   /* LZS_STREAM_DEBUG, LZS_PIPE_TRACE */
+    double t_copy, t_wait, t_queue, t_mark, t_all;
+    unsigned long rounds;
+    /* this round of host copies: chunk numbers, or -1 */
     long fill, drain;
-    uint8_t *pin_in, *pin_out;
-    const uint64_t *drain_off;      /* drain: offsets of the chunk's blocks in pin_out (chunk + 1 entries) */
     /* the workers */
     pthread_t th[PIPE_MAX_THREADS];
     int nth, started;
@@ -71,41 +84,43 @@ typedef struct {
     pthread_cond_t cv_work, cv_done;
     unsigned gen;
     int pending, quit;
-} pipe_t;
+} pipe_run_t;
 
 /* worker w's share of this round: its slice of the blocks to fill and of the blocks to drain */
-static void pipe_do_share(const pipe_t *p, int w)
+static void pipe_do_share(const pipe_run_t *p, int w)
 {
     if (p->fill >= 0) {
-        const size_t b0 = (size_t)p->fill * p->chunk;
-        const size_t nb = p->nblocks - b0 < p->chunk ? p->nblocks - b0 : p->chunk;
+        const size_t b0 = (size_t)p->fill * p->pl.chunk;
+        const size_t nb = p->nblocks - b0 < p->pl.chunk ? p->nblocks - b0 : p->pl.chunk;
         const size_t lo = nb * (size_t)w / (size_t)p->nth, hi = nb * (size_t)(w + 1) / (size_t)p->nth;
         if (!p->in_len_each && p->in_stride == p->d_in_stride) {
             /* contiguous blocks of the device's own stride: one copy (the last block of the batch may be short of its stride) */
             if (hi > lo) {
                 const size_t bytes = (hi - lo - 1) * p->d_in_stride + (b0 + hi == p->nblocks ? p->in_len : p->d_in_stride);
-                memcpy(p->pin_in + lo * p->d_in_stride, p->in + (b0 + lo) * p->in_stride, bytes);
+                memcpy(p->pin_in[p->fill & 1] + lo * p->d_in_stride, p->in + (b0 + lo) * p->in_stride, bytes);
             }
         } else {
-            for (size_t b = lo; b < hi; b++)
-                memcpy(p->pin_in + b * p->d_in_stride, p->in + (b0 + b) * p->in_stride, p->in_len_each ? p->in_len_each[b0 + b] : p->in_len);
+            lay_blocks_in(p->pin_in[p->fill & 1] + lo * p->d_in_stride, p->d_in_stride, p->in, p->in_stride, p->in_len_each, p->in_len,
+                          b0 + lo, hi - lo);
         }
     }
     if (p->drain >= 0) {
-        const size_t b0 = (size_t)p->drain * p->chunk;
-        const size_t nb = p->nblocks - b0 < p->chunk ? p->nblocks - b0 : p->chunk;
+        const size_t b0 = (size_t)p->drain * p->pl.chunk;
+        const size_t nb = p->nblocks - b0 < p->pl.chunk ? p->nblocks - b0 : p->pl.chunk;
         const size_t lo = nb * (size_t)w / (size_t)p->nth, hi = nb * (size_t)(w + 1) / (size_t)p->nth;
+        const uint8_t *const piece = p->pin_out[p->drain % 3];
+        const uint64_t *const off = p->doff[p->drain % 3];
         for (size_t b = lo; b < hi; b++)
-            memcpy(p->out + (b0 + b) * p->out_stride, p->pin_out + p->drain_off[b], p->out_len[b0 + b]);
+            memcpy(p->out + (b0 + b) * p->out_stride, piece + off[b], p->out_len[b0 + b]);
     }
 }
 
-typedef struct { pipe_t *p; int w; } pipe_arg_t;
+typedef struct { pipe_run_t *p; int w; } pipe_arg_t;
 
 static void *pipe_worker(void *argp)
 {
     pipe_arg_t *a = (pipe_arg_t *)argp;
-    pipe_t *p = a->p;
+    pipe_run_t *p = a->p;
     const int w = a->w;
     unsigned seen = 0;
     pthread_mutex_lock(&p->mu);
@@ -123,7 +138,7 @@ static void *pipe_worker(void *argp)
 }
 
 /* one round of host copies on all workers; the calling thread takes share 0 itself */
-static void pipe_round(pipe_t *p)
+static void pipe_round(pipe_run_t *p)
 {
     if (p->fill < 0 && p->drain < 0) return;
     pthread_mutex_lock(&p->mu);
@@ -137,17 +152,12 @@ static void pipe_round(pipe_t *p)
     pthread_mutex_unlock(&p->mu);
 }
 
-static size_t round16(size_t v) { return (v + 15u) & ~(size_t)15u; }
-
-LZS_HIDDEN int host_batch_pipelined(const char *who, launch_fn launch, uint8_t *out, size_t out_stride, uint32_t cap32, uint32_t *out_len,
-                                    const uint8_t *in, size_t in_stride, const uint32_t *in_len_each, size_t in_len, size_t nblocks,
-                                    int *taken)
+/* The plan: chunks of about 45 MiB of the wider side (640 blocks of 64 KiB), at least 64 blocks; worth it from four chunks on. */
+LZS_HIDDEN pipe_plan_t pipe_plan(launch_fn launch, uint32_t cap32, size_t nblocks, size_t in_len, const lzs_env_t *env)
 {
-    *taken = 0;
-    const lzs_env_t *env = lzs_env();
+    pipe_plan_t pl = { 0, 0, 0, 0, 0, 0, 0 };
     const size_t d_in_stride = round16(in_len ? in_len : 1), d_out_stride = round16(cap32 ? cap32 : 1);
     const size_t widest = d_in_stride > d_out_stride ? d_in_stride : d_out_stride;
-    /* chunks of about 45 MiB of the wider side (640 blocks of 64 KiB), at least 64 blocks; worth it from four chunks on */
     size_t chunk = ((size_t)(env->pipe_chunk_mb > 0 ? env->pipe_chunk_mb : 46) << 20) / widest;
     chunk = chunk < 64 ? 64 : chunk & ~(size_t)63;
     /* From 24 MiB on (batches of streams up to 64 MiB of output are decompressed in segments before this is asked:
@@ -156,236 +166,267 @@ LZS_HIDDEN int host_batch_pipelined(const char *who, launch_fn launch, uint8_t *
      * 512: 2.7 -> 2.2, equal at 256: profiles/r04/hostbatch_small_routes.txt). */
     const unsigned long long least = (unsigned long long)(env->pipe_min_mb > 0 ? env->pipe_min_mb : PIPE_MIN_MB) << 20;
     if (env->overlap_off || !cap32 || nblocks < PIPE_MIN_BLOCKS || (unsigned long long)nblocks * widest < least ||
-        widest > ((size_t)4 << 20)) return LZS_OK;
+        widest > ((size_t)4 << 20)) return pl;
     if (nblocks < 4 * chunk) chunk = ((nblocks + 3) / 4 + 63) & ~(size_t)63;
-    const size_t K = (nblocks + chunk - 1) / chunk;
-    size_t G = env->pipe_group > 0 && env->pipe_group <= PIPE_GROUP_MAX ? (size_t)env->pipe_group
-             : launch == lzs_hip_launch_compress ? 2 : 8;                  /* chunks per launch ... */
-    if (G > K) G = K;                                                       /* ... of the chunks there are (a 1024-block
+    pl.chunk = chunk;
+    pl.K = (nblocks + chunk - 1) / chunk;
+    pl.G = env->pipe_group > 0 && env->pipe_group <= PIPE_GROUP_MAX ? (size_t)env->pipe_group
+         : launch == lzs_hip_launch_compress ? 2 : 8;                      /* chunks per launch ... */
+    if (pl.G > pl.K) pl.G = pl.K;                                           /* ... of the chunks there are (a 1024-block
                                                                              * decompress batch is ONE launch of four chunks, not a ring
                                                                              * of three launches of eight) */
-    const size_t J = (K + G - 1) / G;                                       /* launches */
-    const size_t slots = J < PIPE_SLOTS ? J : PIPE_SLOTS;                   /* launches' worth of device memory in the ring */
-    if ((unsigned long long)G * chunk * d_out_stride > 0xF0000000ull) return LZS_OK;
+    pl.J = (pl.K + pl.G - 1) / pl.G;                                        /* launches */
+    pl.slots = pl.J < PIPE_SLOTS ? pl.J : PIPE_SLOTS;                       /* launches' worth of device memory in the ring */
+    pl.threads = env->copy_threads > 0 ? env->copy_threads : 4;
+    if (pl.threads > PIPE_MAX_THREADS) pl.threads = PIPE_MAX_THREADS;
+    pl.taken = (unsigned long long)pl.G * chunk * d_out_stride <= 0xF0000000ull;
+    return pl;
+}
+
+enum { S_IN, S_OUT, S_RUN };        /* streams: copy in, copy out, PIPE_RUN run streams in turn */
+static void *pipe_stream(const pipe_run_t *R, int which, size_t j)
+{
+    return R->st->pipe_stream[which + (which == S_RUN ? j % PIPE_RUN : 0)];
+}
+static void *pipe_event(const pipe_run_t *R, int group, size_t i) { return R->st->pipe_event[group + i % (group == EV_IN ? 2 : 3)]; }
+
+#define TRACE(R, ...) do { if ((R)->trace) { fprintf(stderr, "  %8.2f ms  ", now_ms() - (R)->t_all); fprintf(stderr, __VA_ARGS__); \
+                                             fputc('\n', stderr); } } while (0)
+static void mark(pipe_run_t *R) { R->t_mark = R->debug ? now_ms() : 0; }
+static void since(pipe_run_t *R, double *acc) { if (R->debug) { const double n = now_ms(); *acc += n - R->t_mark; R->t_mark = n; } }
+static size_t at_most(size_t a, size_t b) { return a < b ? a : b; }
+
+/* ---- launches whose chunks are all on their way in, and whose dense piece and length slot are free again
+ * (launch j - PIPE_RUN used them: all its chunks must have been handed to the copy-out stream) */
+static int pipe_queue_launches(pipe_run_t *R)
+{
+    const size_t G = R->pl.G, K = R->pl.K, group = R->group;
+    while (R->n_run < R->pl.J && R->n_fill >= at_most((R->n_run + 1) * G, K) &&
+           (R->n_run < PIPE_SLOTS || R->n_fin >= at_most((R->n_run - PIPE_SLOTS + 1) * G, K))) {
+        const size_t j = R->n_run, q = j % PIPE_SLOTS, b0 = j * group, nb = at_most(R->nblocks - b0, group);
+        uint8_t *const dense = (uint8_t *)R->d_dense + q * R->dense_piece;
+        uint64_t *const offs = (uint64_t *)R->d_offs + q * (group + 1);
+        uint8_t *const lens = R->pin_len + q * R->len_piece;
+        uint8_t *const c_in = (uint8_t *)R->d_in + q * group * R->d_in_stride, *const c_out = (uint8_t *)R->d_out + q * group * R->d_out_stride;
+        uint32_t *const c_len = (uint32_t *)R->d_len + q * group;
+        void *const run = pipe_stream(R, S_RUN, j);
+        HIP_TRY_RET(lzs_hip_stream_wait_event(run, pipe_event(R, EV_INS, j)), "hipStreamWaitEvent");
+        HIP_TRY_RET(R->launch(c_out, R->d_out_stride, R->cap32, c_len, c_in, R->d_in_stride,
+                              R->d_in_len ? (const uint32_t *)R->d_in_len + b0 : NULL, (uint32_t)R->in_len, (uint32_t)nb, run), R->who);
+        if (j >= PIPE_SLOTS)                                             /* (the dense piece is read out) */
+            HIP_TRY_RET(lzs_hip_stream_wait_event(run, pipe_event(R, EV_OUTS, j)), "hipStreamWaitEvent");
+        HIP_TRY_RET(lzs_hip_launch_compact(dense, offs, c_out, R->d_out_stride, c_len, (uint32_t)nb, run), R->who);
+        /* (the lengths and the byte total reach the host by a kernel, not by a copy engine: see lzs_hip_words_to_host) */
+        HIP_TRY_RET(lzs_hip_words_to_host((uint32_t *)lens, c_len, nb, run), R->who);
+        HIP_TRY_RET(lzs_hip_words_to_host((uint32_t *)(lens + sizeof(uint32_t) * group), (const uint32_t *)(offs + nb), 2, run), R->who);
+        HIP_TRY_RET(lzs_hip_event_record(pipe_event(R, EV_RUN, j), run), "hipEventRecord");
+        TRACE(R, "launch %zu queued (%zu blocks)", j, nb);
+        R->n_run++;
+        R->progressed = 1;
+    }
+    return LZS_OK;
+}
+
+/* Launch j is through (*ready) or not yet: its lengths, and where each of its chunks begins in the dense piece */
+static int pipe_read_lengths(pipe_run_t *R, size_t j, int *ready)
+{
+    *ready = lzs_hip_event_done(pipe_event(R, EV_RUN, j));
+    if (*ready < 0) return hip_fail(-*ready, "hipEventQuery");
+    if (!*ready) return LZS_OK;
+    const size_t group = R->group, chunk = R->pl.chunk, g0 = j * group, gn = at_most(R->nblocks - g0, group);
+    const uint8_t *const lp = R->pin_len + (j % PIPE_SLOTS) * R->len_piece;
+    const uint32_t *lens = (const uint32_t *)lp;
+    uint64_t total = 0, at = 0;
+    memcpy(&total, lp + sizeof(uint32_t) * group, sizeof total);
+    for (size_t b = 0; b < gn; b++) {
+        if (b % chunk == 0) R->chunk_at[b / chunk] = at;
+        R->out_len[g0 + b] = lens[b];
+        at += lens[b];
+    }
+    R->chunk_at[(gn + chunk - 1) / chunk] = at;
+    if (at != total || total > (uint64_t)group * R->d_out_stride)
+        return fail(LZS_E_HIP, "%s: inconsistent lengths from the device (launch %zu: %llu bytes by the lengths, %llu by the offsets)",
+                    R->who, j, (unsigned long long)at, (unsigned long long)total);
+    R->j_known = j;
+    R->n_done = j + 1;
+    TRACE(R, "launch %zu seen finished", j);
+    return LZS_OK;
+}
+
+/* ---- chunks of a finished launch: exactly their bytes to a free pinned piece (three: one being drained, one
+ * being copied into, one waiting) */
+static int pipe_queue_copy_outs(pipe_run_t *R)
+{
+    const size_t G = R->pl.G, K = R->pl.K, chunk = R->pl.chunk;
+    while (R->n_fin < K && R->n_fin / G < R->n_run && R->n_fin - R->n_drain < 3) {
+        const size_t k = R->n_fin, j = k / G, b0 = k * chunk, nb = at_most(R->nblocks - b0, chunk);
+        if (j != R->j_known) {
+            int ready = 0;
+            const int rc = pipe_read_lengths(R, j, &ready);
+            if (rc != LZS_OK) return rc;
+            if (!ready) break;
+        }
+        const size_t c = k - j * G;                 /* the chunk's number inside its launch */
+        uint64_t *o = R->doff[k % 3], at = 0;
+        for (size_t b = 0; b < nb; b++) { o[b] = at; at += R->out_len[b0 + b]; }
+        o[nb] = at;
+        HIP_TRY_RET(lzs_hip_d2h(R->pin_out[k % 3], (const uint8_t *)R->d_dense + (j % PIPE_SLOTS) * R->dense_piece + R->chunk_at[c],
+                                (size_t)(R->chunk_at[c + 1] - R->chunk_at[c]), pipe_stream(R, S_OUT, 0)), "hipMemcpy D2H");
+        HIP_TRY_RET(lzs_hip_event_record(pipe_event(R, EV_OUT, k), pipe_stream(R, S_OUT, 0)), "hipEventRecord");
+        if (c + 1 == G || k + 1 == K) HIP_TRY_RET(lzs_hip_event_record(pipe_event(R, EV_OUTS, j), pipe_stream(R, S_OUT, 0)), "hipEventRecord");
+        TRACE(R, "chunk %zu: copy out queued (%llu bytes)", k, (unsigned long long)(R->chunk_at[c + 1] - R->chunk_at[c]));
+        R->n_fin++;
+        R->progressed = 1;
+    }
+    return LZS_OK;
+}
+
+/* (a chunk goes where launch j - PIPE_SLOTS read its blocks from: that launch must be through) */
+static int pipe_can_fill(const pipe_run_t *R)
+{
+    return R->n_fill < R->pl.K && (R->n_fill / R->pl.G < PIPE_SLOTS || R->n_done + PIPE_SLOTS > R->n_fill / R->pl.G);
+}
+
+/* ---- the host threads: the next chunk in (its pinned piece is free once the copy before last has left it), and
+ * the oldest chunk whose bytes have arrived out; then the chunk's copy to the device */
+static int pipe_host_round(pipe_run_t *R)
+{
+    int do_fill = pipe_can_fill(R), do_drain = 0;
+    if (do_fill && R->n_fill >= 2) {
+        const int ready = lzs_hip_event_done(pipe_event(R, EV_IN, R->n_fill));
+        if (ready < 0) return hip_fail(-ready, "hipEventQuery");
+        do_fill = ready;
+    }
+    if (R->n_drain < R->n_fin) {
+        const int ready = lzs_hip_event_done(pipe_event(R, EV_OUT, R->n_drain));
+        if (ready < 0) return hip_fail(-ready, "hipEventQuery");
+        do_drain = ready;
+    }
+    if (!do_fill && !do_drain) return LZS_OK;
+    R->fill = do_fill ? (long)R->n_fill : -1;
+    R->drain = do_drain ? (long)R->n_drain : -1;
+    pipe_round(R);
+    since(R, &R->t_copy);
+    R->rounds++;
+    TRACE(R, "host copies done: fill %ld, drain %ld", R->fill, R->drain);
+    if (do_fill) {
+        const size_t G = R->pl.G, k = R->n_fill, b0 = k * R->pl.chunk, nb = at_most(R->nblocks - b0, R->pl.chunk);
+        uint8_t *const to = (uint8_t *)R->d_in + (((k / G) % PIPE_SLOTS) * R->group + (k % G) * R->pl.chunk) * R->d_in_stride;
+        HIP_TRY_RET(lzs_hip_h2d(to, R->pin_in[k & 1], nb * R->d_in_stride, pipe_stream(R, S_IN, 0)), "hipMemcpy H2D");
+        HIP_TRY_RET(lzs_hip_event_record(pipe_event(R, EV_IN, k), pipe_stream(R, S_IN, 0)), "hipEventRecord");
+        if ((k + 1) % G == 0 || k + 1 == R->pl.K)
+            HIP_TRY_RET(lzs_hip_event_record(pipe_event(R, EV_INS, k / G), pipe_stream(R, S_IN, 0)), "hipEventRecord");
+        R->n_fill++;
+    }
+    if (do_drain) R->n_drain++;
+    since(R, &R->t_queue);
+    R->progressed = 1;
+    return LZS_OK;
+}
+
+/* nothing is ready: wait for what the pipeline needs next -- the copy out that is under way, else the
+ * launch that is on the device; but first of all the copy in whose pinned piece the next chunk wants */
+static int pipe_wait(pipe_run_t *R)
+{
+    void *ev;
+    if (pipe_can_fill(R)) ev = pipe_event(R, EV_IN, R->n_fill);                                     /* (the shortest wait first) */
+    else if (R->n_drain < R->n_fin) ev = pipe_event(R, EV_OUT, R->n_drain);
+    else if (R->n_fin < R->pl.K && R->n_fin / R->pl.G < R->n_run) ev = pipe_event(R, EV_RUN, R->n_fin / R->pl.G);
+    else return fail(LZS_E_HIP, "%s: the pipeline has nothing to wait for (filled %zu, launched %zu, copied out %zu, drained %zu of %zu)",
+                     R->who, R->n_fill, R->n_run, R->n_fin, R->n_drain, R->pl.K);
+    HIP_TRY_RET(lzs_hip_event_sync(ev), "hipEventSynchronize");
+    since(R, &R->t_wait);
+    return LZS_OK;
+}
+
+/* the ring on the device, the pinned pieces, the offset tables (sizes that stay with the thread between calls: no allocation
+ * per call); 0, or no room */
+static int pipe_reserve(pipe_run_t *R, size_t slots)
+{
+    staging_t *st = R->st;
+    const size_t group = R->group, nblocks = R->nblocks;
+    int e = staging_reserve(st, BUF_IN, slots * group * R->d_in_stride, &R->d_in);
+    if (!e) e = staging_reserve(st, BUF_OUT, slots * group * R->d_out_stride, &R->d_out);
+    if (!e) e = staging_reserve(st, BUF_LEN, slots * sizeof(uint32_t) * group, &R->d_len);
+    if (!e && R->in_len_each) e = staging_reserve(st, BUF_INLEN, sizeof(uint32_t) * nblocks, &R->d_in_len);
+    if (!e) e = staging_reserve(st, BUF_KEEP, slots * R->dense_piece + 64, &R->d_dense);
+    if (!e) e = staging_reserve(st, BUF_AUX, slots * sizeof(uint64_t) * (group + 1), &R->d_offs);
+    for (int i = 0; i < 2 && !e; i++) e = staging_pin_reserve(st, PIN_IN0 + i, R->pl.chunk * R->d_in_stride, &R->pin_in[i]);
+    for (int i = 0; i < 3 && !e; i++) e = staging_pin_reserve(st, PIN_OUT0 + i, R->pl.chunk * R->d_out_stride, &R->pin_out[i]);
+    if (!e) e = staging_pin_reserve(st, PIN_LENGTHS, slots * R->len_piece, &R->pin_len);
+    /* (The runtime keeps a failed allocation as its "last error" until somebody fetches it, and every launcher returns the
+     * last error after its launch: fetch it here, or the route that is to save the call reports this out-of-memory as its
+     * own -- ADVICE r04) */
+    if (e) { lzs_hip_clear_error(); return e; }
+    for (int i = 0; i < 3; i++) R->doff[i] = (uint64_t *)malloc(sizeof(uint64_t) * (R->pl.chunk + 1));
+    return !R->doff[0] || !R->doff[1] || !R->doff[2];
+}
+
+LZS_HIDDEN int host_batch_pipelined(const char *who, launch_fn launch, uint8_t *out, size_t out_stride, uint32_t cap32, uint32_t *out_len,
+                                    const uint8_t *in, size_t in_stride, const uint32_t *in_len_each, size_t in_len, size_t nblocks,
+                                    int *taken)
+{
+    const lzs_env_t *env = lzs_env();
+    const pipe_plan_t pl = pipe_plan(launch, cap32, nblocks, in_len, env);
+    *taken = 0;
+    if (!pl.taken) return LZS_OK;
     staging_t *st = staging_get();
     if (!st) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
     *taken = 1;
 
     int rc = LZS_OK, e = 0;
-    pipe_t P;
     pipe_arg_t args[PIPE_MAX_THREADS];
-    uint64_t *doff[3] = {NULL, NULL, NULL};
-    memset(&P, 0, sizeof P);
-    P.out = out; P.out_stride = out_stride; P.out_len = out_len;
-    P.in = in; P.in_stride = in_stride; P.in_len_each = in_len_each; P.in_len = in_len;
-    P.d_in_stride = d_in_stride; P.nblocks = nblocks; P.chunk = chunk;
-    P.fill = P.drain = -1;
-    P.nth = env->copy_threads > 0 ? env->copy_threads : 4;
-    if (P.nth > PIPE_MAX_THREADS) P.nth = PIPE_MAX_THREADS;
-    pthread_mutex_init(&P.mu, NULL);
-    pthread_cond_init(&P.cv_work, NULL);
-    pthread_cond_init(&P.cv_done, NULL);
-
-#define HIP_TRY(call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto done; } } while (0)
-    for (size_t i = 0; i < 2 + PIPE_RUN; i++)
-        if (!st->pipe_stream[i]) HIP_TRY(lzs_hip_stream_create(&st->pipe_stream[i]), "hipStreamCreate");
-    for (size_t i = 0; i < EV_COUNT; i++)
-        if (!st->pipe_event[i]) HIP_TRY(lzs_hip_event_create(&st->pipe_event[i]), "hipEventCreate");
-    void *const s_in = st->pipe_stream[0], *const s_out = st->pipe_stream[1];
-    void **const ev = st->pipe_event;
-#define S_RUN(j)   (st->pipe_stream[2 + (j) % PIPE_RUN])
-#define E_IN(k)    (ev[EV_IN + ((k) & 1)])
-#define E_INS(j)   (ev[EV_INS + (j) % PIPE_SLOTS])
-#define E_RUN(j)   (ev[EV_RUN + (j) % PIPE_SLOTS])
-#define E_OUT(k)   (ev[EV_OUT + (k) % 3])
-#define E_OUTS(j)  (ev[EV_OUTS + (j) % PIPE_SLOTS])
-
-    /* device memory: a ring of PIPE_SLOTS launches' worth of blocks, slots, lengths and dense bytes (sizes that stay with
-     * the thread between calls: no allocation per call) */
-    void *d_in = NULL, *d_out = NULL, *d_len = NULL, *d_in_len = NULL, *d_dense = NULL, *d_offs = NULL;
-    const size_t group = G * chunk;                                         /* blocks per launch */
-    const size_t dense_piece = group * d_out_stride + 32;
-    e = staging_reserve(st, BUF_IN, slots * group * d_in_stride, &d_in);
-    if (!e) e = staging_reserve(st, BUF_OUT, slots * group * d_out_stride, &d_out);
-    if (!e) e = staging_reserve(st, BUF_LEN, slots * sizeof(uint32_t) * group, &d_len);
-    if (!e && in_len_each) e = staging_reserve(st, BUF_INLEN, sizeof(uint32_t) * nblocks, &d_in_len);
-    if (!e) e = staging_reserve(st, BUF_KEEP, slots * dense_piece + 64, &d_dense);
-    if (!e) e = staging_reserve(st, BUF_AUX, slots * sizeof(uint64_t) * (group + 1), &d_offs);
+    pipe_run_t run, *const R = &run;
+    memset(R, 0, sizeof *R);
+    R->who = who; R->launch = launch; R->st = st; R->cap32 = cap32; R->nblocks = nblocks;
+    R->out = out; R->out_stride = out_stride; R->out_len = out_len;
+    R->in = in; R->in_stride = in_stride; R->in_len_each = in_len_each; R->in_len = in_len;
+    R->pl = pl; R->group = pl.G * pl.chunk;
+    R->d_in_stride = round16(in_len ? in_len : 1); R->d_out_stride = round16(cap32 ? cap32 : 1);
+    R->dense_piece = R->group * R->d_out_stride + 32; R->len_piece = sizeof(uint32_t) * R->group + sizeof(uint64_t);
+    R->j_known = (size_t)-1; R->fill = R->drain = -1; R->nth = pl.threads;
+    pthread_mutex_init(&R->mu, NULL); pthread_cond_init(&R->cv_work, NULL); pthread_cond_init(&R->cv_done, NULL);
+    for (size_t i = 0; i < PIPE_STREAMS; i++)
+        if (!st->pipe_stream[i]) HIP_TRY_OR(done, lzs_hip_stream_create(&st->pipe_stream[i]), "hipStreamCreate");
+    for (size_t i = 0; i < PIPE_EVENTS; i++)
+        if (!st->pipe_event[i]) HIP_TRY_OR(done, lzs_hip_event_create(&st->pipe_event[i]), "hipEventCreate");
     /* (no room for the ring or the pinned pieces -- a small cgroup, many threads at once: nothing has been queued yet, the
-     * batch takes the one-after-the-other route, which needs neither.  The runtime keeps a failed allocation as its "last
-     * error" until somebody fetches it, and every launcher returns the last error after its launch: fetch it here, or the
-     * route that is to save the call reports this out-of-memory as its own -- ADVICE r04) */
-    if (e) { lzs_hip_clear_error(); *taken = 0; goto done; }
-    uint8_t *pin_in[2], *pin_out[3], *pin_len = NULL;
-    const size_t len_piece = sizeof(uint32_t) * group + sizeof(uint64_t);
-    for (int i = 0; i < 2 && !e; i++) e = staging_pin_reserve(st, PIPE_IN(i), chunk * d_in_stride, &pin_in[i]);
-    for (int i = 0; i < 3 && !e; i++) e = staging_pin_reserve(st, PIPE_OUT(i), chunk * d_out_stride, &pin_out[i]);
-    if (!e) e = staging_pin_reserve(st, PIN_LENGTHS, slots * len_piece, &pin_len);
-    if (e) { lzs_hip_clear_error(); *taken = 0; goto done; }
-    for (int i = 0; i < 3; i++) doff[i] = (uint64_t *)malloc(sizeof(uint64_t) * (chunk + 1));
-    if (!doff[0] || !doff[1] || !doff[2]) { *taken = 0; goto done; }
+     * batch takes the one-after-the-other route, which needs neither) */
+    if (pipe_reserve(R, pl.slots)) { *taken = 0; goto done; }
 
-    for (int w = 1; w < P.nth; w++) {
-        args[w].p = &P; args[w].w = w;
-        if (pthread_create(&P.th[w], NULL, pipe_worker, &args[w]) != 0) { P.nth = w; break; }
-        P.started++;
+    for (int w = 1; w < R->nth; w++) {
+        args[w].p = R; args[w].w = w;
+        if (pthread_create(&R->th[w], NULL, pipe_worker, &args[w]) != 0) { R->nth = w; break; }
+        R->started++;
     }
     if (in_len_each) {
-        HIP_TRY(lzs_hip_h2d(d_in_len, in_len_each, sizeof(uint32_t) * nblocks, s_in), "hipMemcpy H2D");
-        HIP_TRY(lzs_hip_stream_sync(s_in), "hipStreamSynchronize");
+        HIP_TRY_OR(done, lzs_hip_h2d(R->d_in_len, in_len_each, sizeof(uint32_t) * nblocks, pipe_stream(R, S_IN, 0)), "hipMemcpy H2D");
+        HIP_TRY_OR(done, lzs_hip_stream_sync(pipe_stream(R, S_IN, 0)), "hipStreamSynchronize");
     }
-
-    const int debug = env->stream_debug, trace = env->stream_debug && env->pipe_trace;
-#define TRACE(...) do { if (trace) { fprintf(stderr, "  %8.2f ms  ", now_ms() - t_all); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } } while (0)
-    double t_copy = 0, t_wait = 0, t_queue = 0, t_mark = 0, t_all = debug ? now_ms() : 0;
-#define MARK() (t_mark = debug ? now_ms() : 0)
-#define SINCE(acc) do { if (debug) { const double n_ = now_ms(); acc += n_ - t_mark; t_mark = n_; } } while (0)
-    /* The four hands of the pipeline, each a counter of what it has done: chunks filled + copied in, launches queued,
-     * chunks whose copy out is queued, chunks drained. */
-    size_t n_fill = 0, n_run = 0, n_fin = 0, n_drain = 0, n_done = 0;       /* (n_done: launches the host has seen finished) */
-    size_t j_known = (size_t)-1;                        /* the launch whose lengths the host has read */
-    uint64_t chunk_at[PIPE_GROUP_MAX + 1];              /* of that launch: where its chunks begin in the dense piece */
-    unsigned long rounds = 0;
-    while (n_drain < K) {
-        int progressed = 0;
-        MARK();
-        /* ---- launches whose chunks are all on their way in, and whose dense piece and length slot are free again
-         * (launch j - PIPE_RUN used them: all its chunks must have been handed to the copy-out stream) */
-        while (n_run < J && n_fill >= ((n_run + 1) * G < K ? (n_run + 1) * G : K) &&
-               (n_run < PIPE_SLOTS || n_fin >= ((n_run - PIPE_SLOTS + 1) * G < K ? (n_run - PIPE_SLOTS + 1) * G : K))) {
-            const size_t j = n_run, q = j % PIPE_SLOTS, b0 = j * group, nb = nblocks - b0 < group ? nblocks - b0 : group;
-            uint8_t *const dense = (uint8_t *)d_dense + q * dense_piece;
-            uint64_t *const offs = (uint64_t *)d_offs + q * (group + 1);
-            uint8_t *const lens = pin_len + q * len_piece;
-            uint8_t *const c_in = (uint8_t *)d_in + q * group * d_in_stride, *const c_out = (uint8_t *)d_out + q * group * d_out_stride;
-            uint32_t *const c_len = (uint32_t *)d_len + q * group;
-            HIP_TRY(lzs_hip_stream_wait_event(S_RUN(j), E_INS(j)), "hipStreamWaitEvent");
-            HIP_TRY(launch(c_out, d_out_stride, cap32, c_len, c_in, d_in_stride,
-                           d_in_len ? (const uint32_t *)d_in_len + b0 : NULL, (uint32_t)in_len, (uint32_t)nb, S_RUN(j)), who);
-            if (j >= PIPE_SLOTS) HIP_TRY(lzs_hip_stream_wait_event(S_RUN(j), E_OUTS(j)), "hipStreamWaitEvent");   /* (the dense piece is read out) */
-            HIP_TRY(lzs_hip_launch_compact(dense, offs, c_out, d_out_stride, c_len, (uint32_t)nb, S_RUN(j)), who);
-            /* (the lengths and the byte total reach the host by a kernel, not by a copy engine: see lzs_hip_words_to_host) */
-            HIP_TRY(lzs_hip_words_to_host((uint32_t *)lens, c_len, nb, S_RUN(j)), who);
-            HIP_TRY(lzs_hip_words_to_host((uint32_t *)(lens + sizeof(uint32_t) * group), (const uint32_t *)(offs + nb), 2, S_RUN(j)), who);
-            HIP_TRY(lzs_hip_event_record(E_RUN(j), S_RUN(j)), "hipEventRecord");
-            TRACE("launch %zu queued (%zu blocks)", j, nb);
-            n_run++;
-            progressed = 1;
-        }
-        /* ---- chunks of a finished launch: exactly their bytes to a free pinned piece (three: one being drained, one
-         * being copied into, one waiting) */
-        while (n_fin < K && n_fin / G < n_run && n_fin - n_drain < 3) {
-            const size_t k = n_fin, j = k / G, b0 = k * chunk, nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
-            if (j != j_known) {
-                const int ready = lzs_hip_event_done(E_RUN(j));
-                if (ready < 0) HIP_TRY(-ready, "hipEventQuery");
-                if (!ready) break;
-                /* the launch is through: its lengths, and where each of its chunks begins in the dense piece */
-                const size_t g0 = j * group, gn = nblocks - g0 < group ? nblocks - g0 : group;
-                const uint8_t *const lp = pin_len + (j % PIPE_SLOTS) * len_piece;
-                const uint32_t *lens = (const uint32_t *)lp;
-                uint64_t total = 0, at = 0;
-                memcpy(&total, lp + sizeof(uint32_t) * group, sizeof total);
-                for (size_t b = 0; b < gn; b++) {
-                    if (b % chunk == 0) chunk_at[b / chunk] = at;
-                    out_len[g0 + b] = lens[b];
-                    at += lens[b];
-                }
-                chunk_at[(gn + chunk - 1) / chunk] = at;
-                if (at != total || total > (uint64_t)group * d_out_stride) {
-                    rc = fail(LZS_E_HIP, "%s: inconsistent lengths from the device (launch %zu: %llu bytes by the lengths, %llu by the offsets)",
-                              who, j, (unsigned long long)at, (unsigned long long)total);
-                    goto done;
-                }
-                j_known = j;
-                n_done = j + 1;
-                TRACE("launch %zu seen finished", j);
-            }
-            const size_t c = k - j * G;                 /* the chunk's number inside its launch */
-            uint64_t *o = doff[k % 3], at = 0;
-            for (size_t b = 0; b < nb; b++) { o[b] = at; at += out_len[b0 + b]; }
-            o[nb] = at;
-            HIP_TRY(lzs_hip_d2h(pin_out[k % 3], (const uint8_t *)d_dense + (j % PIPE_SLOTS) * dense_piece + chunk_at[c],
-                                (size_t)(chunk_at[c + 1] - chunk_at[c]), s_out), "hipMemcpy D2H");
-            HIP_TRY(lzs_hip_event_record(E_OUT(k), s_out), "hipEventRecord");
-            if (c + 1 == G || k + 1 == K) HIP_TRY(lzs_hip_event_record(E_OUTS(j), s_out), "hipEventRecord");
-            TRACE("chunk %zu: copy out queued (%llu bytes)", k, (unsigned long long)(chunk_at[c + 1] - chunk_at[c]));
-            n_fin++;
-            progressed = 1;
-        }
-        SINCE(t_queue);
-        /* ---- the host threads: the next chunk in (its pinned piece is free once the copy before last has left it), and
-         * the oldest chunk whose bytes have arrived out */
-        /* (a chunk goes where launch j - PIPE_SLOTS read its blocks from: that launch must be through) */
-        const int do_fill_possible = n_fill < K && (n_fill / G < PIPE_SLOTS || n_done + PIPE_SLOTS > n_fill / G);
-        int do_fill = do_fill_possible, do_drain = 0;
-        if (do_fill && n_fill >= 2) {
-            const int ready = lzs_hip_event_done(E_IN(n_fill));
-            if (ready < 0) HIP_TRY(-ready, "hipEventQuery");
-            do_fill = ready;
-        }
-        if (n_drain < n_fin) {
-            const int ready = lzs_hip_event_done(E_OUT(n_drain));
-            if (ready < 0) HIP_TRY(-ready, "hipEventQuery");
-            do_drain = ready;
-        }
-        if (do_fill || do_drain) {
-            P.fill = do_fill ? (long)n_fill : -1;
-            P.drain = do_drain ? (long)n_drain : -1;
-            P.pin_in = pin_in[n_fill & 1];
-            P.pin_out = pin_out[n_drain % 3];
-            P.drain_off = doff[n_drain % 3];
-            pipe_round(&P);
-            SINCE(t_copy);
-            rounds++;
-            TRACE("host copies done: fill %ld, drain %ld", P.fill, P.drain);
-            if (do_fill) {
-                const size_t k = n_fill, b0 = k * chunk, nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
-                uint8_t *const to = (uint8_t *)d_in + (((k / G) % PIPE_SLOTS) * group + (k % G) * chunk) * d_in_stride;
-                HIP_TRY(lzs_hip_h2d(to, pin_in[k & 1], nb * d_in_stride, s_in), "hipMemcpy H2D");
-                HIP_TRY(lzs_hip_event_record(E_IN(k), s_in), "hipEventRecord");
-                if ((k + 1) % G == 0 || k + 1 == K) HIP_TRY(lzs_hip_event_record(E_INS(k / G), s_in), "hipEventRecord");
-                n_fill++;
-            }
-            if (do_drain) n_drain++;
-            SINCE(t_queue);
-            progressed = 1;
-        }
-        if (!progressed) {
-            /* nothing is ready: wait for what the pipeline needs next -- the copy out that is under way, else the
-             * launch that is on the device; but first of all the copy in whose pinned piece the next chunk wants */
-            if (do_fill_possible) HIP_TRY(lzs_hip_event_sync(E_IN(n_fill)), "hipEventSynchronize");     /* (the shortest wait first) */
-            else if (n_drain < n_fin) HIP_TRY(lzs_hip_event_sync(E_OUT(n_drain)), "hipEventSynchronize");
-            else if (n_fin < K && n_fin / G < n_run) HIP_TRY(lzs_hip_event_sync(E_RUN(n_fin / G)), "hipEventSynchronize");
-            else { rc = fail(LZS_E_HIP, "%s: the pipeline has nothing to wait for (filled %zu, launched %zu, copied out %zu, drained %zu of %zu)",
-                             who, n_fill, n_run, n_fin, n_drain, K); goto done; }
-            SINCE(t_wait);
-        }
+    R->debug = env->stream_debug; R->trace = env->stream_debug && env->pipe_trace; R->t_all = R->debug ? now_ms() : 0;
+    while (R->n_drain < R->pl.K) {
+        R->progressed = 0;
+        mark(R);
+        if ((rc = pipe_queue_launches(R)) != LZS_OK || (rc = pipe_queue_copy_outs(R)) != LZS_OK) goto done;
+        since(R, &R->t_queue);
+        if ((rc = pipe_host_round(R)) != LZS_OK) goto done;
+        if (!R->progressed && (rc = pipe_wait(R)) != LZS_OK) goto done;
     }
-    if (debug)
+    if (R->debug)
         fprintf(stderr, "liblzs pipeline: %s, %zu blocks in %zu chunks of %zu, %zu chunks a launch, %d host threads: %.1f ms = host copies %.1f "
                         "(%lu rounds) + waiting %.1f + queueing %.1f\n",
-                who, nblocks, K, chunk, G, P.started + 1, now_ms() - t_all, t_copy, rounds, t_wait, t_queue);
-#undef MARK
-#undef SINCE
-#undef HIP_TRY
-#undef S_RUN
-#undef E_IN
-#undef E_INS
-#undef E_RUN
-#undef E_OUT
-#undef E_OUTS
+                who, nblocks, R->pl.K, R->pl.chunk, R->pl.G, R->started + 1, now_ms() - R->t_all, R->t_copy, R->rounds, R->t_wait, R->t_queue);
 
 done:
     if (rc != LZS_OK)                                       /* nothing of ours may still be in flight */
         for (int i = 0; i < PIPE_STREAMS; i++) if (st->pipe_stream[i]) lzs_hip_stream_sync(st->pipe_stream[i]);
-    pthread_mutex_lock(&P.mu);
-    P.quit = 1;
-    pthread_cond_broadcast(&P.cv_work);
-    pthread_mutex_unlock(&P.mu);
-    for (int w = 1; w <= P.started; w++) pthread_join(P.th[w], NULL);
-    pthread_mutex_destroy(&P.mu); pthread_cond_destroy(&P.cv_work); pthread_cond_destroy(&P.cv_done);
-    free(doff[0]); free(doff[1]); free(doff[2]);
+    pthread_mutex_lock(&R->mu);
+    R->quit = 1;
+    pthread_cond_broadcast(&R->cv_work);
+    pthread_mutex_unlock(&R->mu);
+    for (int w = 1; w <= R->started; w++) pthread_join(R->th[w], NULL);
+    pthread_mutex_destroy(&R->mu); pthread_cond_destroy(&R->cv_work); pthread_cond_destroy(&R->cv_done);
+    free(R->doff[0]); free(R->doff[1]); free(R->doff[2]);
     staging_trim(st);
     return rc;
 }

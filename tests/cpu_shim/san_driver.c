@@ -9,7 +9,8 @@
  *   segments / stitch / extend-resume / decode-resume; host route: lzs_hostcodec.c) with 1-12 bytes of room for the
  *   low-memory block; the one-shot calls on both routes; decompression by many wavefronts ("streamdec": the scan rounds with
  *   their settle rule and all-0xFF shortcut, placement, one stream / concatenated streams / batches by segments / pieces of
- *   the incremental interface, each compared with the same call by one wavefront).
+ *   the incremental interface, each compared with the same call by one wavefront); the route decision and the pipeline's plan
+ *   against a table ("routes"); the one-after-the-other route's copy layouts where they switch ("layouts").
  * Every result is compared with the oracle.  Exit code 0 = all cases passed (the sanitizers make it non-zero themselves).
  * TEST INFRASTRUCTURE ONLY.
  */
@@ -20,6 +21,7 @@
 
 #include "lzs/lzs.h"
 #include "lzs/lzs_batch.h"
+#include "lzs_internal.h"                /* "routes": host_batch_route() and pipe_plan(), asked directly */
 
 size_t lzs_oracle_compress(uint8_t *out, size_t cap, const uint8_t *in, size_t n);
 size_t lzs_oracle_decompress(uint8_t *out, size_t cap, const uint8_t *in, size_t n);
@@ -78,6 +80,115 @@ static void ragged_batches(void)
         free(want); free(out);
     }
     free(x);
+}
+
+/* ---------------------------------------------------------------- which way a batch goes: host_batch_route() and pipe_plan() against a table
+ * (every row confirmed against the code before the two functions existed: the pipeline rows by its LZS_STREAM_DEBUG line, the
+ * others by the stage lines and the scan launches of the same shapes, and by reading its conditions) */
+static void routes(void)
+{
+    lzs_env_t dflt, one_wave, seg8, serial;
+    memset(&dflt, 0, sizeof dflt);                                  /* no switch set */
+    one_wave = seg8 = serial = dflt;
+    one_wave.one_wave = 1; seg8.batch_seg_mb = 8; serial.overlap_off = 1;
+    const launch_fn C = lzs_hip_launch_compress, D = lzs_hip_launch_decompress;
+    const uint32_t cmax = LZS_COMPRESSED_MAX(65536);
+    enum { SEGMENTS, PIPELINE, SERIAL_OFFERED, SERIAL_NOT_OFFERED };   /* (serial: one after the other; offered: to the pipeline, which declined) */
+    const struct { const char *what; launch_fn op; uint32_t cap; size_t nb, in_len; const lzs_env_t *env; int want; size_t chunk, K, G, J; } rows[] = {
+        { "256 blocks", D, 65536, 256, 36000, &dflt, SEGMENTS, 0, 0, 0, 0 },
+        { "1024 blocks: 64 MiB of extent exactly", D, 65536, 1024, 36000, &dflt, SEGMENTS, 0, 0, 0, 0 },
+        { "1025 blocks", D, 65536, 1025, 36000, &dflt, PIPELINE, 320, 4, 4, 1 },
+        { "1000 blocks, streams of 500 bytes: the preserved corner", D, 65536, 1000, 500, &dflt, SERIAL_NOT_OFFERED, 0, 0, 0, 0 },
+        { "5000 blocks of 4096: over 4096 blocks, 19.5 MiB", D, 4096, 5000, 2400, &dflt, SERIAL_OFFERED, 0, 0, 0, 0 },
+        { "256 blocks, LZS_ONE_WAVE", D, 65536, 256, 36000, &one_wave, SERIAL_OFFERED, 0, 0, 0, 0 },
+        { "256 blocks, LZS_BATCH_SEG_MB=8: 16 MiB", D, 65536, 256, 36000, &seg8, SERIAL_OFFERED, 0, 0, 0, 0 },
+        { "1024 blocks, LZS_ONE_WAVE", D, 65536, 1024, 36000, &one_wave, PIPELINE, 256, 4, 4, 1 },
+        { "compress, 416 blocks: three chunks of 128 and a short fourth", C, cmax, 416, 65536, &dflt, PIPELINE, 128, 4, 2, 2 },
+        { "compress, 2597 blocks", C, cmax, 2597, 65536, &dflt, PIPELINE, 640, 5, 2, 3 },
+        { "compress, 37 blocks", C, cmax, 37, 65536, &dflt, SERIAL_OFFERED, 0, 0, 0, 0 },
+        { "compress, 416 blocks, LZS_HOST_SERIAL", C, cmax, 416, 65536, &serial, SERIAL_OFFERED, 0, 0, 0, 0 },
+        { "compress, no capacity", C, 0, 416, 65536, &dflt, SERIAL_OFFERED, 0, 0, 0, 0 },
+        { "decompress, no capacity", D, 0, 1025, 36000, &dflt, SERIAL_OFFERED, 0, 0, 0, 0 },
+    };
+    for (unsigned i = 0; i < sizeof rows / sizeof rows[0]; i++) {
+        const size_t d_in = round16(rows[i].in_len), d_out = round16(rows[i].cap ? rows[i].cap : 1);
+        const batch_route_t r = host_batch_route(rows[i].op, rows[i].cap, rows[i].nb, d_in, d_out, rows[i].nb * rows[i].in_len, rows[i].env);
+        const pipe_plan_t pl = pipe_plan(rows[i].op, rows[i].cap, rows[i].nb, rows[i].in_len, rows[i].env);
+        const int got = r == ROUTE_SEGMENTS ? SEGMENTS : r == ROUTE_SERIAL ? SERIAL_NOT_OFFERED : pl.taken ? PIPELINE : SERIAL_OFFERED;
+        CHECK(got == rows[i].want, "%s: route %d (host_batch_route %d, pipe_plan taken %d), expected %d", rows[i].what, got, (int)r, pl.taken, rows[i].want);
+        if (got == PIPELINE && rows[i].want == PIPELINE)
+            CHECK(pl.chunk == rows[i].chunk && pl.K == rows[i].K && pl.G == rows[i].G && pl.J == rows[i].J && pl.slots == (pl.J < 3 ? pl.J : 3) && pl.threads == 4,
+                  "%s: %zu chunks of %zu, %zu a launch, %zu launches, %zu slots, %d threads", rows[i].what, pl.K, pl.chunk, pl.G, pl.J, pl.slots, pl.threads);
+    }
+}
+
+/* ---------------------------------------------------------------- the one-after-the-other route's copy layouts, where they switch
+ * (one copy / a copy per block below 16 blocks / pinned pieces laid out by the CPU on the way in; a copy per block / one copy of
+ * full blocks / compact + pieces + layout on the way out).  `want` / `want_len`: blocks at `wstride`. */
+static void lay_check(const char *what, size_t nb, const uint8_t *got, size_t stride, size_t cap, const uint32_t *got_len,
+                      const uint8_t *want, size_t wstride, const uint32_t *want_len, uint8_t fill)
+{
+    for (size_t b = 0; b < nb; b++) {
+        CHECK(got_len[b] == want_len[b] && memcmp(got + b * stride, want + b * wstride, want_len[b]) == 0, "%s, %zu blocks: block %zu differs (%u bytes, %u expected)",
+              what, nb, b, got_len[b], want_len[b]);
+        for (size_t i = want_len[b]; i < stride; i++)
+            if (got[b * stride + i] != fill) { CHECK(0, "%s, %zu blocks: block %zu: byte %zu past its length (capacity %zu) touched", what, nb, b, i, cap); break; }
+    }
+    CHECK(got[nb * stride] == fill, "%s, %zu blocks: the byte past the array touched", what, nb);
+}
+
+static void layouts(void)
+{
+    enum { LEN = 4096, CAP = LZS_COMPRESSED_MAX(LEN), S16 = (CAP + 15) / 16 * 16, RSTRIDE = LEN + 5, NBMAX = 17 };
+    uint8_t *x = sample(1, (size_t)NBMAX * LEN, 50), *xr = (uint8_t *)calloc(NBMAX, RSTRIDE);
+    uint8_t *want = (uint8_t *)malloc(NBMAX * S16), *got = (uint8_t *)malloc(NBMAX * S16 + 1), *comp = (uint8_t *)malloc(NBMAX * S16 + 1);
+    uint8_t *back = (uint8_t *)malloc((size_t)NBMAX * RSTRIDE + 1);
+    static const size_t counts[4] = { 1, 15, 16, 17 };
+    for (unsigned ci = 0; ci < 4; ci++) {
+        const size_t nb = counts[ci], mid = nb / 2;
+        uint32_t full[NBMAX], ragged[NBMAX], want_len[NBMAX], got_len[NBMAX], comp_len[NBMAX], back_len[NBMAX];
+        for (size_t b = 0; b < nb; b++) {
+            full[b] = LEN;
+            ragged[b] = b % 3 == 1 ? 0 : rnd_in(1, LEN);
+            memcpy(xr + b * RSTRIDE, x + b * LEN, LEN);
+        }
+        /* compress: (a) uniform blocks at the device stride in, into slots of a 16-aligned stride; (b) ragged and strided in */
+        for (size_t b = 0; b < nb; b++) want_len[b] = (uint32_t)lzs_oracle_compress(want + b * S16, CAP, x + b * LEN, LEN);
+        memset(comp, 0xA5, nb * S16 + 1);
+        CHECK(lzs_compress_batch(comp, S16, CAP, comp_len, x, LEN, NULL, LEN, nb) == 0, "compress (a), %zu blocks: %s", nb, lzs_last_error());
+        lay_check("compress (a)", nb, comp, S16, CAP, comp_len, want, S16, want_len, 0xA5);
+        for (size_t b = 0; b < nb; b++) want_len[b] = (uint32_t)lzs_oracle_compress(want + b * S16, CAP, x + b * LEN, ragged[b]);
+        memset(got, 0xA5, nb * S16 + 1);
+        CHECK(lzs_compress_batch(got, CAP + 2, CAP, got_len, xr, RSTRIDE, ragged, LEN, nb) == 0, "compress (b), %zu blocks: %s", nb, lzs_last_error());
+        lay_check("compress (b)", nb, got, CAP + 2, CAP, got_len, want, S16, want_len, 0xA5);
+        /* ... and back: (b) ragged streams with empty ones among them, strided in and out */
+        memset(back, 0x5A, nb * RSTRIDE + 1);
+        CHECK(lzs_decompress_batch(back, RSTRIDE, LEN, back_len, got, CAP + 2, got_len, CAP, nb) == 0, "decompress (b), %zu blocks: %s", nb, lzs_last_error());
+        lay_check("decompress (b)", nb, back, RSTRIDE, LEN, back_len, x, LEN, ragged, 0x5A);
+        /* compress (c): capacity = stride = 16 and every block full, the one-copy way out; (d) the middle block short */
+        for (int d = 0; d < 2; d++) {
+            if (d) full[mid] = 3;
+            for (size_t b = 0; b < nb; b++) want_len[b] = (uint32_t)lzs_oracle_compress(want + b * S16, 16, x + b * LEN, full[b]);
+            CHECK(d ? want_len[mid] < 16 : want_len[mid] == 16, "compress (%c): the middle block gives %u bytes", "cd"[d], want_len[mid]);
+            memset(got, 0xA5, nb * S16 + 1);
+            CHECK(lzs_compress_batch(got, 16, 16, got_len, x, LEN, d ? full : NULL, LEN, nb) == 0, "compress (%c), %zu blocks: %s", "cd"[d], nb, lzs_last_error());
+            lay_check(d ? "compress (d)" : "compress (c)", nb, got, 16, 16, got_len, want, S16, want_len, 0xA5);
+            full[mid] = LEN;
+        }
+        /* decompress: (a) uniform lengths at the device stride in (the streams end before their slots do), (c) capacity = stride
+         * and every block full out; (d) the middle block's stream that of a shorter block */
+        for (int d = 0; d < 2; d++) {
+            if (d) {
+                full[mid] = 1000;
+                memset(comp + mid * S16, 0xA5, S16);
+                lzs_oracle_compress(comp + mid * S16, CAP, x + mid * LEN, 1000);
+            }
+            memset(back, 0x5A, nb * RSTRIDE + 1);
+            CHECK(lzs_decompress_batch(back, LEN, LEN, back_len, comp, S16, NULL, S16, nb) == 0, "decompress (%s), %zu blocks: %s", d ? "a, d" : "a, c", nb, lzs_last_error());
+            lay_check(d ? "decompress (a, d)" : "decompress (a, c)", nb, back, LEN, LEN, back_len, x, LEN, full, 0x5A);
+        }
+    }
+    free(x); free(xr); free(want); free(got); free(comp); free(back);
 }
 
 /* ---------------------------------------------------------------- the overlapped pipeline (>= 24 MiB), two threads at once */
@@ -566,7 +677,9 @@ int main(int argc, char **argv)
     const char *only = argc > 1 ? argv[1] : "";
     char info[256];
     if (lzs_backend_info(info, sizeof info) != 0 || !strstr(info, "cpu shim")) { fprintf(stderr, "not linked with the cpu shim: %s\n", info); return 2; }
+    if (!*only || !strcmp(only, "routes")) routes();
     if (!*only || !strcmp(only, "ragged")) ragged_batches();
+    if (!*only || !strcmp(only, "layouts")) layouts();
     if (!*only || !strcmp(only, "streams")) one_shot_streams();
     if (!*only || !strcmp(only, "incremental")) incremental();
     if (!*only || !strcmp(only, "streamdec")) streamdec();

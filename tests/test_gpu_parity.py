@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
-from conftest import golden_bytes, golden_json, length_bits, uncompressible_sequence
+from conftest import CACHED_ENV, golden_bytes, golden_json, length_bits, uncompressible_sequence
 import lzs_compression_amd as lzs
 from lzs_compression_amd import workload
 
@@ -1375,7 +1375,11 @@ def test_device_batch_calls_capture_into_a_hip_graph():
 
 def test_small_batch_in_device_memory_decompressed_in_segments():
     """lzs_decompress_batch_device_sync(): the segment route for batches whose buffers are already
-    in HBM (lengths on the host, synchronous).  Same results as the one-launch device call."""
+    in HBM (lengths on the host, synchronous).  Same results as the one-launch device call -- and as the same call with
+    LZS_ONE_WAVE set, which reaches it like the host-buffer batches (one route decision: host_batch_route()).  Same bytes
+    either way cannot show that the switch arrived: that it turns the segments off is the `routes` case of
+    tests/cpu_shim/san_driver.c (256 blocks with one_wave).  A process that reads its switches once (LZS_TEST_CACHED_ENV)
+    would not see the switch flipped, and leaves that comparison out."""
     for cls, nb in (("text", 7), ("lowent", 40), ("random", 3), ("text", 200)):
         x = torch.from_numpy(workload.fill(cls, nb)).cuda()
         slots, lens = lzs.compress_blocks(x)
@@ -1387,6 +1391,75 @@ def test_small_batch_in_device_memory_decompressed_in_segments():
             torch.cuda.synchronize()
             assert (out_len == ref_len.cpu().numpy()).all() and (out_len == cap).all()
             assert torch.equal(out[:, :cap], ref[:, :cap]) and torch.equal(out[:, :cap], x[:, :cap])
+            if (cls, nb) == ("text", 7) and not CACHED_ENV:      # (a process that reads its switches once does not see this one)
+                with pytest.MonkeyPatch.context() as env:
+                    env.setenv("LZS_ONE_WAVE", "1")
+                    one, one_len = lzs.decompress_blocks_sync(slots, host_lens, cap)
+                assert (one_len == out_len).all() and torch.equal(one[:, :cap], out[:, :cap])
+
+
+def test_the_one_after_the_other_routes_copy_layouts_where_they_switch():
+    """Host-buffer batches on the one-after-the-other route (lzs_host.c: copy_blocks_in(), copy_blocks_out()) at the smallest
+    shapes at which each copy layout is chosen: 1, 15, 16, 17 blocks of 4096 bytes; on the way in (a) uniform blocks at the
+    16-aligned device stride (one copy) and (b) ragged blocks in a strided array, some of them empty (a copy per block below
+    16 blocks, pinned pieces laid out by the CPU from there on); on the way out (c) stride = capacity, a multiple of 16, and
+    every block full (one copy from 16 blocks on) and (d) the same with the middle block short (compact + layout).  Bytes and
+    lengths against the oracle and the data; the fill behind every out_len[b] and past every capacity untouched."""
+    LEN, RSTRIDE = 4096, 4096 + 5
+    CAP = lzs.compressed_max(LEN)
+    S16 = (CAP + 15) // 16 * 16
+    L = lzs.lib()
+    rng = np.random.default_rng(50)
+
+    def call(fn, ostride, cap, inp, istride, lens, in_len, nb, fill):
+        out = np.full(nb * ostride + 1, fill, dtype=np.uint8)
+        out_len = np.zeros(nb, dtype=np.uint32)
+        rc = fn(out.ctypes.data, ostride, cap, out_len.ctypes.data, inp.ctypes.data, istride, lens.ctypes.data if lens is not None else None, in_len, nb)
+        assert rc == 0, lzs.last_error()
+        return out, out_len
+
+    def check(what, out, ostride, out_len, wants, fill):
+        for b, want in enumerate(wants):
+            assert int(out_len[b]) == len(want) and out[b * ostride: b * ostride + len(want)].tobytes() == want, (what, len(wants), b)
+            assert (out[b * ostride + len(want): (b + 1) * ostride] == fill).all(), (what, len(wants), b, "touched past its length")
+        assert out[len(wants) * ostride] == fill, (what, len(wants), "touched past the array")
+
+    for nb in (1, 15, 16, 17):
+        mid = nb // 2
+        x = workload.fill("lowent", nb, LEN)
+        xr = np.zeros((nb, RSTRIDE), dtype=np.uint8)
+        xr[:, :LEN] = x
+        ragged = rng.integers(1, LEN + 1, nb).astype(np.uint32)
+        ragged[1::3] = 0
+        full = np.full(nb, LEN, dtype=np.uint32)
+        # compress: (a) in, into slots of a 16-aligned stride; (b) in
+        comp, comp_len = call(L.lzs_compress_batch, S16, CAP, x, LEN, None, LEN, nb, 0xA5)
+        check("compress (a)", comp, S16, comp_len, [O.compress(bytes(x[b])) for b in range(nb)], 0xA5)
+        rag, rag_len = call(L.lzs_compress_batch, CAP + 2, CAP, xr, RSTRIDE, ragged, LEN, nb, 0xA5)
+        check("compress (b)", rag, CAP + 2, rag_len, [O.compress(bytes(x[b, :ragged[b]])) for b in range(nb)], 0xA5)
+        # ... and back: (b) in, strided out
+        back, back_len = call(L.lzs_decompress_batch, RSTRIDE, LEN, rag, CAP + 2, rag_len, CAP, nb, 0x5A)
+        check("decompress (b)", back, RSTRIDE, back_len, [bytes(x[b, :ragged[b]]) for b in range(nb)], 0x5A)
+        # compress (c): capacity = stride = 16 and every block full; (d) the middle block short
+        for form in "cd":
+            lens = full.copy()
+            if form == "d":
+                lens[mid] = 3
+            wants = [O.compress(bytes(x[b, :lens[b]]))[:16] for b in range(nb)]
+            assert (len(wants[mid]) < 16) == (form == "d") and all(len(w) == 16 for b, w in enumerate(wants) if b != mid)
+            cut, cut_len = call(L.lzs_compress_batch, 16, 16, x, LEN, lens if form == "d" else None, LEN, nb, 0xA5)
+            check("compress (%s)" % form, cut, 16, cut_len, wants, 0xA5)
+        # decompress: (a) in (uniform lengths: the streams end before their slots do), (c) out; (d) the middle block's stream
+        # that of a shorter block
+        for form in "cd":
+            lens = full.copy()
+            if form == "d":
+                lens[mid] = 1000
+                short = O.compress(bytes(x[mid, :1000]))
+                comp[mid * S16: (mid + 1) * S16] = 0xA5
+                comp[mid * S16: mid * S16 + len(short)] = np.frombuffer(short, dtype=np.uint8)
+            back, back_len = call(L.lzs_decompress_batch, LEN, LEN, comp, S16, None, S16, nb, 0x5A)
+            check("decompress (a, %s)" % form, back, LEN, back_len, [bytes(x[b, :lens[b]]) for b in range(nb)], 0x5A)
 
 
 def test_a_batch_whose_ring_does_not_fit_takes_the_serial_route_and_succeeds(monkeypatch):

@@ -8,7 +8,8 @@ c/src/liblzs/lzs-compression.c:329,349,437) are the reason to look.
   device memory is heap memory, the launches are backed by the oracle and by serial restatements of the kernels'
   contracts, the many-wavefront decompression's scan and decode among them) and driven by tests/cpu_shim/san_driver.c
   through the ragged-batch, truncation, >= 24 MiB pipeline, one-stream-in-segments, incremental-pieces and
-  many-wavefront-decompression ("streamdec": scan rounds, settle rule, placement) cases, under -fsanitize=address,undefined and under -fsanitize=thread.
+  many-wavefront-decompression ("streamdec": scan rounds, settle rule, placement) cases, the route decision and the
+  pipeline's plan against a table ("routes") and the serial route's copy layouts where they switch ("layouts"), under -fsanitize=address,undefined and under -fsanitize=thread.
 * The checkers themselves (oracle/lzs_oracle.c, cpu_bench.c, csrc/lzs_workload.c): tests/test_oracle.py against their
   ASan + UBSan builds.
 A report from a sanitizer fails the run by itself (non-zero exit, text on stderr)."""
@@ -41,7 +42,7 @@ def _run(exe, cases, env_extra, timeout):
 def test_host_sources_under_address_and_undefined_behaviour_sanitizers(built):
     # ("release": what a thread keeps between calls goes back on lzs_release_thread_cache(), on thread exit, and above
     # LZS_KEEP_MAX_MB -- the shim counts its outstanding "device" bytes; leak detection is on)
-    _run(os.path.join(built, "san_asan"), ["ragged", "streams", "incremental", "streamdec", "pipeline", "release"],
+    _run(os.path.join(built, "san_asan"), ["routes", "ragged", "layouts", "streams", "incremental", "streamdec", "pipeline", "release"],
          {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, 900)
 
 
@@ -55,7 +56,7 @@ def test_host_sources_under_thread_sanitizer(built):
     """The cases with threads in them: the pipeline's four workers per batch call, two calling threads at once, the
     per-thread staging and environment (the one-stream case is single-threaded and the oracle's brute-force search behind
     the shim's segments takes 100 s under this sanitizer: the address run covers it, and "streamdec", single-threaded too)."""
-    _run(os.path.join(built, "san_tsan"), ["ragged", "pipeline", "release"], {"TSAN_OPTIONS": "halt_on_error=1"}, 900)
+    _run(os.path.join(built, "san_tsan"), ["ragged", "layouts", "pipeline", "release"], {"TSAN_OPTIONS": "halt_on_error=1"}, 900)
 
 
 def test_the_checkers_under_address_and_undefined_behaviour_sanitizers():

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Wall time per call of the many-wavefront decompression's host paths, this build against another build of liblzs.so.
+"""Wall time per call of the many-wavefront decompression's host paths and of the host-buffer batches, this build against
+another build of liblzs.so.
 
     python tools/stream_host_ab.py --other path/to/other/liblzs.so [--reps 10] [--shapes dec-1m,dec-64m,dev-1g,batch-256] [--out FILE]
 
 Shapes (text): dec-1m / dec-64m  lzs_decompress of a stream that decodes to 1 / 64 MiB, host buffers;
                dev-1g            lzs_decompress_stream_device of 1 GiB;
-               batch-256         lzs_decompress_batch of 256 blocks of 64 KiB, host buffers (goes by segments).
+               batch-256         lzs_decompress_batch of 256 blocks of 64 KiB, host buffers (goes by segments);
+               cbatch-2597 / dbatch-2597  lzs_compress_batch / lzs_decompress_batch of 2597 blocks of 64 KiB, host buffers
+                                 (the overlapped route, lzs_pipeline.c);
+               cbatch-64         lzs_compress_batch of 64 blocks of 64 KiB, host buffers (one after the other).
 Every shape gets two worker processes -- one per build, chosen by LZS_LIBRARY, each with its data made, checked and three calls
 warm -- and the two are timed in turn, one call each, `--reps` times: what one build sees of the machine the other sees too.
 The verdict per shape: this build's median is no more than the other's median plus the other's own spread (max - min).
@@ -19,7 +23,8 @@ import sys
 import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SHAPES = {"dec-1m": 16, "dec-64m": 1024, "dev-1g": 16384, "batch-256": 256}       # 64 KiB blocks of text
+SHAPES = {"dec-1m": 16, "dec-64m": 1024, "dev-1g": 16384, "batch-256": 256,          # 64 KiB blocks of text
+          "cbatch-2597": 2597, "dbatch-2597": 2597, "cbatch-64": 64}
 
 
 def worker(shape):
@@ -30,7 +35,15 @@ def worker(shape):
     from lzs_compression_amd import workload
     L = lzs.lib()
     x = workload.fill("text", SHAPES[shape])
-    if shape == "batch-256":
+    if shape.startswith("cbatch-"):
+        want, want_len = lzs.compress_batch(x)
+        out, out_len = np.zeros_like(want), np.zeros(len(x), dtype=np.uint32)
+
+        def call():
+            assert L.lzs_compress_batch(out.ctypes.data, out.shape[1], out.shape[1], out_len.ctypes.data, x.ctypes.data, x.shape[1],
+                                        None, x.shape[1], len(x)) == 0
+        check = lambda: np.array_equal(out_len, want_len) and all(np.array_equal(out[b, :out_len[b]], want[b, :out_len[b]]) for b in range(len(x)))
+    elif shape in ("batch-256", "dbatch-2597"):
         comp, lens = lzs.compress_batch(x)
         out, out_len = np.zeros_like(x), np.zeros(len(x), dtype=np.uint32)
 
@@ -112,15 +125,15 @@ def main():
                 p.stdin.close()
                 p.wait(timeout=120)
         for who in ("other", "this"):
-            say(f"{shape:10} {who:5} " + " ".join(f"{t:9.3f}" for t in times[who]))
+            say(f"{shape:12} {who:5} " + " ".join(f"{t:9.3f}" for t in times[who]))
         med = {w: statistics.median(times[w]) for w in times}
         spread = max(times["other"]) - min(times["other"])
         ok = med["this"] <= med["other"] + spread
         failed |= not ok
-        table.append(f"{shape:10} {med['other']:12.3f} {min(times['other']):9.3f} {max(times['other']):9.3f} {med['this']:12.3f} {min(times['this']):9.3f} "
+        table.append(f"{shape:12} {med['other']:12.3f} {min(times['other']):9.3f} {max(times['other']):9.3f} {med['this']:12.3f} {min(times['this']):9.3f} "
                      f"{max(times['this']):9.3f}   {'ok' if ok else 'SLOWER'} (this <= {med['other'] + spread:.3f})")
     say("")
-    say(f"{'shape':10} {'other median':>12} {'min':>9} {'max':>9} {'this median':>12} {'min':>9} {'max':>9}   this median <= other median + (other max - min)")
+    say(f"{'shape':12} {'other median':>12} {'min':>9} {'max':>9} {'this median':>12} {'min':>9} {'max':>9}   this median <= other median + (other max - min)")
     for row in table:
         say(row)
     if a.out:
