@@ -83,6 +83,11 @@ class _Codec:
 # what lzs_oracle_decompress_channel counts (the enum beside it), in order
 CHANNEL_COUNTERS = ("zero_bytes", "crossing", "overlap", "long_small", "long_zero", "cut", "nibble0_marker", "nibble0_full")
 
+# what lzs_oracle_compress_channel counts (the enum before compress_core), in order
+CHANNEL_ENCODE_COUNTERS = ("src_in_history", "src_straddles", "offset_2047", "reaches_view_0", "short_form_127", "long_form_128",
+                           "nibble_15", "ext_ends_at_packet_end", "search_cut_by_end", "last_byte_literal", "first_token_offset_1",
+                           "cut")
+
 
 class _Oracle(_Codec):
     def __init__(self):
@@ -103,6 +108,11 @@ class _Oracle(_Codec):
             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
             ctypes.c_void_p, ctypes.c_void_p]
+        self.lib.lzs_oracle_compress_channel.restype = ctypes.c_size_t
+        self.lib.lzs_oracle_compress_channel.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+            ctypes.c_void_p]
 
     def compress_brute(self, data: bytes, cap: Optional[int] = None) -> bytes:
         return self._call(self._lzs_oracle_compress_brute, data,
@@ -141,6 +151,37 @@ class _Oracle(_Codec):
         assert n <= room
         got = (dst.raw[:n], int(status.value), new.raw[:new_h.value])
         return got + (rec[:ntok.value], int(stop.value)) if trace else got
+
+    def compress_channel(self, hist: bytes, data: bytes, cap: Optional[int] = None, brute: bool = False,
+                         counters: Optional[np.ndarray] = None, trace: bool = False):
+        """One packet of a channel through the plain model of include/lzs/lzs_channels.h compression
+        (lzs_oracle_compress_channel): ``hist`` is the channel's history (at most 2047 bytes), ``cap`` the output capacity
+        (default: compressed_max(len(data)), room for all of it).  Returns (the stream cut at ``cap``, the uncut length, the
+        status byte, the new history) -- and, with ``trace``, the token list [(position in the packet, offset or 0, bytes
+        covered, bit position)].  ``brute``: the written search rule instead of the chained finder.  ``counters``: a uint64
+        array of len(CHANNEL_ENCODE_COUNTERS) that the call adds to."""
+        assert len(hist) <= 2047
+        if cap is None:
+            cap = compressed_max(len(data))
+        src = ctypes.create_string_buffer(bytes(data), len(data) + 1)
+        old = ctypes.create_string_buffer(bytes(hist), len(hist) + 1)
+        dst = ctypes.create_string_buffer(cap + 1)
+        new = ctypes.create_string_buffer(2048)
+        new_h, ntok, total, status = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_uint8(0)
+        if counters is not None:
+            assert counters.dtype == np.uint64 and counters.size == len(CHANNEL_ENCODE_COUNTERS) and counters.flags.c_contiguous
+        max_tok = len(data) if trace else 0           # no token covers less than a byte
+        rec = np.zeros((max_tok, 4), dtype=np.uint32) if trace else None
+        n = self.lib.lzs_oracle_compress_channel(
+            ctypes.addressof(dst), cap, ctypes.addressof(src), len(data), ctypes.addressof(old), len(hist), int(brute),
+            ctypes.addressof(total), ctypes.addressof(new), ctypes.addressof(new_h), ctypes.addressof(status),
+            None if counters is None else counters.ctypes.data, None if rec is None else rec.ctypes.data, max_tok,
+            ctypes.addressof(ntok))
+        if n == ctypes.c_size_t(-1).value:
+            raise MemoryError("lzs_oracle_compress_channel")
+        assert n == min(total.value, cap) and dst.raw[cap:] == b"\0"
+        got = (dst.raw[:n], int(total.value), int(status.value), new.raw[:new_h.value])
+        return got + (rec[:ntok.value],) if trace else got
 
 
 _oracle: Optional[_Oracle] = None

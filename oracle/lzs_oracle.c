@@ -1,5 +1,7 @@
 /*
- * oracle/lzs_oracle.c -- CPU restatement of the LZS one-shot codec.
+ * oracle/lzs_oracle.c -- CPU restatement of the LZS one-shot codec, and plain models of one channel packet's decoding and
+ * compression (lzs_oracle_decompress_channel, lzs_oracle_compress_channel: tests/test_channel_model.py,
+ * tests/test_channel_encode_model.py hold them to the reference).
  *
  * TEST INFRASTRUCTURE ONLY.  Nothing in the shipped library (liblzs.so, the
  * lzs_compression_amd package) links, loads or calls this file.  Only tests/,
@@ -139,11 +141,34 @@ static unsigned chained_search(const chains_t *ch, const uint8_t *in, size_t n, 
     return best;
 }
 
-static size_t compress_core(uint8_t *out, size_t cap, const uint8_t *in, size_t n, int brute)
+/* What lzs_oracle_compress_channel counts (in order; oracle/__init__.py: CHANNEL_ENCODE_COUNTERS).  A token's source is
+ * view[c - off, c - off + len); `start` is where the packet begins in the view. */
+enum {
+    CE_SRC_IN_HISTORY = 0,   /* matches whose source lies wholly before the packet                */
+    CE_SRC_STRADDLES,        /* matches whose source starts before the packet and ends inside it  */
+    CE_OFFSET_2047,          /* matches at the farthest offset                                    */
+    CE_REACHES_VIEW_0,       /* matches whose source starts at byte 0 of the view                 */
+    CE_SHORT_127,            /* the last offset of the 7-bit form                                 */
+    CE_LONG_128,             /* the first offset of the 11-bit form                               */
+    CE_NIBBLE_15,            /* extension nibbles of 15: the match continues                      */
+    CE_EXT_ENDS_AT_END,      /* extended matches that end with the packet                         */
+    CE_SEARCH_CUT_BY_END,    /* matches taken where fewer than 12 bytes were left to search       */
+    CE_LAST_BYTE_LITERAL,    /* packets whose last byte is a literal                              */
+    CE_FIRST_TOKEN_OFF_1,    /* packets whose first token is a match at offset 1                  */
+    CE_CUT,                  /* packets cut at the capacity                                       */
+    CE_COUNTERS
+};
+
+/* The token loop over in[0, n), the first token at `start`: what lies before it is only searched (`start` = 0: a whole
+ * block).  The chains are built over in[0, start) too.  *total (may be NULL) receives the length of the uncut stream.
+ * counters[] (may be NULL) are ADDED to; trace[] (may be NULL) receives up to max_tok records {position in the packet,
+ * offset (0 = literal), bytes covered, bit position}, one a token, and *ntok the token count. */
+static size_t compress_core(uint8_t *out, size_t cap, const uint8_t *in, size_t n, size_t start, int brute, size_t *total,
+                            uint64_t *counters, uint32_t *trace, size_t max_tok, size_t *ntok)
 {
     sink_t   s = { out, cap, 0, 0, 0 };
     chains_t ch = { NULL, NULL };
-    size_t   c = 0, inserted = 0;
+    size_t   c = start, inserted = 0, tok = 0;
 
     if (!brute) {
         ch.head = (int32_t *)malloc(65536 * sizeof(int32_t));
@@ -154,6 +179,9 @@ static size_t compress_core(uint8_t *out, size_t cap, const uint8_t *in, size_t 
 
     while (c < n) {
         unsigned off, len;
+        size_t   at = c;
+        uint64_t bit = (uint64_t)s.total * 8u + s.pending;
+        int      extended = 0;
         if (!brute) {
             /* make every position before c searchable */
             for (; inserted < c; inserted++) {
@@ -171,20 +199,44 @@ static size_t compress_core(uint8_t *out, size_t cap, const uint8_t *in, size_t 
         if (len < 2) {                                   /* :365-375 literal */
             sink_put(&s, in[c], 9);
             c += 1;
-            continue;
+            off = 0;
+            if (counters && c == n)
+                counters[CE_LAST_BYTE_LITERAL]++;
+        } else {
+            unsigned first = len < TOKEN_MAX ? len : TOKEN_MAX;   /* :399 */
+            if (counters && n - c < SEARCH_CAP)
+                counters[CE_SEARCH_CUT_BY_END]++;
+            put_match_head(&s, off, first);
+            c += first;
+            if (first == TOKEN_MAX) {                        /* :411-431 extension */
+                unsigned e;
+                extended = 1;
+                do {
+                    unsigned lim = (n - c < NIBBLE_MAX) ? (unsigned)(n - c) : NIBBLE_MAX;
+                    e = common_prefix(in, c, c - off, lim);
+                    sink_put(&s, e, 4);
+                    c += e;
+                    if (counters && e == NIBBLE_MAX)
+                        counters[CE_NIBBLE_15]++;
+                } while (e == NIBBLE_MAX);
+            }
+            if (counters) {
+                size_t from = at - off, to = from + (c - at);            /* the source: in[from, to) */
+                if (from < start && to <= start) counters[CE_SRC_IN_HISTORY]++;
+                if (from < start && to > start)  counters[CE_SRC_STRADDLES]++;
+                if (off == WINDOW)               counters[CE_OFFSET_2047]++;
+                if (from == 0)                   counters[CE_REACHES_VIEW_0]++;
+                if (off == SHORT_MAX)            counters[CE_SHORT_127]++;
+                if (off == SHORT_MAX + 1)        counters[CE_LONG_128]++;
+                if (extended && c == n)          counters[CE_EXT_ENDS_AT_END]++;
+                if (at == start && off == 1)     counters[CE_FIRST_TOKEN_OFF_1]++;
+            }
         }
-        unsigned first = len < TOKEN_MAX ? len : TOKEN_MAX;   /* :399 */
-        put_match_head(&s, off, first);
-        c += first;
-        if (first == TOKEN_MAX) {                        /* :411-431 extension */
-            unsigned e;
-            do {
-                unsigned lim = (n - c < NIBBLE_MAX) ? (unsigned)(n - c) : NIBBLE_MAX;
-                e = common_prefix(in, c, c - off, lim);
-                sink_put(&s, e, 4);
-                c += e;
-            } while (e == NIBBLE_MAX);
+        if (trace && tok < max_tok) {
+            trace[4 * tok + 0] = (uint32_t)(at - start); trace[4 * tok + 1] = off;
+            trace[4 * tok + 2] = (uint32_t)(c - at);     trace[4 * tok + 3] = (uint32_t)bit;
         }
+        tok++;
     }
     /* End marker 1 1 0000000 then zero bits to the byte boundary (:449-466). */
     sink_put(&s, 0x180, 9);
@@ -193,19 +245,76 @@ static size_t compress_core(uint8_t *out, size_t cap, const uint8_t *in, size_t 
 
     free(ch.head);
     free(ch.prev);
+    if (total)
+        *total = s.total;
+    if (ntok)
+        *ntok = tok;
+    if (counters && s.total > cap)
+        counters[CE_CUT]++;
     return s.total < cap ? s.total : cap;
 }
 
 /* lzs_compress() semantics (c/src/liblzs/lzs-compression.c:249-467). */
 size_t lzs_oracle_compress(uint8_t *out, size_t cap, const uint8_t *in, size_t n)
 {
-    return compress_core(out, cap, in, n, 0);
+    return compress_core(out, cap, in, n, 0, 0, NULL, NULL, NULL, 0, NULL);
 }
 
 /* Same contract, brute-force finder: slow, but it *is* the written rule. */
 size_t lzs_oracle_compress_brute(uint8_t *out, size_t cap, const uint8_t *in, size_t n)
 {
-    return compress_core(out, cap, in, n, 1);
+    return compress_core(out, cap, in, n, 0, 1, NULL, NULL, NULL, 0, NULL);
+}
+
+/* ------------------------------------------------------------------ */
+/* One packet of a channel, compressed (include/lzs/lzs_channels.h:    */
+/* "Device-pointer channel compression"): what                         */
+/* lzs_compress_incremental(add_end_marker) writes for in[0, n) on a   */
+/* parameter block that has seen the channel's earlier packets.  The   */
+/* rule is that of a block, on the view hist[0, h) | in[0, n), h <=    */
+/* 2047, with the first token at h: offsets reach back min(position,   */
+/* 2047) bytes of the view, lengths are capped by the end of the view, */
+/* the nearest offset wins; the stream starts at bit 0 and ends with   */
+/* the marker and its padding.                                         */
+/*                                                                     */
+/*  - out[] receives the stream cut at `cap`, as lzs_compress() cuts   */
+/*    it; the return value is min(*total, cap), *total the uncut       */
+/*    length.                                                          */
+/*  - *status: END_MARKER | INPUT_FINISHED | INPUT_STARVED (0x07) if   */
+/*    *total <= cap, else NO_OUTPUT_BUFFER_SPACE in the marker's place */
+/*    (0x0B).                                                          */
+/*  - new_hist[0, *new_h): the last min(2047, h + n) bytes of the view,*/
+/*    cut or not.                                                      */
+/*                                                                     */
+/* `brute`: the written rule instead of the chained finder.  counters, */
+/* trace, max_tok, ntok: as compress_core takes them.  Returns         */
+/* (size_t)-1 if memory ran out.                                       */
+/* ------------------------------------------------------------------ */
+size_t lzs_oracle_compress_channel(uint8_t *out, size_t cap, const uint8_t *in, size_t n,
+                                   const uint8_t *hist, size_t h, int brute, size_t *total,
+                                   uint8_t *new_hist, size_t *new_h, uint8_t *status,
+                                   uint64_t *counters, uint32_t *trace, size_t max_tok, size_t *ntok)
+{
+    size_t   view_n = h + n, uncut = 0;
+    uint8_t *view = (uint8_t *)malloc(view_n + 1);
+    if (!view)
+        return (size_t)-1;
+    if (h)
+        memcpy(view, hist, h);
+    if (n)
+        memcpy(view + h, in, n);
+
+    size_t got = compress_core(out, cap, view, view_n, h, brute, &uncut, counters, trace, max_tok, ntok);
+    if (got != (size_t)-1) {
+        size_t keep = view_n < WINDOW ? view_n : WINDOW;
+        if (keep)
+            memcpy(new_hist, view + view_n - keep, keep);
+        *new_h = keep;
+        *total = uncut;
+        *status = uncut <= cap ? 0x07 : 0x0B;
+    }
+    free(view);
+    return got;
 }
 
 /* ------------------------------------------------------------------ */

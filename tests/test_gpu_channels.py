@@ -2,7 +2,13 @@
 incremental interface on that channel's own parameter block (itself pinned to the reference: test_gpu_incremental.py,
 tests/golden/inc_packets.lzs), the reference itself where oracle/_ref/liblzs_ref.so was built, round trips with the
 decoder's state equal to the compressor's, resets, cut capacity, the order-independent CHAIN form, malformed packets,
-the ratio against stateless blocks and repeated channel ids through ChannelCodec."""
+the ratio against stateless blocks and repeated channel ids through ChannelCodec.
+
+Not covered here: the packets are workload data at aligned places (_pack: a 16-byte-aligned base, strides of 16, the library's
+own output), so matches, comparisons and refills on the border between history and packet, the extreme matches, unaligned rows
+and the exact status byte at total == out_cap come up by chance or not at all.  tests/test_gpu_channel_encode_model.py builds
+those cases on purpose and compares with the plain model of channel compression (oracle/lzs_oracle.c:
+lzs_oracle_compress_channel)."""
 import ctypes
 import hashlib
 import os

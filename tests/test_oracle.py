@@ -227,3 +227,24 @@ def test_channel_model_on_synthesised_packets():
             assert sum(int(t[2]) for t in tokens) == len(out) <= cap, (i, cap)
             assert O.decompress_channel(b"", p, cap)[0] == O.decompress(p, cap), (i, cap)
     assert counters.all(), counters
+
+
+def test_channel_encode_model_on_built_packets():
+    """lzs_oracle_compress_channel on a few packets built from their histories (tests/test_channel_encode_model.py holds it to
+    everything else; here it also runs in the sanitizer builds of the checkers): chained == brute, the cut law, the history law,
+    the round trip through lzs_oracle_decompress_channel, counters and trace."""
+    import test_channel_encode_model as E
+    rng = np.random.default_rng(8)
+    counters = np.zeros(len(oracle.CHANNEL_ENCODE_COUNTERS), dtype=np.uint64)
+    for i in range(400):
+        hist = E.make_history(rng, int(rng.choice(E.HIST_LENS)), str(rng.choice(E.HIST_KINDS)))
+        for _ in range(3):
+            p = E.next_packet(rng, hist)
+            out, total, st, new, tokens = O.compress_channel(hist, p, counters=counters, trace=True)
+            assert (out, total, st, new) == O.compress_channel(hist, p, brute=True), (i, len(hist), len(p))
+            assert st == E.DONE and total == len(out) and new == (hist + p)[-2047:] and sum(int(t[2]) for t in tokens) == len(p)
+            cap = int(rng.integers(0, total + 2))
+            assert O.compress_channel(hist, p, cap, counters=counters) == (out[:cap], total, E.DONE if total <= cap else E.CUT, new)
+            assert O.decompress_channel(hist, out, len(p)) == (p, 0x04, new), (i, len(hist), len(p))
+            hist = new
+    assert counters.all(), dict(zip(oracle.CHANNEL_ENCODE_COUNTERS, counters.tolist()))
