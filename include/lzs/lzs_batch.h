@@ -176,8 +176,8 @@ int lzs_compact_device(void *d_dense, uint64_t *d_offsets, const void *d_slots, 
 /*
  * PACKED streams and packed outputs: blocks addressed by OFFSETS instead of a stride -- what lzs_compact_device() produces, how
  * a shard arrives over RCCL, how a file of concatenated streams with a length table or a drained packet queue lies in memory.
- * ("Ragged" in this library means per-block lengths in a strided array; this is the other thing.)  The three calls below and
- * lzs_decompress_channels_packed_device() (lzs_channels.h) share their addressing:
+ * ("Ragged" in this library means per-block lengths in a strided array; this is the other thing.)  The calls below,
+ * lzs_decompress_channels_packed_device() and lzs_compress_channels_packed_device() (lzs_channels.h) share their addressing:
  *
  *   input   block b starts at d_in + d_in_off[b].  With d_in_len NULL its length is d_in_off[b + 1] - d_in_off[b]: nblocks + 1
  *           entries are read and must not decrease.  With d_in_len given its length is d_in_len[b]: only nblocks entries of
@@ -194,11 +194,11 @@ int lzs_compact_device(void *d_dense, uint64_t *d_offsets, const void *d_slots, 
  *           (d_size[b] = 0), status ERROR (0x10) where there is a status array, nothing of it is read or written, its channel's
  *           slot is untouched, and the other blocks are unaffected.
  *
- * All four are asynchronous on `hip_stream`, allocate nothing, do not synchronise and may be captured into a hipGraph (the
+ * All of them are asynchronous on `hip_stream`, allocate nothing, do not synchronise and may be captured into a hipGraph (the
  * note on the very first call into the library applies).  Checked before the device is asked (LZS_E_ARG, the call's name in
  * lzs_last_error()): a required pointer that is NULL, an offset array that is not 8-byte aligned, d_out_len / d_size being the
  * array d_in_len, nblocks > 0x7FFFFFFF, limit > 0xFFFFFFFF, a bad align.  Offsets are uint64_t; a torch int64 tensor holds the
- * same bits.  Not offered: packed compression, packed bursts, host-buffer entries.
+ * same bits.  Not offered: packed bursts, host-buffer entries.
  *
  * lzs_offsets_from_sizes_device: d_offsets[0] = 0, d_offsets[b + 1] = d_offsets[b] + round_up(d_size[b], align); nblocks + 1
  * entries, the total in d_offsets[nblocks]; nblocks == 0 writes d_offsets[0] = 0.  `align`: a power of two from 1 to 256 -- 16
@@ -217,6 +217,36 @@ int lzs_decompressed_size_packed_device(uint32_t *d_size, uint8_t *d_status, con
  * more than 4 GiB apart they are decoded one after the other, which is slow and right. */
 int lzs_decompress_batch_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                                        const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks, void *hip_stream);
+
+/*
+ * PACKED COMPRESSION: lzs_compress_batch_device() from packed blocks to packed rooms, with the addressing, the
+ * rule for entries that are not blocks and the argument checks of "PACKED streams" above; nblocks == 0 is LZS_OK and touches nothing.
+ * A drained packet queue, a shard with its offset table or the output of lzs_decompress_batch_packed_device() is compressed where it
+ * lies, into rooms sized on the device: no input slots, no nblocks x LZS_COMPRESSED_MAX(largest) of output slots.
+ *
+ * lzs_compressed_bound_packed_device: d_bound[b] = LZS_COMPRESSED_MAX(length of block b) -- it fits 32 bits for every length up to
+ * LZS_BLOCK_MAX --, 0 for an entry that is not a block (input offsets that decrease where d_in_len is NULL, a length above
+ * LZS_BLOCK_MAX).  lzs_offsets_from_sizes_device() makes the rooms of it.  d_in_off is required and 8-byte aligned (with d_in_len
+ * given it is not read), d_bound must not be the array d_in_len.
+ *
+ * lzs_compress_batch_packed_device: block b is written at d_out + d_out_off[b]; its room is its out_cap.  d_out_len[b] and bytes
+ * [0, d_out_len[b]) of the room are byte for byte what lzs_compress_batch_device() gives for that block alone with out_cap = its
+ * room, the cut included.  Containment: a block stores only inside its own room; the bytes of the room past d_out_len[b] are
+ * unspecified, as the strided call leaves them.  Nothing is read outside the aligned 32-bit words that hold the block's own bytes.
+ * An entry that is not a block: d_out_len[b] = 0, nothing of it read or written, the others unaffected.  d_in and d_out must not
+ * overlap; d_out_len must not be the array d_in_len (LZS_E_ARG: it carries the blocks' class codes during the launch).  LZS_VERIFY's
+ * sampled self-check covers the strided call only.
+ *
+ * lzs_compact_packed_device: lzs_compact_device() with slot b at d_src + d_src_off[b] (only nblocks entries are read) -- the scan of
+ * d_len into d_offsets (nblocks + 1 entries), then the gather.  d_dense must hold sum(d_len) bytes and must not overlap d_src.
+ * Unlike lzs_compact_device() an empty call writes nothing, not even d_offsets[0].
+ */
+int lzs_compressed_bound_packed_device(uint32_t *d_bound, const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks,
+                                       void *hip_stream);
+int lzs_compress_batch_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                     const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks, void *hip_stream);
+int lzs_compact_packed_device(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_len,
+                              size_t nblocks, void *hip_stream);
 
 /*
  * Host-buffer batches: same per-block contract, buffers in host memory.  The call

@@ -109,6 +109,20 @@ int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off
                                           void *d_states, uint8_t *d_status, size_t npackets, void *hip_stream);
 
 /*
+ * lzs_compress_channels_device() from PACKED packets to packed rooms: packet b lies at d_in + d_in_off[b] and is
+ * compressed to d_out + d_out_off[b] with d_out_off[b + 1] - d_out_off[b] bytes of room, its out_cap -- addressing, containment,
+ * entries that are not a block and argument checks as for "PACKED streams" and "PACKED COMPRESSION" in lzs_batch.h; d_states must be
+ * given and 4-byte aligned.  One packet per channel per call.  Every packet's bytes, d_out_len[b], d_status[b] (END_MARKER |
+ * INPUT_FINISHED | INPUT_STARVED = 0x07, or 0x0B with NO_OUTPUT_BUFFER_SPACE in END_MARKER's place where the room cut it) and its
+ * channel's whole slot are those of lzs_compress_channels_device() for that packet alone with out_cap = its room.  A slot with
+ * hist_len > 2047 gets ERROR and d_out_len[b] = 0, nothing changed; an entry that is not a block gets ERROR and d_out_len[b] = 0 and
+ * its channel's slot is not touched.  lzs_compressed_bound_packed_device() sizes the rooms.  Packed bursts are not offered.
+ */
+int lzs_compress_channels_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                        const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                        void *d_states, uint8_t *d_status, size_t npackets, void *hip_stream);
+
+/*
  * BURSTS: many packets per channel in one call -- a queue drained as it stands, busy links with many packets, most with none.
  *
  * The arguments are those of the calls above, and three more: nchannels (the slots in d_states), and a device work area

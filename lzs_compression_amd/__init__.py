@@ -13,6 +13,7 @@ from .api import (IncrementalCompressor, IncrementalDecompressor, LzsError, back
 from .api import (STATUS_END_MARKER, STATUS_ERROR, STATUS_INPUT_FINISHED, STATUS_INPUT_STARVED, STATUS_NO_OUTPUT_BUFFER_SPACE)
 from .api import decompress_blocks_dense, decompressed_sizes
 from .api import decompress_channels_packed, decompress_dense, decompress_packed, decompressed_sizes_packed, offsets_from_sizes
+from .api import compact_packed, compress_channels_packed, compress_dense, compress_packed, compressed_bounds_packed
 from . import workload
 
 __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_bytes", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
@@ -22,4 +23,5 @@ __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_byt
            "decompress_stream", "decompressed_max", "incremental_compress", "last_error", "lib", "release_thread_cache", "workload",
            "STATUS_END_MARKER", "STATUS_ERROR", "STATUS_INPUT_FINISHED", "STATUS_INPUT_STARVED", "STATUS_NO_OUTPUT_BUFFER_SPACE",
            "decompress_blocks_dense", "decompressed_sizes",
-           "decompress_channels_packed", "decompress_dense", "decompress_packed", "decompressed_sizes_packed", "offsets_from_sizes"]
+           "decompress_channels_packed", "decompress_dense", "decompress_packed", "decompressed_sizes_packed", "offsets_from_sizes",
+           "compact_packed", "compress_channels_packed", "compress_dense", "compress_packed", "compressed_bounds_packed"]

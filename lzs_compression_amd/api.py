@@ -116,6 +116,15 @@ def lib() -> ctypes.CDLL:
             L.lzs_decompress_batch_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
             L.lzs_decompress_channels_packed_device.restype = ctypes.c_int
             L.lzs_decompress_channels_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        if hasattr(L, "lzs_compress_batch_packed_device"):        # (the same: packed compression)
+            L.lzs_compressed_bound_packed_device.restype = ctypes.c_int
+            L.lzs_compressed_bound_packed_device.argtypes = [_vp, _vp, _vp, _sz, _vp]
+            L.lzs_compress_batch_packed_device.restype = ctypes.c_int
+            L.lzs_compress_batch_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+            L.lzs_compress_channels_packed_device.restype = ctypes.c_int
+            L.lzs_compress_channels_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+            L.lzs_compact_packed_device.restype = ctypes.c_int
+            L.lzs_compact_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp]
         _lib = L
     return _lib
 
@@ -498,6 +507,121 @@ def decompress_dense(data, in_off, in_len=None, align: int = 1, stream=None):
         raise ValueError(f"decompress_dense: block {first_bad} does not end in an end marker (status 0x{its_status:02x})")
     dense = torch.empty(total, dtype=torch.uint8, device=data.device)
     decompress_packed(data, in_off, dense, offsets, in_len=in_len, out_len=size, stream=stream)
+    return dense, offsets
+
+
+# ------------------------------- packed compression (lzs_batch.h "PACKED COMPRESSION", lzs_channels.h)
+def compressed_bounds_packed(in_off, in_len=None, bound=None, stream=None):
+    """lzs_compressed_bound_packed_device(): bound[b] = LZS_COMPRESSED_MAX(length of packed block b) -- int32 [nblocks], the bits of
+    a uint32 --, 0 for an entry that is not a block.  ``in_off``: int64 [nblocks + 1], or [nblocks] with ``in_len`` (int32), which
+    then says the lengths.  offsets_from_sizes(bound, align) makes the rooms of it.  Asynchronous on ``stream``."""
+    import torch
+    assert in_off.is_cuda and in_off.dtype == torch.int64 and in_off.dim() == 1 and in_off.is_contiguous(), \
+        "offsets are a contiguous CUDA int64 tensor"
+    if in_len is not None:
+        assert in_len.is_cuda and in_len.dtype == torch.int32 and in_len.dim() == 1 and in_len.is_contiguous()
+        nb = in_len.numel()
+        assert in_off.numel() >= nb
+    else:
+        assert in_off.numel() >= 1, "without in_len the offsets have nblocks + 1 entries"
+        nb = in_off.numel() - 1
+    if bound is None:
+        bound = torch.empty(nb, dtype=torch.int32, device=in_off.device)
+    assert bound.is_cuda and bound.dtype == torch.int32 and bound.numel() == nb and bound.is_contiguous()
+    _check(lib().lzs_compressed_bound_packed_device(bound.data_ptr(), in_off.data_ptr(), None if in_len is None else in_len.data_ptr(),
+                                                    nb, _stream_handle(stream)))
+    return bound
+
+
+def compress_packed(data, in_off, out, out_off, in_len=None, out_len=None, stream=None):
+    """lzs_compress_batch_packed_device(): block b (data[in_off[b]:in_off[b + 1]], or ``in_len[b]`` bytes at in_off[b]) compressed
+    to out[out_off[b]:out_off[b + 1]] -- that slice is its room, its out_capacity, and nothing outside it is written for the block.
+    ``data``, ``out``: CUDA uint8, one dimension, not overlapping; ``out_off``: int64 [nblocks + 1].  Returns (out, out_len int32
+    [nblocks]); an entry that is not a block has length 0.  Asynchronous."""
+    import torch
+    nb = _packed_output(out, out_off)
+    _packed_input(data, in_off, in_len, nb)
+    if out_len is None:
+        out_len = torch.empty(nb, dtype=torch.int32, device=data.device)
+    assert out_len.is_cuda and out_len.dtype == torch.int32 and out_len.numel() == nb and out_len.is_contiguous()
+    _check(lib().lzs_compress_batch_packed_device(
+        _ptr(out, out_off), out_off.data_ptr(), out_len.data_ptr(), _ptr(data, in_off), in_off.data_ptr(),
+        None if in_len is None else in_len.data_ptr(), nb, _stream_handle(stream)))
+    return out, out_len
+
+
+def compress_channels_packed(data, in_off, channels, states, out, out_off, in_len=None, out_len=None, status=None, stream=None):
+    """lzs_compress_channels_packed_device(): compress_channels() from packed packets to packed rooms, one packet per channel per
+    call (``channels``: int32 [npackets] or None for packet b on channel b; ``states`` from new_channel_states).  Returns (out,
+    out_len int32, status uint8: 0x07, or 0x0B where the room cut the packet, STATUS_ERROR for an entry that is not a block or a
+    slot that is no state).  Asynchronous."""
+    import torch
+    nb = _packed_output(out, out_off)
+    _packed_input(data, in_off, in_len, nb)
+    if out_len is None:
+        out_len = torch.empty(nb, dtype=torch.int32, device=data.device)
+    assert out_len.is_cuda and out_len.dtype == torch.int32 and out_len.numel() == nb and out_len.is_contiguous()
+    if status is None:
+        status = torch.empty(nb, dtype=torch.uint8, device=data.device)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.numel() == nb and status.is_contiguous()
+    if channels is not None:
+        assert channels.is_cuda and channels.dtype == torch.int32 and channels.numel() == nb and channels.is_contiguous()
+    assert states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()
+    _check(lib().lzs_compress_channels_packed_device(
+        _ptr(out, out_off), out_off.data_ptr(), out_len.data_ptr(), _ptr(data, in_off), in_off.data_ptr(),
+        None if in_len is None else in_len.data_ptr(), None if channels is None else channels.data_ptr(), states.data_ptr(),
+        status.data_ptr(), nb, _stream_handle(stream)))
+    return out, out_len, status
+
+
+def compact_packed(src, src_off, lengths, stream=None, dense=None, offsets=None):
+    """lzs_compact_packed_device(): compact() with slot b at src[src_off[b]:] -- the rooms of compress_packed.  Returns (dense
+    uint8, offsets int64 [nblocks + 1]): offsets is the scan of ``lengths`` (int32 [nblocks]), dense[offsets[b]:offsets[b + 1]] the
+    first lengths[b] bytes of slot b.  ``dense`` (at least sum(lengths) bytes, not overlapping ``src``; by default as large as
+    ``src``) and ``offsets`` may be passed in.  Asynchronous."""
+    import torch
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()
+    assert lengths.is_cuda and lengths.dtype == torch.int32 and lengths.dim() == 1 and lengths.is_contiguous()
+    nb = lengths.numel()
+    assert src_off.is_cuda and src_off.dtype == torch.int64 and src_off.is_contiguous() and src_off.numel() >= nb
+    if offsets is None:
+        offsets = torch.empty(nb + 1, dtype=torch.int64, device=src.device)
+    if dense is None:
+        dense = torch.empty(src.numel(), dtype=torch.uint8, device=src.device)
+    assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.numel() == nb + 1 and offsets.is_contiguous()
+    assert dense.is_cuda and dense.dtype == torch.uint8 and dense.is_contiguous()
+    if nb == 0:
+        offsets.zero_()                                            # (the C call touches nothing for an empty batch)
+        return dense, offsets
+    _check(lib().lzs_compact_packed_device(_ptr(dense, offsets), offsets.data_ptr(), _ptr(src, offsets), src_off.data_ptr(),
+                                           lengths.data_ptr(), nb, _stream_handle(stream)))
+    return dense, offsets
+
+
+def compress_dense(data, in_off, in_len=None, align: int = 16, stream=None):
+    """Packed blocks compressed into ONE dense byte string of independent LZS streams: compressed_bounds_packed(),
+    offsets_from_sizes() at ``align`` for the rooms, one host read of their total, one allocation of the rooms, compress_packed(),
+    the scan of the lengths, one host read of the dense total, one allocation of exactly that, compact_packed().  Returns (dense
+    uint8 [total], offsets int64 [nblocks + 1]); stream b is dense[offsets[b]:offsets[b + 1]], and decompress_dense(dense, offsets)
+    gives the blocks back.  An entry that is not a block becomes an empty stream.
+
+    Peak device memory: the rooms (the sum of LZS_COMPRESSED_MAX(len[b]) rounded up to ``align``: 9/8 of the data and 3 to
+    3 + ``align`` bytes a block) plus the result plus three small arrays -- the bounds, which become the lengths (int32 [nblocks]),
+    the rooms' offsets and the result's offsets (int64 [nblocks + 1] each).  No input slots and no nblocks x max anything: the
+    strided route needs nblocks * max(len) bytes of input slots and nblocks * LZS_COMPRESSED_MAX(max(len)) of output slots
+    beside the same result.  Two host reads, which wait for the work before them."""
+    import torch
+    nb = _packed_input(data, in_off, in_len)
+    if nb == 0:
+        return torch.empty(0, dtype=torch.uint8, device=data.device), torch.zeros(1, dtype=torch.int64, device=data.device)
+    size = compressed_bounds_packed(in_off, in_len, stream=stream)
+    room_off = offsets_from_sizes(size, align, stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        rooms = torch.empty(int(room_off[nb].cpu()), dtype=torch.uint8, device=data.device)          # the first host read
+        compress_packed(data, in_off, rooms, room_off, in_len=in_len, out_len=size, stream=stream)   # (the bounds are spent: the lengths take their place)
+        offsets = offsets_from_sizes(size, 1, stream=stream)
+        dense = torch.empty(int(offsets[nb].cpu()), dtype=torch.uint8, device=data.device)           # the second host read
+    compact_packed(rooms, room_off, size, stream=stream, dense=dense, offsets=offsets)
     return dense, offsets
 
 

@@ -25,6 +25,31 @@ constexpr uint32_t kChanStateBytes = 2112u, kChanHistAt = 64u;
 
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// Entry b of a packed compress call (include/lzs/lzs_batch.h "PACKED streams"; DESIGN.md 3.15): its input at `from`, n bytes (in_len[b],
+// or up to in_off[b + 1] without in_len), its output at `to` with `room` bytes (up to out_off[b + 1], clamped to 0xFFFFFFFF).  false:
+// not a block -- offsets that decrease, or more than LZS_BLOCK_MAX bytes -- and n = room = 0: nothing of it is read or written.
+__device__ __forceinline__ bool packed_entry(const uint64_t *in_off, const uint32_t *in_len, const uint64_t *out_off, uint32_t b,
+                                             uint64_t &from, uint32_t &n, uint64_t &to, uint32_t &room)
+{
+    from = in_off[b];
+    to = out_off[b];
+    const uint64_t to_end = out_off[b + 1u];
+    bool ok = to_end >= to;
+    uint64_t len;
+    if (in_len) {
+        len = in_len[b];
+    } else {
+        const uint64_t next = in_off[b + 1u];
+        ok = ok && next >= from;
+        len = next - from;
+    }
+    ok = ok && len <= 0xC0000000ull;                               // LZS_BLOCK_MAX
+    const uint64_t space = to_end - to;
+    n = ok ? (uint32_t)len : 0u;
+    room = ok ? (space < 0xFFFFFFFFull ? (uint32_t)space : 0xFFFFFFFFu) : 0u;
+    return ok;
+}
+
 // A value the optimiser may not look through (keeps a select a select, a compare a compare).
 template <class T> __device__ __forceinline__ T opaque(T x) { asm volatile("" : "+v"(x)); return x; }
 

@@ -58,6 +58,36 @@ void lzs_gather_slots_kernel(uint8_t *__restrict__ dense, const uint64_t *__rest
     if (threadIdx.x < n - done) d[done + threadIdx.x] = s[done + threadIdx.x];
 }
 
+// The same with slot b at src + src_off[b] -- the rooms of a packed compress launch (lzs_compact_packed_device; DESIGN.md 3.15).
+__global__ __launch_bounds__(256)
+void lzs_gather_packed_kernel(uint8_t *__restrict__ dense, const uint64_t *__restrict__ offsets,
+                              const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                              const uint32_t *__restrict__ len, uint32_t nblocks)
+{
+    const uint32_t b = blockIdx.x;
+    if (b >= nblocks) return;
+    const uint8_t *s = src + src_off[b];
+    uint8_t *d = dense + offsets[b];
+    const uint32_t n = len[b];
+    // head bytes until d is 4-aligned, then dst-aligned words assembled from two aligned
+    // source words, then tail bytes
+    const uint32_t head = (uint32_t)((4u - ((uintptr_t)d & 3u)) & 3u);
+    const uint32_t h = head < n ? head : n;
+    if (threadIdx.x < h) d[threadIdx.x] = s[threadIdx.x];
+    const uint32_t words = (n - h) >> 2;
+    const uint8_t *sb = s + h;
+    const uint32_t shift = (uint32_t)((uintptr_t)sb & 3u);
+    const uint32_t *sw = reinterpret_cast<const uint32_t *>(sb - shift);
+    uint32_t *dw = reinterpret_cast<uint32_t *>(d + h);
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) {
+        const uint32_t lo = sw[i];
+        const uint32_t hi = shift ? sw[i + 1] : 0u;
+        dw[i] = __builtin_amdgcn_alignbyte(hi, lo, shift);
+    }
+    const uint32_t done = h + 4 * words;
+    if (threadIdx.x < n - done) d[done + threadIdx.x] = s[done + threadIdx.x];
+}
+
 // ---------------------------------------------------------------------------------
 // lzs_decompress_incremental(): one call's worth of decoding, resumable.
 // reference lzs-decompression.c:459-743 (a 9-state machine over a 32-bit queue; here the same

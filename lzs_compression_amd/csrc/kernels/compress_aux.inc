@@ -65,6 +65,80 @@ void lzs_classify_blocks_kernel(uint32_t *__restrict__ out_len, const uint8_t *_
     }
 }
 
+// The same for a packed launch (lzs_compress_packed_wg_kernel; DESIGN.md 3.15): block b lies at in + in_off[b]; the counting and the
+// thresholds are those above, line for line (a copy: a body shared with lzs_classify_blocks_kernel moved that kernel's
+// instructions).  An entry that is not a block gets its length, 0, HERE: that is no variant's code, so none of them serves it.
+__global__ __launch_bounds__(256)
+void lzs_classify_packed_kernel(uint32_t *__restrict__ out_len, const uint64_t *__restrict__ out_off, const uint8_t *__restrict__ in,
+                                const uint64_t *__restrict__ in_off, const uint32_t *__restrict__ in_len, uint32_t nblocks,
+                                uint32_t allow, uint32_t catch_all, uint32_t *__restrict__ h_seen, uint32_t id)
+{
+    __shared__ uint32_t seen[4][128];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const uint32_t b = blockIdx.x * 4u + wv;
+    if (b >= nblocks) return;
+    uint64_t from, to;
+    uint32_t n, room;
+    if (!packed_entry(in_off, in_len, out_off, b, from, n, to, room)) {
+        if (lane == 0) out_len[b] = 0;
+        return;
+    }
+    const uint8_t *src = in + from;
+    uint32_t cls = 1u;
+    if (n >= 2049u) {                                  // (a shorter block is over before the choice could matter)
+        seen[wv][lane] = 0; seen[wv][64u + lane] = 0;
+        __builtin_amdgcn_wave_barrier();
+        // positions 32 lane .. 32 lane + 31 and the byte after them: two 16-byte loads a lane (byte loads at a stride of 32
+        // were 33 requests of 64 sectors each for 2 KiB: the classifier took 0.1 ms of a 14.7 ms launch), the byte after from
+        // the next lane's first word (the last lane's from memory: n >= 2049)
+        const bool src16 = ((uintptr_t)src & 15u) == 0, src4 = ((uintptr_t)src & 3u) == 0;
+        const uint4 lo = load16(src, 32u * lane, n, src16, src4), hi = load16(src, 32u * lane + 16u, n, src16, src4);
+        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        uint32_t after = (uint32_t)__shfl_down((int)lo.x, 1, 64) & 0xFFu;
+        if (lane == 63u) after = src[2048];
+        uint32_t prev = w[0] & 0xFFu;
+#pragma unroll
+        for (uint32_t i = 1; i <= 32u; i++) {
+            const uint32_t cur = i < 32u ? (w[i >> 2] >> (8u * (i & 3u))) & 0xFFu : after;
+            const uint32_t h = (((prev | (cur << 8)) * 40503u) >> 4) & 4095u;
+            // (looked at first: on a block of runs all sixty-four lanes want the same bit thirty-two times over, and
+            // same-address atomics of one instruction take their turns -- 0.1 ms of a 2.7 ms launch on the low-entropy class)
+            if (!((seen[wv][h >> 5] >> (h & 31u)) & 1u)) atomicOr(&seen[wv][h >> 5], 1u << (h & 31u));
+            prev = cur;
+        }
+        __builtin_amdgcn_wave_barrier();
+        uint32_t c2 = (uint32_t)__builtin_popcount(seen[wv][lane]) + (uint32_t)__builtin_popcount(seen[wv][64u + lane]);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) c2 += (uint32_t)__shfl_xor((int)c2, m, 64);
+        cls = c2 <= kClassFewMax ? 2u : (c2 >= kClassManyMin ? 3u : 1u);
+    }
+    if (lane == 0) {
+        out_len[b] = kClassCode | (((allow >> cls) & 1u) ? cls : catch_all);
+        if (h_seen && (blockIdx.x & 63u) == 0u) __hip_atomic_store(&h_seen[cls], id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// d_bound[b] = LZS_COMPRESSED_MAX(length of packed block b), 0 for an entry that is not a block: the rooms' sizes before
+// compression (lzs_compressed_bound_packed_device).  At most 0xC0000000 + 0x18000000 + 3: it fits 32 bits.
+__global__ __launch_bounds__(256)
+void lzs_compressed_bound_packed_kernel(uint32_t *__restrict__ bound, const uint64_t *__restrict__ in_off,
+                                        const uint32_t *__restrict__ in_len, uint32_t nblocks)
+{
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= nblocks) return;
+    uint64_t len;
+    bool ok = true;
+    if (in_len) {
+        len = in_len[b];
+    } else {
+        const uint64_t from = in_off[b], next = in_off[b + 1u];
+        ok = next >= from;
+        len = next - from;
+    }
+    ok = ok && len <= 0xC0000000ull;                               // LZS_BLOCK_MAX
+    bound[b] = ok ? (uint32_t)(len + (len + 7u) / 8u + 3u) : 0u;
+}
+
 // Segment k's bits (nbits[k] of them, MSB first from bit 0 of its slot) go to bit bit_at[k] of the
 // stream; the last segment is followed by the end marker 1 1 0000000.  `out` is 4-aligned and
 // zeroed.  A destination word is assembled from the two source words it spans (round 6: rounds 1-5 ORed every source

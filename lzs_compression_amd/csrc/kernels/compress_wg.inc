@@ -802,6 +802,9 @@ __device__ __forceinline__ u32x4 wg_view_read16(const WgJob &job, uint32_t q)
 }
 #endif
 
+// (ENTRY changes nothing in the code: the packed entries below take instance 1, so that every strided entry stays the only caller
+// of the instance it had -- as a second caller of that one they moved the strided kernels' instructions; DESIGN.md 3.15)
+template <int ENTRY = 0>
 __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgOut o)
 {
     const uint32_t tid  = threadIdx.x;
@@ -1401,6 +1404,49 @@ void lzs_compress_blocks_wg_kernel(uint8_t *__restrict__ out, size_t out_stride,
     o.limit = out_cap; o.ored = false;
     wg_compress_job(L, job, o);
 }
+
+// The same from PACKED blocks to rooms (include/lzs/lzs_batch.h "PACKED streams"; DESIGN.md 3.15): block b lies at in + in_off[b] and
+// is written at out + out_off[b]; its room, out_off[b + 1] - out_off[b], is its capacity AND where its stores stop, so the
+// neighbour's first byte, which lies right behind, is never touched.  An entry that is not a block gets length 0 here when the
+// kernel runs alone (`serve` 0); under the variants' protocol lzs_classify_packed_kernel has written that 0 already, and 0 is no
+// variant's code.  (An entry of its own beside lzs_compress_blocks_wg_kernel, not a body shared with it, and its own instance of
+// wg_compress_job: either kind of sharing moved that kernel's instructions in some variants.)
+#ifdef LZS_WGV_WAVES
+__global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(LZS_WGV_WAVES, LZS_WGV_WAVES)))
+#else
+__global__ __launch_bounds__(kWgThreads)
+#endif
+void lzs_compress_packed_wg_kernel(uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off, uint32_t *__restrict__ out_len,
+                                   const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                   const uint32_t *__restrict__ in_len, uint32_t nblocks, uint32_t serve)
+{
+    __shared__ BlkLds L;
+    const uint32_t b = blockIdx.x;
+    if (b >= nblocks) return;
+    if (serve != 0u) {                                         // (as in lzs_compress_blocks_wg_kernel)
+        uint32_t code;
+        asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(code) : "s"(out_len + b) : "memory");
+        if (code != serve) return;
+    }
+    uint64_t from, to;
+    uint32_t n, room;
+    if (!packed_entry(in_off, in_len, out_off, b, from, n, to, room)) {
+        if (threadIdx.x == 0) out_len[b] = 0;
+        return;
+    }
+    WgJob job;
+    job.src = in + from;
+    job.n = n;
+    job.cend = job.n; job.c0 = 0; job.w0 = 0; job.last = true;
+    job.out_len = out_len + b; job.exit_pos = nullptr; job.nbits = nullptr; job.open_info = nullptr;
+    WgOut o;
+    o.flushed = 0; o.head = 0;
+    o.dst = out + to;
+    o.cap = room;
+    o.aligned4 = ((uintptr_t)o.dst & 3u) == 0;
+    o.limit = room; o.ored = false;
+    wg_compress_job<1>(L, job, o);
+}
 #endif  // !LZS_WGV_CHANNELS
 
 // One long stream cut into segments of `seg` bytes (a multiple of 64), one workgroup each.  The
@@ -1512,6 +1558,66 @@ void lzs_compress_channels_wg_kernel(uint8_t *__restrict__ out, size_t out_strid
     o.aligned4 = ((uintptr_t)o.dst & 3u) == 0;
     o.limit = out_cap; o.ored = false;
     wg_compress_job(L, job, o);
+    // ---- the new history: hist[0, H) = view[n - H, n), hist[H, 2048) = 0 (the decoder writes the same bytes)
+    __syncthreads();                                           // every read of the ring and of the old history is done
+    const uint32_t H = job.n < kWindow ? job.n : kWindow, base = job.n - H;
+    static_assert(kWgRingWords >= 512u && kWgThreads * 2u >= 512u, "the 2048 bytes of history are staged in the ring");
+    for (uint32_t w = threadIdx.x; w < 512u; w += kWgThreads) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t i = 4u * w + k;
+            if (i < H) v |= wg_view_byte(job, base + i) << (8u * k);
+        }
+        L.ring[w] = v;
+    }
+    __syncthreads();
+    uint32_t *const hist = reinterpret_cast<uint32_t *>(st + kChanHistAt);
+    for (uint32_t w = threadIdx.x; w < 512u; w += kWgThreads) hist[w] = L.ring[w];
+    if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(st) = H;
+}
+// The same from PACKED packets to rooms (include/lzs/lzs_channels.h; DESIGN.md 3.15): packet b lies at in + in_off[b], its room at
+// out + out_off[b] is its capacity and where its stores stop.  An entry that is not a block gets ERROR and length 0 before
+// anything of it -- its channel's slot included -- is looked at.  (An entry of its own, as lzs_compress_packed_wg_kernel is.)
+#ifdef LZS_WGV_WAVES
+__global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(LZS_WGV_WAVES, LZS_WGV_WAVES)))
+#else
+__global__ __launch_bounds__(kWgThreads)
+#endif
+void lzs_compress_channels_packed_wg_kernel(uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off, uint32_t *__restrict__ out_len,
+                                            const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                            const uint32_t *__restrict__ in_len, const uint32_t *__restrict__ channel,
+                                            uint8_t *__restrict__ states, uint8_t *__restrict__ status, uint32_t npackets)
+{
+    __shared__ BlkLds L;
+    const uint32_t b = blockIdx.x;
+    if (b >= npackets) return;
+    uint64_t from, to;
+    uint32_t len, room;
+    if (!packed_entry(in_off, in_len, out_off, b, from, len, to, room)) {
+        if (threadIdx.x == 0) { out_len[b] = 0; if (status) status[b] = 0x10u; }
+        return;
+    }
+    const uint32_t ch = channel ? channel[b] : b;
+    uint8_t *const st = states + (size_t)ch * kChanStateBytes;
+    const uint32_t h = uniform(*reinterpret_cast<const uint32_t *>(st));
+    if (h > kWindow) {                                         // not a state: nothing is written, nothing changes
+        if (threadIdx.x == 0) { out_len[b] = 0; if (status) status[b] = 0x10u; }
+        return;
+    }
+    WgJob job;
+    job.src = in + from;
+    job.hist = st + kChanHistAt; job.hlen = h;
+    job.n = h + len;
+    job.cend = job.n; job.c0 = h; job.w0 = 0; job.last = true;
+    job.out_len = out_len + b; job.exit_pos = nullptr; job.nbits = nullptr; job.open_info = nullptr;
+    job.status = status ? status + b : nullptr;
+    WgOut o;
+    o.flushed = 0; o.head = 0;
+    o.dst = out + to;
+    o.cap = room;
+    o.aligned4 = ((uintptr_t)o.dst & 3u) == 0;
+    o.limit = room; o.ored = false;
+    wg_compress_job<1>(L, job, o);
     // ---- the new history: hist[0, H) = view[n - H, n), hist[H, 2048) = 0 (the decoder writes the same bytes)
     __syncthreads();                                           // every read of the ring and of the old history is done
     const uint32_t H = job.n < kWindow ? job.n : kWindow, base = job.n - H;

@@ -195,6 +195,19 @@ int lzs_hip_launch_decompress_channels_packed(void *d_out, const uint64_t *d_out
                                               const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
                                               void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
 int lzs_hip_launch_scan_sizes(uint64_t *d_offsets, const uint32_t *d_size, uint32_t align, uint32_t nblocks, void *stream);
+/* Packed compression (lzs_packed.c checks the arguments): block b lies at d_in + d_in_off[b] and is compressed to
+ * d_out + d_out_off[b] with d_out_off[b + 1] - d_out_off[b] bytes of room, its capacity.  lzs_hip_launch_compress_packed takes the
+ * decisions of lzs_hip_launch_compress (the variants by class; LZS_VERIFY does not cover it); d_bound[b] = LZS_COMPRESSED_MAX of
+ * block b's length, 0 for an entry that is not a block; lzs_hip_launch_compact_packed is lzs_hip_launch_compact from rooms. */
+int lzs_hip_launch_compressed_bound_packed(uint32_t *d_bound, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks,
+                                           void *stream);
+int lzs_hip_launch_compress_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                   const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream);
+int lzs_hip_launch_compress_channels_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                            const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                            void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
+int lzs_hip_launch_compact_packed(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off,
+                                  const uint32_t *d_len, uint32_t nblocks, void *stream);
 
 #ifdef __cplusplus
 }

@@ -372,6 +372,39 @@ static int verify_launch(void *d_out, size_t out_stride, uint32_t out_cap, uint3
     return 0;
 }
 
+// LZS_VARIANT=text|few|lit (development, read once) gives every block that variant: 1, 2, 3; 0: the blocks' classes decide.
+static int forced_variant(void)
+{
+    static const int forced = [] {
+        const char *v = getenv("LZS_VARIANT");
+        return !v ? 0 : (v[0] == 't' ? 1 : (v[0] == 'f' ? 2 : (v[0] == 'l' ? 3 : 0)));
+    }();
+    return forced;
+}
+
+// The variants recent launches had blocks for (all three while nothing is known) as `allow`, bit c for class c; a block of another class
+// goes to `catch_all`: the default variant if that runs, else the first that does.  h_seen: where this launch's classifier leaves what
+// it met, under `id`.
+static void variant_hint(void *stream, uint32_t &allow, uint32_t &catch_all, uint32_t *&h_seen, uint32_t &id)
+{
+    int dev = 0;
+    allow = 0xEu; catch_all = 1u; h_seen = nullptr;
+    id = (uint32_t)__atomic_add_fetch(&g_hint_launch, 1u, __ATOMIC_RELAXED) | 0x80000000u;      // (never 0)
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && (h_seen = __atomic_load_n(&g_hint_seen[dev], __ATOMIC_ACQUIRE)) != nullptr) {
+        uint32_t s[4], newest = 0;
+        for (int c = 1; c <= 3; c++) { s[c] = __atomic_load_n(&h_seen[c], __ATOMIC_RELAXED); if (s[c] && (newest == 0 || (int32_t)(s[c] - newest) > 0)) newest = s[c]; }
+        // (while the stream is being captured into a graph the guess would be frozen with it: every variant is launched, so that
+        // a replay on another class of data keeps its variant -- ADVICE r05)
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (stream && hipStreamIsCapturing((hipStream_t)stream, &capturing) != hipSuccess) { capturing = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+        if (newest && capturing == hipStreamCaptureStatusNone) {
+            allow = 0;
+            for (int c = 1; c <= 3; c++) if (s[c] && newest - s[c] <= 2u) allow |= 1u << c;       // (seen by one of the last three classifiers)
+            catch_all = (allow & 2u) ? 1u : ((allow & 4u) ? 2u : 3u);
+        }
+    }
+}
+
 int lzs_hip_launch_compress(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                             const void *d_in, size_t in_stride, const uint32_t *d_in_len,
                             uint32_t in_len, uint32_t nblocks, void *stream)
@@ -412,10 +445,7 @@ int lzs_hip_launch_compress(void *d_out, size_t out_stride, uint32_t out_cap, ui
     // block's class decides, on the device (lzs_classify_blocks_kernel leaves a code in out_len[b]; every variant is launched
     // over the whole grid and a workgroup whose block is another's returns at once: ~10 us per empty grid of 16 384).
     // LZS_VARIANT=text|few|lit (development, read once) gives every block that one; small launches take the default alone.
-    static const int forced = [] {
-        const char *v = getenv("LZS_VARIANT");
-        return !v ? 0 : (v[0] == 't' ? 1 : (v[0] == 'f' ? 2 : (v[0] == 'l' ? 3 : 0)));
-    }();
+    const int forced = forced_variant();
 #define LZS_LAUNCH_VARIANT(ns, serve) \
     hipLaunchKernelGGL(ns::lzs_compress_blocks_wg_kernel, dim3(nblocks), dim3(ns::kWgThreads), 0, (hipStream_t)stream, (uint8_t *)d_out, out_stride, \
                        out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, serve)
@@ -424,24 +454,8 @@ int lzs_hip_launch_compress(void *d_out, size_t out_stride, uint32_t out_cap, ui
     else if (forced == 2) LZS_LAUNCH_VARIANT(wgv_few, 0u);
     else if (forced == 3) LZS_LAUNCH_VARIANT(wgv_lit, 0u);
     else if (forced == 0 && nblocks >= kClassifyMinBlocks) {
-        // the variants recent launches had blocks for (all three while nothing is known); a block of another class goes to the default
-        // variant if that runs, else to the first that does
-        int dev = 0;
-        uint32_t allow = 0xEu, catch_all = 1u, *h_seen = nullptr;
-        const uint32_t id = (uint32_t)__atomic_add_fetch(&g_hint_launch, 1u, __ATOMIC_RELAXED) | 0x80000000u;      // (never 0)
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && (h_seen = __atomic_load_n(&g_hint_seen[dev], __ATOMIC_ACQUIRE)) != nullptr) {
-            uint32_t s[4], newest = 0;
-            for (int c = 1; c <= 3; c++) { s[c] = __atomic_load_n(&h_seen[c], __ATOMIC_RELAXED); if (s[c] && (newest == 0 || (int32_t)(s[c] - newest) > 0)) newest = s[c]; }
-            // (while the stream is being captured into a graph the guess would be frozen with it: every variant is launched, so that
-            // a replay on another class of data keeps its variant -- ADVICE r05)
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            if (stream && hipStreamIsCapturing((hipStream_t)stream, &capturing) != hipSuccess) { capturing = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-            if (newest && capturing == hipStreamCaptureStatusNone) {
-                allow = 0;
-                for (int c = 1; c <= 3; c++) if (s[c] && newest - s[c] <= 2u) allow |= 1u << c;       // (seen by one of the last three classifiers)
-                catch_all = (allow & 2u) ? 1u : ((allow & 4u) ? 2u : 3u);
-            }
-        }
+        uint32_t allow, catch_all, *h_seen, id;
+        variant_hint(stream, allow, catch_all, h_seen, id);
         hipLaunchKernelGGL(lzs_classify_blocks_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_out_len,
                            (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, allow, catch_all, h_seen, id);
         if (allow & 2u) LZS_LAUNCH_VARIANT(wgv_text, kClassCode | 1u);
@@ -470,6 +484,54 @@ int lzs_hip_classify_blocks(uint32_t *d_codes, const void *d_in, size_t in_strid
     if (nblocks == 0) return 0;
     hipLaunchKernelGGL(lzs_classify_blocks_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_codes,
                        (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, 0xEu, 1u, (uint32_t *)nullptr, 0u);
+    return (int)hipGetLastError();
+}
+
+// Packed compression (lzs_packed.c checks the arguments): lzs_hip_launch_compress() once more with every block's
+// place, length and room read from the offset arrays by the kernels -- the same decisions in the same order (chain_mode, LZS_VARIANT,
+// kClassifyMinBlocks, allow / catch_all from what recent launches saw, all variants while capturing); the A/B kernels of
+// LZS_KERNEL= have no packed entry.  NOT covered by the sampled self-check: LZS_VERIFY (verify_every) compares strided slots, and
+// a packed launch neither counts towards its sample nor is run again.
+int lzs_hip_launch_compress_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                   const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream)
+{
+    if (nblocks == 0) return 0;
+    int chain_mode = 0;
+    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
+    const int forced = forced_variant();
+#define LZS_LAUNCH_VARIANT(ns, serve) \
+    hipLaunchKernelGGL(ns::lzs_compress_packed_wg_kernel, dim3(nblocks), dim3(ns::kWgThreads), 0, (hipStream_t)stream, (uint8_t *)d_out, d_out_off, \
+                       d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, nblocks, serve)
+    if (chain_mode != 0) LZS_LAUNCH_VARIANT(wgv_safe, 0u);
+#ifndef LZS_ONE_VARIANT
+    else if (forced == 2) LZS_LAUNCH_VARIANT(wgv_few, 0u);
+    else if (forced == 3) LZS_LAUNCH_VARIANT(wgv_lit, 0u);
+    else if (forced == 0 && nblocks >= kClassifyMinBlocks) {
+        uint32_t allow, catch_all, *h_seen, id;
+        variant_hint(stream, allow, catch_all, h_seen, id);
+        hipLaunchKernelGGL(lzs_classify_packed_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_out_len, d_out_off,
+                           (const uint8_t *)d_in, d_in_off, d_in_len, nblocks, allow, catch_all, h_seen, id);
+        if (allow & 2u) LZS_LAUNCH_VARIANT(wgv_text, kClassCode | 1u);
+        if (allow & 4u) LZS_LAUNCH_VARIANT(wgv_few, kClassCode | 2u);
+        if (allow & 8u) LZS_LAUNCH_VARIANT(wgv_lit, kClassCode | 3u);
+    }
+#endif
+    else LZS_LAUNCH_VARIANT(wgv_text, 0u);
+#undef LZS_LAUNCH_VARIANT
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (chain_mode == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) == hipSuccess) load_check_step(dev, nblocks >= 256u);     // (beside a launch that fills the device)
+    }
+    return 0;
+}
+
+int lzs_hip_launch_compressed_bound_packed(uint32_t *d_bound, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream)
+{
+    if (nblocks == 0) return 0;
+    hipLaunchKernelGGL(lzs_compressed_bound_packed_kernel, dim3((nblocks + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, d_bound, d_in_off,
+                       d_in_len, nblocks);
     return (int)hipGetLastError();
 }
 
@@ -595,6 +657,25 @@ int lzs_hip_launch_compress_channels(void *d_out, size_t out_stride, uint32_t ou
         hipLaunchKernelGGL(wgv_text_ch::lzs_compress_channels_wg_kernel, dim3(npackets), dim3(wgv_text_ch::kWgThreads), 0, (hipStream_t)stream,
                            (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
                            d_channel, (uint8_t *)d_states, d_status, npackets);
+    return (int)hipGetLastError();
+}
+
+// The same from packed packets to rooms (lzs_packed.c checks the arguments).
+int lzs_hip_launch_compress_channels_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                            const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                            void *d_states, uint8_t *d_status, uint32_t npackets, void *stream)
+{
+    if (npackets == 0) return 0;
+    int chain_mode = 0;
+    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
+    if (chain_mode != 0)
+        hipLaunchKernelGGL(wgv_safe_ch::lzs_compress_channels_packed_wg_kernel, dim3(npackets), dim3(wgv_safe_ch::kWgThreads), 0, (hipStream_t)stream,
+                           (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, d_channel, (uint8_t *)d_states,
+                           d_status, npackets);
+    else
+        hipLaunchKernelGGL(wgv_text_ch::lzs_compress_channels_packed_wg_kernel, dim3(npackets), dim3(wgv_text_ch::kWgThreads), 0, (hipStream_t)stream,
+                           (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, d_channel, (uint8_t *)d_states,
+                           d_status, npackets);
     return (int)hipGetLastError();
 }
 
@@ -772,6 +853,17 @@ int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slo
     return (int)hipGetLastError();
 }
 
+// lzs_hip_launch_compact() with slot b at d_src + d_src_off[b]: the scan of the lengths, then the gather from the rooms.
+int lzs_hip_launch_compact_packed(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off,
+                                  const uint32_t *d_len, uint32_t nblocks, void *stream)
+{
+    hipLaunchKernelGGL(lzs_scan_lengths_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_offsets, d_len, nblocks);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || nblocks == 0) return (int)e;
+    hipLaunchKernelGGL(lzs_gather_packed_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_dense, d_offsets,
+                       (const uint8_t *)d_src, d_src_off, d_len, nblocks);
+    return (int)hipGetLastError();
+}
 
 int lzs_hip_launch_decode_resume(lzs_dec_resume_t *d_state, const void *d_in, uint32_t n,
                                  void *d_out, uint32_t cap, void *stream)

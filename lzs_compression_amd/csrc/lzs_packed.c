@@ -1,9 +1,11 @@
 /*
- * lzs_packed.c -- the offset-addressed ("packed") calls (include/lzs/lzs_batch.h, lzs_channels.h; DESIGN.md 3.14):
+ * lzs_packed.c -- the offset-addressed ("packed") calls (include/lzs/lzs_batch.h, lzs_channels.h; DESIGN.md 3.14, 3.15):
  * lzs_offsets_from_sizes_device, lzs_decompressed_size_packed_device, lzs_decompress_batch_packed_device,
- * lzs_decompress_channels_packed_device.  The arguments are checked here; lzs_scan_sizes_kernel, lzs_decoded_size_packed_kernel
- * (lzs_decoded_size.hip) and lzs_decompress_packed_grp_kernel (kernels/decompress_packed.inc) do the rest.  Offsets and lengths
- * stay on the device: what they say about a single block is the kernels' to check.
+ * lzs_decompress_channels_packed_device; lzs_compressed_bound_packed_device, lzs_compress_batch_packed_device,
+ * lzs_compress_channels_packed_device, lzs_compact_packed_device.  The arguments are checked here; lzs_scan_sizes_kernel,
+ * lzs_decoded_size_packed_kernel (lzs_decoded_size.hip), lzs_decompress_packed_grp_kernel (kernels/decompress_packed.inc), the packed
+ * entries of kernels/compress_wg.inc and compress_aux.inc and lzs_gather_packed_kernel (kernels/compact_resume.inc) do the rest.
+ * Offsets and lengths stay on the device: what they say about a single block is the kernels' to check.
  */
 #include "lzs_internal.h"
 #include "lzs/lzs_channels.h"
@@ -51,7 +53,7 @@ int lzs_decompressed_size_packed_device(uint32_t *d_size, uint8_t *d_status, con
     return e ? hip_fail(e, who) : LZS_OK;
 }
 
-/* what both decoders ask of their arguments */
+/* what the decoders and the compressors ask of their arguments */
 static int check_decode(const char *who, const void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_len, const void *d_in,
                         const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks)
 {
@@ -97,5 +99,74 @@ int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off
     if (rc != LZS_OK) return rc;
     const int e = lzs_hip_launch_decompress_channels_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
                                                             d_status, (uint32_t)npackets, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compressed_bound_packed_device(uint32_t *d_bound, const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks,
+                                       void *hip_stream)
+{
+    const char *who = "lzs_compressed_bound_packed_device";
+    if (nblocks == 0) return LZS_OK;
+    if (!d_bound) return fail(LZS_E_ARG, "%s: bound is NULL", who);
+    if (!d_in_off) return fail(LZS_E_ARG, "%s: in_off is NULL", who);
+    int rc = offsets_aligned(who, "d_in_off", d_in_off);
+    if (rc != LZS_OK) return rc;
+    if (d_in_len && (const void *)d_in_len == (const void *)d_bound)
+        return fail(LZS_E_ARG, "%s: d_bound and d_in_len are the same array", who);
+    if (nblocks > 0x7FFFFFFFu) return fail(LZS_E_ARG, "%s: too many blocks (%zu)", who, nblocks);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_compressed_bound_packed(d_bound, d_in_off, d_in_len, (uint32_t)nblocks, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compress_batch_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                     const uint64_t *d_in_off, const uint32_t *d_in_len, size_t nblocks, void *hip_stream)
+{
+    const char *who = "lzs_compress_batch_packed_device";
+    if (nblocks == 0) return LZS_OK;
+    int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, nblocks);
+    if (rc != LZS_OK) return rc;
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_compress_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, (uint32_t)nblocks, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compress_channels_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                        const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                        void *d_states, uint8_t *d_status, size_t npackets, void *hip_stream)
+{
+    const char *who = "lzs_compress_channels_packed_device";
+    if (npackets == 0) return LZS_OK;
+    int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
+    if (rc != LZS_OK) return rc;
+    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
+    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_compress_channels_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
+                                                          d_status, (uint32_t)npackets, hip_stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compact_packed_device(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_len,
+                              size_t nblocks, void *hip_stream)
+{
+    const char *who = "lzs_compact_packed_device";
+    if (nblocks == 0) return LZS_OK;
+    if (!d_dense) return fail(LZS_E_ARG, "%s: dense is NULL", who);
+    if (!d_offsets) return fail(LZS_E_ARG, "%s: offsets is NULL", who);
+    if (!d_src) return fail(LZS_E_ARG, "%s: src is NULL", who);
+    if (!d_src_off) return fail(LZS_E_ARG, "%s: src_off is NULL", who);
+    if (!d_len) return fail(LZS_E_ARG, "%s: len is NULL", who);
+    int rc = offsets_aligned(who, "d_offsets", d_offsets);
+    if (rc != LZS_OK) return rc;
+    rc = offsets_aligned(who, "d_src_off", d_src_off);
+    if (rc != LZS_OK) return rc;
+    if (nblocks > 0x7FFFFFFFu) return fail(LZS_E_ARG, "%s: too many blocks (%zu)", who, nblocks);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const int e = lzs_hip_launch_compact_packed(d_dense, d_offsets, d_src, d_src_off, d_len, (uint32_t)nblocks, hip_stream);
     return e ? hip_fail(e, who) : LZS_OK;
 }
