@@ -89,6 +89,44 @@ CHANNEL_ENCODE_COUNTERS = ("src_in_history", "src_straddles", "offset_2047", "re
                            "cut")
 
 
+# ---- lzs_oracle_scan_segments (oracle/lzs_oracle.c: the enums beside it)
+SEGMENT_FIELDS = ("entry_bit", "entry_ext", "entry_off", "bytes", "out_start", "stop", "merge", "phantoms")
+SEGMENT_NEVER = 0xFFFFFFFF                      # entry_bit: the walk never got here; merge: not inside the segment
+STOP_MARKER, STOP_INPUT, STOP_FULL = 1, 2, 3    # stop
+STEP_KINDS = ("lit", "short2", "long2", "short4", "long4", "short8", "long8", "first_nibble", "nib15", "close0", "close1",
+              "close14", "close_other", "marker", "long_zero")
+STEP_WIDTH = {"lit": 9, "short2": 11, "long2": 15, "short4": 13, "long4": 17, "short8": 13, "long8": 17, "first_nibble": 4,
+              "nib15": 4, "close0": 4, "close1": 4, "close14": 4, "close_other": 4, "marker": 9, "long_zero": 13}
+OFFSET_CLASSES = ("1", "2", "127 short form", "127 long form", "128", "1024", "2047", "other")
+OFFSET_EDGES = (1023, 1024, 1025, 2046, 2047)
+_SCAN_B = 24
+
+
+class ScanCounters:
+    """What lzs_oracle_scan_segments counts, as named views of one uint64 array (``raw``) that its calls add to."""
+    _LAYOUT = (("straddle", (len(STEP_KINDS), _SCAN_B)),      # [kind][b]: steps with b of their bits in front of a border
+               ("ext_entry", (8, 16)),                       # [offset class][closing nibble, 15 = never closed]
+               ("close_at", (16,)),                          # [d + 8]: closing nibbles that start d bits behind a border
+               ("ones_seg", (2, 4)),                         # [next three bits set][entry bit & 3]: whole 0xFF segments in an extension
+               ("ones_run", (5,)),                           # [0 1 2 3 >=4] whole 0xFF segments under one extension that crosses a border
+               ("short_all_ones", (1,)),                     # borders crossed by the extension of a short token 11 1111111 1111
+               ("phantom", (5,)),                            # [0 1 2 3 >=4] end markers the guessed walk read before it merged
+               ("never", (1,)), ("never_run_max", (1,)),
+               ("src_own", (1,)), ("src_other", (1,)), ("src_straddle", (1,)), ("src_before_out0", (1,)),
+               ("before_out0_seg", (16,)),                   # [segment, 15 = later]
+               ("off_edge", (5,)), ("off_edge_first", (5,)), # [1023 1024 1025 2046 2047]; ... producing a segment's first byte
+               ("chain_max", (1,)), ("small_segs", (1,)))
+
+    def __init__(self):
+        size = sum(int(np.prod(shape)) for _, shape in self._LAYOUT)
+        self.raw = np.zeros(size, dtype=np.uint64)
+        at = 0
+        for name, shape in self._LAYOUT:
+            k = int(np.prod(shape))
+            setattr(self, name, self.raw[at:at + k].reshape(shape))
+            at += k
+
+
 class _Oracle(_Codec):
     def __init__(self):
         if not os.path.exists(_ORACLE_SO):
@@ -113,6 +151,35 @@ class _Oracle(_Codec):
             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
             ctypes.c_void_p]
+        self.lib.lzs_oracle_scan_segments.restype = ctypes.c_size_t
+        self.lib.lzs_oracle_scan_segments.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        sizes = (ctypes.c_uint32 * 4)()
+        self.lib.lzs_oracle_scan_layout(sizes)
+        assert list(sizes) == [ScanCounters().raw.size, len(SEGMENT_FIELDS), len(STEP_KINDS), _SCAN_B], list(sizes)
+
+    def scan_segments(self, data: bytes, seg: int, cap: int, file_rule: bool = False, counters: Optional[ScanCounters] = None,
+                      trace: bool = False):
+        """The plain model of a segment border (lzs_oracle_scan_segments): ``data`` cut every ``seg`` bytes, walked once from
+        bit 0 under the one-shot rule (or the file rule of lzs_decompress_concat) up to ``cap`` bytes of output, and every
+        segment walked once more from its border bit in the normal state.  Returns (bytes produced, records [nseg,
+        len(SEGMENT_FIELDS)] uint32) -- and, with ``trace``, the steps of the true walk [(bit, kind, offset, bytes, output
+        position)], one a token and one a length nibble.  ``counters``: a ScanCounters that the call adds to."""
+        nseg = (len(data) + seg - 1) // seg
+        src = ctypes.create_string_buffer(bytes(data), len(data) + 1)
+        rec = np.zeros((max(nseg, 1), len(SEGMENT_FIELDS)), dtype=np.uint32)
+        max_tok = 2 * len(data) + 1 if trace else 0   # no step is shorter than four bits
+        steps = np.zeros((max_tok, 5), dtype=np.uint32) if trace else None
+        ntok = ctypes.c_size_t(0)
+        n = self.lib.lzs_oracle_scan_segments(
+            ctypes.addressof(src), len(data), seg, int(file_rule), cap, rec.ctypes.data, nseg,
+            None if counters is None else counters.raw.ctypes.data, None if steps is None else steps.ctypes.data, max_tok,
+            ctypes.addressof(ntok))
+        if n == ctypes.c_size_t(-1).value:
+            raise MemoryError("lzs_oracle_scan_segments")
+        got = (int(n), rec[:nseg])
+        return got + (steps[:ntok.value],) if trace else got
 
     def compress_brute(self, data: bytes, cap: Optional[int] = None) -> bytes:
         return self._call(self._lzs_oracle_compress_brute, data,

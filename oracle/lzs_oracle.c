@@ -1,7 +1,8 @@
 /*
  * oracle/lzs_oracle.c -- CPU restatement of the LZS one-shot codec, and plain models of one channel packet's decoding and
  * compression (lzs_oracle_decompress_channel, lzs_oracle_compress_channel: tests/test_channel_model.py,
- * tests/test_channel_encode_model.py hold them to the reference).
+ * tests/test_channel_encode_model.py hold them to the reference), and of what a segment border of the many-wavefront stream
+ * decoders is (lzs_oracle_scan_segments: tests/test_stream_border_model.py).
  *
  * TEST INFRASTRUCTURE ONLY.  Nothing in the shipped library (liblzs.so, the
  * lzs_compression_amd package) links, loads or calls this file.  Only tests/,
@@ -655,4 +656,316 @@ size_t lzs_oracle_decompress_channel(uint8_t *out, size_t cap, const uint8_t *in
     }
     *new_h = keep;
     return count;
+}
+
+/* ------------------------------------------------------------------ */
+/* What a segment border IS, for the many-wavefront stream decoders     */
+/* (DESIGN.md 3.6): the stream in[0, n) cut every `seg` bytes, walked   */
+/* ONCE from bit 0, a bit at a time, under the one-shot rule            */
+/* (lzs_oracle_decompress: the first end marker ends it) or, with       */
+/* `file_rule`, the rule of lzs_decompress_concat (an end marker is     */
+/* followed by zero bits to the next byte, and the walk goes on with    */
+/* the history kept), up to `cap` bytes of output.  A token, and every  */
+/* length nibble, is one STEP; a step belongs to the segment in which   */
+/* its first bit lies, with all the bytes it produces.                  */
+/*                                                                      */
+/* rec[] receives SS_FIELDS words for each of the first max_seg         */
+/* segments (the enum below); counters[] (may be NULL) are ADDED to     */
+/* (the two *_MAX ones raised); trace[] (may be NULL) receives up to    */
+/* max_tok records {bit, kind, offset, bytes produced, output position} */
+/* of the steps the true walk took whole, *ntok their number.  Returns  */
+/* the bytes produced (the sum of the segments'), (size_t)-1 if memory  */
+/* ran out.                                                             */
+/*                                                                      */
+/* Second, for every segment k >= 1 the true walk reaches, the walk a   */
+/* decoder takes that knows nothing: entered at the border's own bit in */
+/* the normal state, a step at a time for as long as its steps start    */
+/* inside the segment.  SS_MERGE: after how many steps it stands on a   */
+/* step of the true walk in the same state (SS_NEVER: not inside the    */
+/* segment); SS_PHANTOMS: the end markers it read before that (it goes  */
+/* on behind them -- under the file rule from the next byte on).        */
+/*                                                                      */
+/* The model knows nothing of marks, rounds or origins: it says what    */
+/* those arrive at.                                                     */
+/* ------------------------------------------------------------------ */
+enum {                      /* a segment's record */
+    SS_ENTRY_BIT = 0,       /* bits past the border at which the first step that starts in the segment begins; SS_NEVER: the walk never got here */
+    SS_ENTRY_EXT,           /* that step is a length nibble: an extension is running ...                                */
+    SS_ENTRY_OFF,           /* ... at this offset                                                                        */
+    SS_BYTES,               /* bytes the segment's steps produce                                                         */
+    SS_OUT_START,           /* where they begin in the output                                                            */
+    SS_STOP,                /* 0, or why the walk stopped at a step of this segment: 1 end marker, 2 the input ended (in a token or not), 3 the output was full */
+    SS_MERGE,
+    SS_PHANTOMS,
+    SS_FIELDS
+};
+#define SS_NEVER 0xFFFFFFFFu
+
+enum {                      /* step kinds: the trace, and the rows of the straddle matrix */
+    SK_LIT = 0, SK_SHORT2, SK_LONG2, SK_SHORT4, SK_LONG4, SK_SHORT8, SK_LONG8,
+    SK_FIRST_NIBBLE,        /* (matrix only: a nibble right behind its length-8 token, whatever its value -- counted under its value too) */
+    SK_NIB15, SK_CLOSE0, SK_CLOSE1, SK_CLOSE14, SK_CLOSE_OTHER, SK_MARKER, SK_LONG_ZERO,
+    SK_KINDS
+};
+
+enum {                      /* counters (oracle/__init__.py: SCAN_COUNTERS has the same layout) */
+    SC_STRADDLE   = 0,                              /* [kind][b]: steps with b of their bits in front of a border, b = 0 .. width    */
+    SC_B          = 24,
+    SC_EXT_ENTRY  = SC_STRADDLE + SK_KINDS * SC_B,  /* [offset class][closing nibble, 15 = never closed]: segments entered in an extension */
+    SC_CLOSE_AT   = SC_EXT_ENTRY + 8 * 16,          /* [d + 8]: closing nibbles that start d bits behind a border, d = -8 .. 7        */
+    SC_ONES_SEG   = SC_CLOSE_AT + 16,               /* [next three bits set][entry bit & 3]: whole segments of 0xFF inside an extension */
+    SC_ONES_RUN   = SC_ONES_SEG + 8,                /* [0 1 2 3 >=4]: extensions that cross a border, by the whole 0xFF segments they cover */
+    SC_SHORT_ONES = SC_ONES_RUN + 5,                /* borders crossed by the extension of a short token 11 1111111 1111               */
+    SC_PHANTOM    = SC_SHORT_ONES + 1,              /* [0 1 2 3 >=4]: segments by the end markers the guessed walk read before it merged */
+    SC_NEVER      = SC_PHANTOM + 5,                 /* segments in which the guessed walk never merged                                  */
+    SC_NEVER_RUN_MAX,                               /* ... the most of them in a row (raised, not added)                                */
+    SC_SRC_OWN,                                     /* copying steps by where their source lies: the segment's own output,              */
+    SC_SRC_OTHER,                                   /* another segment's,                                                              */
+    SC_SRC_STRADDLE,                                /* both: it straddles the segment's output start;                                  */
+    SC_SRC_BEFORE0,                                 /* (also) in front of out[0]                                                       */
+    SC_BEFORE0_SEG,                                 /* [segment, 15 = later]: the last of these, by segment                             */
+    SC_OFF_EDGE   = SC_BEFORE0_SEG + 16,            /* [1023 1024 1025 2046 2047]: match tokens at these offsets                        */
+    SC_OFF_EDGE_FIRST = SC_OFF_EDGE + 5,            /* ... of which: producing the first byte of their segment's output                 */
+    SC_CHAIN_MAX  = SC_OFF_EDGE_FIRST + 5,          /* the longest chain of copies of copies, in segments crossed (raised)              */
+    SC_SMALL_SEGS,                                  /* segments the walk reaches that produce fewer than 2047 bytes                     */
+    SC_COUNTERS
+};
+
+static unsigned offset_class(unsigned off, int short_form)
+{
+    return off == 1 ? 0 : off == 2 ? 1 : (off == 127 && short_form) ? 2 : off == 127 ? 3 : off == 128 ? 4
+         : off == 1024 ? 5 : off == 2047 ? 6 : 7;
+}
+
+/* One step at r->at in the state (ext, off).  Returns 0 if the input lacks bits for it (nothing is consumed), else 1 with
+ * *kind, *bytes (what it produces, uncut), the new state, and *form (1 = the match token was in the 7-bit form). */
+static int scan_step(cursor_t *r, int *ext, unsigned *off, unsigned *kind, unsigned *bytes, int *form)
+{
+    *bytes = 0;
+    if (*ext) {
+        if (bits_left(r) < 4)
+            return 0;
+        unsigned e = take_bits(r, 4);
+        *bytes = e;
+        *kind = e == NIBBLE_MAX ? SK_NIB15 : e == 0 ? SK_CLOSE0 : e == 1 ? SK_CLOSE1 : e == 14 ? SK_CLOSE14 : SK_CLOSE_OTHER;
+        if (e != NIBBLE_MAX)
+            *ext = 0;
+        return 1;
+    }
+    if (bits_left(r) < 1)
+        return 0;
+    if (peek_bits(r, 1) == 0) {
+        if (bits_left(r) < 9)
+            return 0;
+        r->at += 9;
+        *kind = SK_LIT; *bytes = 1;
+        return 1;
+    }
+    if (bits_left(r) < 2)
+        return 0;
+    unsigned head, o;
+    if (peek_bits(r, 2) == 3) {
+        if (bits_left(r) < 9)
+            return 0;
+        o = peek_bits(r, 9) & 0x7F; head = 9; *form = 1;
+        if (o == 0) { r->at += 9; *kind = SK_MARKER; return 1; }
+    } else {
+        if (bits_left(r) < 13)
+            return 0;
+        o = peek_bits(r, 13) & 0x7FF; head = 13; *form = 0;
+        if (o == 0) { r->at += 13; *kind = SK_LONG_ZERO; return 1; }
+    }
+    if (bits_left(r) < head + 2)
+        return 0;
+    cursor_t q = *r;
+    q.at += head;
+    unsigned code = peek_bits(&q, 4), len, width;
+    if (code < 0xC) { len = 2 + (code >> 2); width = 2; }
+    else            { len = 5 + (code - 0xC); width = 4; }
+    if (bits_left(&q) < width)
+        return 0;
+    r->at += head + width;
+    *off = o; *bytes = len;
+    *ext = len == TOKEN_MAX;
+    *kind = len == TOKEN_MAX ? (head == 9 ? SK_SHORT8 : SK_LONG8) : width == 2 ? (head == 9 ? SK_SHORT2 : SK_LONG2)
+                                                                                : (head == 9 ? SK_SHORT4 : SK_LONG4);
+    return 1;
+}
+
+size_t lzs_oracle_scan_segments(const uint8_t *in, size_t n, size_t seg, int file_rule, size_t cap,
+                                uint32_t *rec, size_t max_seg, uint64_t *counters,
+                                uint32_t *trace, size_t max_tok, size_t *ntok)
+{
+    static const unsigned edges[5] = { 1023, 1024, 1025, 2046, 2047 };
+    const uint64_t nbits = (uint64_t)n * 8u, segbits = (uint64_t)seg * 8u;
+    const size_t   nseg = seg ? (n + seg - 1) / seg : 0;
+    const size_t   room = cap < 30 * n + 16 ? cap : 30 * n + 16;          /* a nibble gives at most 15 bytes */
+    uint32_t *state_at = (uint32_t *)calloc((size_t)nbits + 1, sizeof(uint32_t));   /* per bit: 0, or 1 | ext << 1 | offset << 2 of the true step there */
+    uint16_t *hops = (uint16_t *)malloc((room + 1) * sizeof(uint16_t));   /* per output byte: segments its chain of copies crosses */
+    uint64_t  zero[SC_COUNTERS];
+    uint64_t *ctr = counters ? counters : zero;
+    if (!state_at || !hops || seg == 0) { free(state_at); free(hops); return (size_t)-1; }
+    memset(zero, 0, sizeof(zero));
+    for (size_t k = 0; k < nseg && k < max_seg; k++) {
+        uint32_t *s = rec + k * SS_FIELDS;
+        s[SS_ENTRY_BIT] = SS_NEVER; s[SS_ENTRY_EXT] = s[SS_ENTRY_OFF] = s[SS_BYTES] = s[SS_OUT_START] = s[SS_STOP] = 0;
+        s[SS_MERGE] = SS_NEVER; s[SS_PHANTOMS] = 0;
+    }
+
+    /* ---- the true walk */
+    cursor_t r = { in, nbits, 0 };
+    size_t   count = 0, tok = 0, reached = 0;       /* reached: segments entered so far */
+    unsigned off = 0, prev_kind = SK_KINDS;
+    int      ext = 0, form = 0, stop = 0;
+    unsigned ext_ones = 0, ext_crossed = 0;         /* the extension running: whole 0xFF segments it covered, borders it crossed */
+    size_t   seg_out_start = 0;
+    unsigned chain_max = 0;
+
+    while (!stop) {
+        if (count >= cap)       { stop = 3; break; }      /* (also where the input ends with the step that filled it) */
+        if (bits_left(&r) == 0) { stop = 2; break; }
+        const uint64_t at = r.at;
+        const size_t   k = (size_t)(at / segbits);
+        if (k >= reached) {                         /* the first step that starts in segment k */
+            reached = k + 1;
+            seg_out_start = count;
+            if (k < max_seg) {
+                uint32_t *s = rec + k * SS_FIELDS;
+                s[SS_ENTRY_BIT] = (uint32_t)(at - k * segbits); s[SS_ENTRY_EXT] = (uint32_t)ext; s[SS_ENTRY_OFF] = ext ? off : 0;
+                s[SS_OUT_START] = (uint32_t)count;
+            }
+            if (ext && k > 0) {
+                ext_crossed++;
+                if (off == SHORT_MAX && form) ctr[SC_SHORT_ONES]++;
+                /* a whole segment of 0xFF inside the extension */
+                if ((k + 1) * seg <= n) {
+                    size_t i = 0;
+                    while (i < seg && in[k * seg + i] == 0xFF) i++;
+                    if (i == seg) {
+                        const int next3 = (k + 1) * seg < n && (in[(k + 1) * seg] & 0xE0) == 0xE0;
+                        ctr[SC_ONES_SEG + 4 * next3 + ((at - k * segbits) & 3)]++;
+                        ext_ones++;
+                    }
+                }
+            }
+        }
+        const int      was_ext = ext, was_form = form;
+        const unsigned was_off = off;
+        unsigned kind = 0, bytes = 0;
+        if (!scan_step(&r, &ext, &off, &kind, &bytes, &form)) {
+            /* the input ends inside this step; the one-shot decoder still takes the type bits it has (no bytes come of them) */
+            stop = 2;
+            break;
+        }
+        state_at[at] = 1u | ((uint32_t)was_ext << 1) | ((was_ext ? was_off : 0u) << 2);
+        const unsigned width = (unsigned)(r.at - at);
+        /* borders this step touches: b bits of it in front (a step is shorter than a segment: one border at most, or one at each end) */
+        for (uint64_t B = (at + segbits - 1) / segbits * segbits; B <= at + width && B < nbits; B += segbits) {
+            if (B == 0) continue;
+            const unsigned b = (unsigned)(B - at);
+            ctr[SC_STRADDLE + kind * SC_B + b]++;
+            if (was_ext && (prev_kind == SK_SHORT8 || prev_kind == SK_LONG8))
+                ctr[SC_STRADDLE + SK_FIRST_NIBBLE * SC_B + b]++;
+        }
+        if (was_ext && kind != SK_NIB15) {
+            /* a closing nibble: d bits behind the nearest border */
+            const uint64_t lo = at / segbits * segbits, hi = lo + segbits;
+            if (at - lo < 8 && lo > 0) ctr[SC_CLOSE_AT + 8 + (unsigned)(at - lo)]++;
+            if (hi - at <= 8 && hi < nbits) ctr[SC_CLOSE_AT + 8 - (unsigned)(hi - at)]++;
+            if (ext_crossed) {                      /* every segment it entered, by the nibble that closes it now */
+                ctr[SC_EXT_ENTRY + 16 * offset_class(was_off, was_form) + bytes] += ext_crossed;
+                ctr[SC_ONES_RUN + (ext_ones < 4 ? ext_ones : 4)]++;
+            }
+            ext_crossed = 0; ext_ones = 0;
+        }
+        if (kind == SK_MARKER) {
+            if (trace && tok < max_tok) {
+                trace[5 * tok + 0] = (uint32_t)at; trace[5 * tok + 1] = kind; trace[5 * tok + 2] = 0; trace[5 * tok + 3] = 0; trace[5 * tok + 4] = (uint32_t)count;
+            }
+            tok++;
+            prev_kind = kind;
+            if (!file_rule) { stop = 1; if (k < max_seg) rec[k * SS_FIELDS + SS_STOP] = 1; break; }
+            r.at = (r.at + 7u) & ~(uint64_t)7u;
+            if (r.at > nbits) r.at = nbits;
+            continue;
+        }
+        /* the bytes of this step, as many as there is room for */
+        const size_t at_out = count;
+        if (bytes && kind != SK_LIT) {
+            int own = 0, other = 0, before0 = 0;
+            for (unsigned i = 0; i < bytes && count < cap; i++, count++) {
+                unsigned h = 0;
+                if (count < off) before0 = 1;
+                else {
+                    const size_t s = count - off;
+                    if (s >= seg_out_start) { own = 1; h = hops[s]; }
+                    else                    { other = 1; h = hops[s] + 1u; }
+                }
+                hops[count] = (uint16_t)(h < 0xFFFF ? h : 0xFFFF);
+                if (h > chain_max) chain_max = h;
+            }
+            if (own && other)  ctr[SC_SRC_STRADDLE]++;
+            else if (own)      ctr[SC_SRC_OWN]++;
+            else if (other)    ctr[SC_SRC_OTHER]++;
+            if (before0) { ctr[SC_SRC_BEFORE0]++; ctr[SC_BEFORE0_SEG + (k < 15 ? k : 15)]++; }
+            if (!was_ext)
+                for (int e = 0; e < 5; e++)
+                    if (off == edges[e]) { ctr[SC_OFF_EDGE + e]++; if (at_out == seg_out_start) ctr[SC_OFF_EDGE_FIRST + e]++; }
+        } else if (bytes) {
+            hops[count++] = 0;
+        }
+        if (k < max_seg) rec[k * SS_FIELDS + SS_BYTES] += (uint32_t)(count - at_out);
+        if (trace && tok < max_tok) {
+            trace[5 * tok + 0] = (uint32_t)at; trace[5 * tok + 1] = kind; trace[5 * tok + 2] = (kind == SK_LIT || kind == SK_LONG_ZERO) ? 0 : off;
+            trace[5 * tok + 3] = (uint32_t)(count - at_out); trace[5 * tok + 4] = (uint32_t)at_out;
+        }
+        tok++;
+        prev_kind = kind;
+    }
+    if (stop != 1 && nseg) {
+        const uint64_t last = r.at < nbits ? r.at : nbits - 1;
+        const size_t   k = (size_t)(last / segbits);
+        if (k < max_seg) rec[k * SS_FIELDS + SS_STOP] = (uint32_t)stop;
+    }
+    if (ext_crossed)                                /* an extension still open when the walk stopped: never closed */
+        ctr[SC_EXT_ENTRY + 16 * offset_class(off, form) + 15] += ext_crossed;
+    if (ntok) *ntok = tok;
+    if (chain_max > ctr[SC_CHAIN_MAX]) ctr[SC_CHAIN_MAX] = chain_max;
+
+    /* ---- the guessed walk of every segment the true walk reached */
+    uint64_t never_run = 0;
+    for (size_t k = 0; k < reached; k++) {
+        uint32_t *s = k < max_seg ? rec + k * SS_FIELDS : NULL;
+        if (s && s[SS_BYTES] < WINDOW) ctr[SC_SMALL_SEGS]++;
+        if (k == 0) { if (s) s[SS_MERGE] = 0; continue; }
+        cursor_t g = { in, nbits, (uint64_t)k * segbits };
+        const uint64_t end = g.at + segbits;
+        unsigned g_off = 0, g_kind = 0, g_bytes = 0, steps = 0, phantoms = 0;
+        int      g_ext = 0, g_form = 0, merged = 0;
+        while (g.at < end && g.at < nbits) {
+            if (state_at[g.at] == (1u | ((uint32_t)g_ext << 1) | ((g_ext ? g_off : 0u) << 2))) { merged = 1; break; }
+            if (!scan_step(&g, &g_ext, &g_off, &g_kind, &g_bytes, &g_form))
+                break;
+            steps++;
+            if (g_kind == SK_MARKER) {
+                phantoms++;
+                if (file_rule) g.at = (g.at + 7u) & ~(uint64_t)7u;
+            }
+        }
+        if (s) { s[SS_MERGE] = merged ? steps : SS_NEVER; s[SS_PHANTOMS] = phantoms; }
+        ctr[SC_PHANTOM + (phantoms < 4 ? phantoms : 4)]++;
+        if (!merged) {
+            ctr[SC_NEVER]++;
+            if (++never_run > ctr[SC_NEVER_RUN_MAX]) ctr[SC_NEVER_RUN_MAX] = never_run;
+        } else
+            never_run = 0;
+    }
+    free(state_at); free(hops);
+    return count;
+}
+
+/* The sizes of what lzs_oracle_scan_segments fills in: counters, words a segment, step kinds, columns of the straddle matrix. */
+void lzs_oracle_scan_layout(uint32_t *sizes)
+{
+    sizes[0] = SC_COUNTERS; sizes[1] = SS_FIELDS; sizes[2] = SK_KINDS; sizes[3] = SC_B;
 }
