@@ -127,6 +127,55 @@ class ScanCounters:
             at += k
 
 
+# ---- lzs_oracle_compress_segments (oracle/lzs_oracle.c: the enums beside it)
+COMPRESS_SEGMENT_FIELDS = ("entry", "exit", "tokens", "bits", "bit_at", "empty", "oversized", "guess_merge", "guess_exit", "redone",
+                           "round_exit")
+COMPRESS_NEVER = 0xFFFFFFFFFFFFFFFF             # entry: a match ran over all of the segment; guess_merge: not inside the segment
+LAST_KINDS = ("lit", "short2-7", "long2-7", "ext0", "ext1", "ext2", "ext3-39", "ext40+")   # ext: length 8 and more, by its nibbles of 15
+LAST_PAST = 21                                  # 0 .. 16 bytes past the border; 17: farther, in the next segment; 18 19 20: past 1, 2, >= 3 whole segments
+FIRST_OFFSETS = (2047, 2046, 2040, 1)
+WARM_UPS = ("at 0", "first beyond", "far")
+MERGE_CLASSES = ("0", "1", "2", "3-4", ">=5", "never")
+
+
+def slot_bits(seg: int) -> int:
+    """The bits of a segment's slot, the host's figure: 8 * align16(LZS_COMPRESSED_MAX(seg))."""
+    return 8 * ((compressed_max(seg) + 15) & ~15)
+
+
+class CompressCounters:
+    """What lzs_oracle_compress_segments counts, as named views of one uint64 array (``raw``) that its calls add to."""
+    _LAYOUT = (("last", (len(LAST_KINDS), LAST_PAST)),       # [kind][past]: the last token of a segment with a border behind it
+               ("last_close", (4,)),                         # [0 1 14 other]: closing nibbles of last tokens that end past their border
+               ("last_start", (9,)),                         # [s]: last tokens that are matches, s = 1 .. 8 bytes before the border (0: farther)
+               ("one_token_last_byte", (1,)),
+               ("entry_mod64", (64,)),
+               ("first_off", (4, 3)),                        # [2047 2046 2040 1][warm-up at 0, first beyond, far]
+               ("first_straddle", (1,)), ("first_far_len", (2,)),
+               ("merge", (6,)),                              # [0 1 2 3-4 >=5 never]
+               ("one_round", (1,)), ("rounds_max", (1,)), ("fix_changes_exit", (1,)), ("fix_keeps_exit", (1,)),
+               ("never_run_max", (1,)),
+               ("long_match", (3,)),                         # [offset 1, 2, 300]: the most segments under one token
+               ("bit_at_mod32", (32,)), ("nbits_mod32", (32,)), ("under_32", (1,)), ("word_share_max", (1,)),
+               ("empty_between_sharers", (1,)), ("total_mod32", (32,)), ("marker_behind_empty", (1,)),
+               ("marker_behind_oversized", (1,)),
+               ("margin", (18,)),                            # [d + 8], d = -8 .. 8; [17]: more than 4096 bits over
+               ("over_bit_at", (4,)),                        # [0, 1-31, 32-2016, >= 2017]: oversized segments by bit_at % 2048
+               ("over_seg0", (1,)), ("over_two", (1,)), ("over_empties_one_token", (1,)),
+               ("len_mod", (5,)),                            # [n % seg: 1 63 64 255 0]
+               ("end_close", (2,)),                          # [0 14]
+               ("end_one_short", (1,)))
+
+    def __init__(self):
+        size = sum(int(np.prod(shape)) for _, shape in self._LAYOUT)
+        self.raw = np.zeros(size, dtype=np.uint64)
+        at = 0
+        for name, shape in self._LAYOUT:
+            k = int(np.prod(shape))
+            setattr(self, name, self.raw[at:at + k].reshape(shape))
+            at += k
+
+
 class _Oracle(_Codec):
     def __init__(self):
         if not os.path.exists(_ORACLE_SO):
@@ -155,6 +204,13 @@ class _Oracle(_Codec):
         self.lib.lzs_oracle_scan_segments.argtypes = [
             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        self.lib.lzs_oracle_compress_segments.restype = ctypes.c_size_t
+        self.lib.lzs_oracle_compress_segments.argtypes = [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        sizes = (ctypes.c_uint32 * 4)()
+        self.lib.lzs_oracle_compress_segments_layout(sizes)
+        assert list(sizes) == [CompressCounters().raw.size, len(COMPRESS_SEGMENT_FIELDS), len(LAST_KINDS), LAST_PAST], list(sizes)
         sizes = (ctypes.c_uint32 * 4)()
         self.lib.lzs_oracle_scan_layout(sizes)
         assert list(sizes) == [ScanCounters().raw.size, len(SEGMENT_FIELDS), len(STEP_KINDS), _SCAN_B], list(sizes)
@@ -180,6 +236,31 @@ class _Oracle(_Codec):
             raise MemoryError("lzs_oracle_scan_segments")
         got = (int(n), rec[:nseg])
         return got + (steps[:ntok.value],) if trace else got
+
+    def compress_segments(self, data: bytes, seg: int, counters: Optional[CompressCounters] = None, trace: bool = False,
+                          brute: bool = False):
+        """The plain model of a segment border of the segmented stream compressor (lzs_oracle_compress_segments): ``data`` cut
+        every ``seg`` bytes and parsed once; every segment behind the first walked once more from its own border; the host's
+        rounds simulated on those walks.  Returns (bits of all tokens, records [nseg, len(COMPRESS_SEGMENT_FIELDS)] uint64,
+        the segments to redo after each round -- its length is the number of rounds) -- and, with ``trace``, the tokens
+        [(position, offset or 0, bytes covered, bit position)].  ``counters``: a CompressCounters that the call adds to;
+        ``brute``: the written search rule instead of the chained finder."""
+        nseg = max((len(data) + seg - 1) // seg, 1)
+        src = ctypes.create_string_buffer(bytes(data), len(data) + 1)
+        rec = np.zeros((nseg, len(COMPRESS_SEGMENT_FIELDS)), dtype=np.uint64)
+        rounds = np.zeros(nseg + 1, dtype=np.uint32)          # a round settles at least one segment more
+        max_tok = len(data) if trace else 0                   # no token covers less than a byte
+        toks = np.zeros((max_tok, 4), dtype=np.uint32) if trace else None
+        ntok, nrounds = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        bits = self.lib.lzs_oracle_compress_segments(
+            ctypes.addressof(src), len(data), seg, int(brute), rec.ctypes.data, nseg, rounds.ctypes.data, rounds.size,
+            ctypes.addressof(nrounds), None if counters is None else counters.raw.ctypes.data,
+            None if toks is None else toks.ctypes.data, max_tok, ctypes.addressof(ntok))
+        if bits == ctypes.c_size_t(-1).value:
+            raise MemoryError("lzs_oracle_compress_segments")
+        assert nrounds.value <= rounds.size
+        got = (int(bits), rec, [int(v) for v in rounds[:nrounds.value]])
+        return got + (toks[:ntok.value],) if trace else got
 
     def compress_brute(self, data: bytes, cap: Optional[int] = None) -> bytes:
         return self._call(self._lzs_oracle_compress_brute, data,

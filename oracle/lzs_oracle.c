@@ -2,7 +2,8 @@
  * oracle/lzs_oracle.c -- CPU restatement of the LZS one-shot codec, and plain models of one channel packet's decoding and
  * compression (lzs_oracle_decompress_channel, lzs_oracle_compress_channel: tests/test_channel_model.py,
  * tests/test_channel_encode_model.py hold them to the reference), and of what a segment border of the many-wavefront stream
- * decoders is (lzs_oracle_scan_segments: tests/test_stream_border_model.py).
+ * decoders is (lzs_oracle_scan_segments: tests/test_stream_border_model.py) and of the segmented stream compressor
+ * (lzs_oracle_compress_segments: tests/test_stream_compress_model.py).
  *
  * TEST INFRASTRUCTURE ONLY.  Nothing in the shipped library (liblzs.so, the
  * lzs_compression_amd package) links, loads or calls this file.  Only tests/,
@@ -962,6 +963,340 @@ size_t lzs_oracle_scan_segments(const uint8_t *in, size_t n, size_t seg, int fil
     }
     free(state_at); free(hops);
     return count;
+}
+
+/* ------------------------------------------------------------------ */
+/* What a segment border IS, for the segmented stream compressor        */
+/* (DESIGN.md 3.5): in[0, n) cut every `seg` bytes (a multiple of 64,   */
+/* >= 256), parsed ONCE from byte 0 by the token loop of compress_core  */
+/* (the chained finder, or with `brute` the written rule).  A token,    */
+/* with all its length nibbles, belongs to the segment in which it      */
+/* STARTS.  The model knows nothing of slots, rounds, chains or warm-up */
+/* windows: it says what they arrive at.                                */
+/*                                                                      */
+/* rec[] receives CP_FIELDS 64-bit words for each of the first max_seg  */
+/* segments (the enum below).  Second, for every segment k >= 1, the    */
+/* walk a workgroup takes that knows nothing: tokens from k * seg       */
+/* itself for as long as they start inside the segment (CP_GUESS_MERGE: */
+/* after how many tokens it stands on a token start of the true walk,   */
+/* CP_NEVER: not inside the segment; CP_GUESS_EXIT: where it ends).     */
+/* Third, the host's rounds exactly as stream_compress_piece() writes   */
+/* them (csrc/lzs_stream.c), on the model's own walks: everyone enters  */
+/* at max(k * seg, c_first) -- c_first = 0 here --, a segment entered   */
+/* at or behind its end leaves where it was entered, and a segment is   */
+/* redone when its predecessor's exit differs from its entry.           */
+/* rounds[r] (up to max_rounds) receives the segments to redo after     */
+/* round r, *nrounds the number of rounds; the rule is deterministic,   */
+/* the device must give these numbers.                                  */
+/*                                                                      */
+/* counters[] (may be NULL) are ADDED to (the *_MAX ones raised), so    */
+/* that a test can prove its inputs reached the edges; trace[] (may be  */
+/* NULL) receives up to max_tok records {position, offset (0 =          */
+/* literal), bytes covered, bit position} of the true walk, *ntok       */
+/* their number.  Returns the bits of all tokens (the end marker and    */
+/* its padding not counted), (size_t)-1 if memory ran out or seg is not */
+/* a segment size.                                                      */
+/* ------------------------------------------------------------------ */
+enum {                      /* a segment's record */
+    CP_ENTRY = 0,           /* where its first token starts; CP_NEVER: a match ran over all of it                 */
+    CP_EXIT,                /* where its last token ends (an empty segment: where it was run over to)             */
+    CP_TOKENS,
+    CP_BITS,
+    CP_BIT_AT,              /* the prefix sum of the bits before it                                               */
+    CP_EMPTY,
+    CP_OVERSIZED,           /* the host's rule: bits > 8 * align16(LZS_COMPRESSED_MAX(seg))                       */
+    CP_GUESS_MERGE,
+    CP_GUESS_EXIT,
+    CP_REDONE,              /* rounds after round 0 in which the host's rule ran it again                         */
+    CP_ROUND_EXIT,          /* the exit the rounds arrived at (the test: == CP_EXIT)                              */
+    CP_FIELDS
+};
+#define CP_NEVER 0xFFFFFFFFFFFFFFFFull
+
+enum {                      /* rows of CC_LAST: the last token of a segment that has a border behind it */
+    CK_LIT = 0, CK_SHORT27, CK_LONG27, CK_EXT0, CK_EXT1, CK_EXT2, CK_EXT3_39, CK_EXT40,   /* length 8 and more: by its nibbles of 15 */
+    CK_KINDS
+};
+enum { CC_PAST = 21 };      /* columns of CC_LAST: ends 0 .. 16 bytes past the border; 17: farther, inside the next segment; 18 19 20: past 1, 2, >= 3 whole segments */
+
+enum {                      /* counters (oracle/__init__.py: CompressCounters has the same layout) */
+    CC_LAST       = 0,                              /* [kind][past]                                                                  */
+    CC_LAST_CLOSE = CC_LAST + CK_KINDS * CC_PAST,   /* [0 1 14 other]: closing nibbles of last tokens that end past their border     */
+    CC_LAST_START = CC_LAST_CLOSE + 4,              /* [s]: last tokens that are matches and start s = 1 .. 8 bytes before the border (0: farther) */
+    CC_ONE_TOKEN_LAST_BYTE = CC_LAST_START + 9,     /* segments entered at their last byte: one token                                */
+    CC_ENTRY_MOD64,                                 /* [c0 & 63]: entries of non-empty segments k >= 1                               */
+    CC_FIRST_OFF  = CC_ENTRY_MOD64 + 64,            /* [2047 2046 2040 1][warm-up window (c0 & ~63) - 2176 clamped: at 0, the first segment beyond, later ones]: first tokens of segments k >= 1 that are matches at these offsets */
+    CC_FIRST_STRADDLE = CC_FIRST_OFF + 12,          /* ... of any offset, whose source has a segment border inside it                */
+    CC_FIRST_FAR_LEN,                               /* [2 3]: first tokens at offset 2047 of exactly this length, warm-up not at 0   */
+    CC_MERGE      = CC_FIRST_FAR_LEN + 2,           /* [0 1 2 3-4 >=5 never]: guessed walks by the tokens before they fall in step   */
+    CC_ONE_ROUND  = CC_MERGE + 6,                   /* inputs of two segments and more settled by round 0                            */
+    CC_ROUNDS_MAX,                                  /* the most rounds (raised)                                                      */
+    CC_FIX_CHANGES_EXIT,                            /* segments whose true entry is not their border: the exit differs from the guessed walk's, */
+    CC_FIX_KEEPS_EXIT,                              /* ... or does not                                                              */
+    CC_NEVER_RUN_MAX,                               /* the most non-empty segments in a row whose guessed walks never merge (raised) */
+    CC_LONG_MATCH,                                  /* [offset 1, 2, 300]: the most segments one token starts in or runs over (raised) */
+    CC_BIT_AT_MOD32 = CC_LONG_MATCH + 3,            /* [bit_at % 32] of non-empty segments                                           */
+    CC_NBITS_MOD32 = CC_BIT_AT_MOD32 + 32,          /* [bits % 32] of non-empty segments                                             */
+    CC_UNDER_32   = CC_NBITS_MOD32 + 32,            /* non-empty segments of fewer than 32 bits                                      */
+    CC_WORD_SHARE_MAX,                              /* the most non-empty segments with bits in one 32-bit word of the stream (raised) */
+    CC_EMPTY_BETWEEN_SHARERS,                       /* runs of empty segments between two that put bits into one word                */
+    CC_TOTAL_MOD32,                                 /* [total % 32]: where the end marker starts                                     */
+    CC_MARKER_BEHIND_EMPTY = CC_TOTAL_MOD32 + 32,   /* inputs whose last segment is empty                                            */
+    CC_MARKER_BEHIND_OVERSIZED,                     /* inputs whose last non-empty segment is oversized (the last segment itself cannot be: its tokens end with the input) */
+    CC_MARGIN,                                      /* [d + 8]: segments whose bits are the slot's + d, d = -8 .. 8; [17]: more than 4096 over */
+    CC_OVER_BIT_AT = CC_MARGIN + 18,                /* [0, 1-31, 32-2016, >= 2017]: oversized segments by bit_at % 2048              */
+    CC_OVER_SEG0  = CC_OVER_BIT_AT + 4,             /* segment 0 oversized                                                           */
+    CC_OVER_TWO,                                    /* inputs with two oversized segments and more                                   */
+    CC_OVER_EMPTIES_ONE_TOKEN,                      /* an oversized segment, empty ones, then a one-token segment                    */
+    CC_LEN_MOD,                                     /* [n % seg: 1 63 64 255 0]                                                      */
+    CC_END_CLOSE  = CC_LEN_MOD + 5,                 /* [0 14]: the last token is a match of 8 and more that reaches n with this closing nibble */
+    CC_END_ONE_SHORT = CC_END_CLOSE + 2,            /* a match that ends one byte before n, then a literal                           */
+    CC_COUNTERS
+};
+
+typedef struct { uint32_t end, bits, nib15; uint16_t off; uint8_t close; } cp_tok_t;
+
+/* the token that starts at c: compress_core's decision, as a function of (input, position) */
+static void cp_token(const uint8_t *in, size_t n, size_t c, int brute, const int32_t *prev, cp_tok_t *t)
+{
+    unsigned off = 0, best = 0;
+    unsigned lim = (n - c < SEARCH_CAP) ? (unsigned)(n - c) : SEARCH_CAP;
+    if (brute)
+        best = lzs_oracle_search(in, n, c, &off);
+    else if (lim >= 2) {
+        /* every earlier position with our 2-gram, nearest first: chained_search on chains that hold all of in[0, c) */
+        for (int32_t q = prev[c]; q >= 0 && c - (size_t)q <= WINDOW; q = prev[q]) {
+            unsigned l = common_prefix(in, c, (size_t)q, lim);
+            if (l > best) {
+                best = l; off = (unsigned)(c - (size_t)q);
+                if (l == lim) break;
+            }
+        }
+    }
+    t->nib15 = 0; t->close = 0xFF;
+    if (best < 2) { t->end = (uint32_t)c + 1; t->bits = 9; t->off = 0; return; }
+    unsigned first = best < TOKEN_MAX ? best : TOKEN_MAX;
+    size_t   e = c + first;
+    t->off = (uint16_t)off;
+    t->bits = (off <= SHORT_MAX ? 9u : 13u) + (first <= 4 ? 2u : 4u);
+    if (first == TOKEN_MAX) {
+        unsigned x;
+        do {
+            unsigned l = (n - e < NIBBLE_MAX) ? (unsigned)(n - e) : NIBBLE_MAX;
+            x = common_prefix(in, e, e - off, l);
+            e += x; t->bits += 4;
+            if (x == NIBBLE_MAX) t->nib15++;
+        } while (x == NIBBLE_MAX);
+        t->close = (uint8_t)x;
+    }
+    t->end = (uint32_t)e;
+}
+
+size_t lzs_oracle_compress_segments(const uint8_t *in, size_t n, size_t seg, int brute,
+                                    uint64_t *rec, size_t max_seg, uint32_t *rounds, size_t max_rounds, size_t *nrounds,
+                                    uint64_t *counters, uint32_t *trace, size_t max_tok, size_t *ntok)
+{
+    static const unsigned first_offs[4] = { 2047, 2046, 2040, 1 }, long_offs[3] = { 1, 2, 300 };
+    if (seg < 256 || (seg & 63) || n >= 0x7FFFFFFFu)
+        return (size_t)-1;
+    const size_t   nseg = n ? (n + seg - 1) / seg : 1;
+    const uint64_t slot_bits = 8u * (uint64_t)(((seg + (seg + 7) / 8 + 3) + 15u) & ~(size_t)15u);
+    uint64_t  zero[CC_COUNTERS];
+    uint64_t *ctr = counters ? counters : zero;
+    cp_tok_t *memo = (cp_tok_t *)calloc(n + 1, sizeof(cp_tok_t));        /* end == 0: not asked for yet */
+    uint8_t  *is_start = (uint8_t *)calloc(n + 1, 1);
+    int32_t  *prev = (int32_t *)malloc((n + 1) * sizeof(int32_t)), *head = (int32_t *)malloc(65536 * sizeof(int32_t));
+    uint64_t *s = (uint64_t *)calloc(nseg * CP_FIELDS, sizeof(uint64_t));  /* all records, whatever max_seg is */
+    uint32_t *entry = (uint32_t *)malloc(nseg * sizeof(uint32_t)), *exitp = (uint32_t *)malloc(nseg * sizeof(uint32_t));
+    uint8_t  *dirty = (uint8_t *)malloc(nseg);
+    size_t    result = (size_t)-1;
+    if (!memo || !is_start || !prev || !head || !s || !entry || !exitp || !dirty)
+        goto done;
+    memset(zero, 0, sizeof(zero));
+    memset(head, 0xFF, 65536 * sizeof(int32_t));
+    for (size_t i = 0; i < n; i++) {
+        prev[i] = -1;
+        if (i + 1 < n) {
+            unsigned key = ((unsigned)in[i] << 8) | in[i + 1];
+            prev[i] = head[key]; head[key] = (int32_t)i;
+        }
+    }
+#define TOKEN(c) (memo[c].end ? &memo[c] : (cp_token(in, n, (c), brute, prev, &memo[c]), &memo[c]))
+#define SEG_END(k) (((k) + 1) * seg < n ? ((k) + 1) * seg : n)
+
+    /* ---- the one walk */
+    for (size_t k = 0; k < nseg; k++) { s[k * CP_FIELDS + CP_ENTRY] = CP_NEVER; s[k * CP_FIELDS + CP_EMPTY] = 1; }
+    size_t   tok = 0;
+    uint64_t bit = 0;
+    for (size_t c = 0; c < n; ) {
+        const cp_tok_t *t = TOKEN(c);
+        const size_t k = c / seg;
+        uint64_t *r = s + k * CP_FIELDS;
+        is_start[c] = 1;
+        if (r[CP_EMPTY]) { r[CP_EMPTY] = 0; r[CP_ENTRY] = c; }
+        r[CP_EXIT] = t->end; r[CP_TOKENS]++; r[CP_BITS] += t->bits;
+        if (trace && tok < max_tok) {
+            trace[4 * tok + 0] = (uint32_t)c; trace[4 * tok + 1] = t->off; trace[4 * tok + 2] = t->end - (uint32_t)c; trace[4 * tok + 3] = (uint32_t)bit;
+        }
+        tok++; bit += t->bits;
+        /* the segments this token starts in or runs over */
+        for (int o = 0; o < 3; o++)
+            if (t->off == long_offs[o]) {
+                const uint64_t over = (t->end - 1) / seg - k + 1;
+                if (over > ctr[CC_LONG_MATCH + o]) ctr[CC_LONG_MATCH + o] = over;
+            }
+        c = t->end;
+    }
+    if (ntok) *ntok = tok;
+    result = (size_t)bit;
+    {
+        uint64_t at = 0, exit_before = 0;
+        for (size_t k = 0; k < nseg; k++) {
+            uint64_t *r = s + k * CP_FIELDS;
+            if (r[CP_EMPTY]) r[CP_EXIT] = exit_before;
+            exit_before = r[CP_EXIT];
+            r[CP_BIT_AT] = at; at += r[CP_BITS];
+            r[CP_OVERSIZED] = r[CP_BITS] > slot_bits;
+        }
+    }
+
+    /* ---- the guessed walk of every segment behind the first */
+    s[CP_GUESS_MERGE] = 0; s[CP_GUESS_EXIT] = s[CP_EXIT];
+    uint64_t never_run = 0;
+    for (size_t k = 1; k < nseg; k++) {
+        uint64_t *r = s + k * CP_FIELDS;
+        const size_t e = SEG_END(k);
+        size_t   g = k * seg;
+        uint64_t steps = 0, merged = CP_NEVER;
+        while (g < e) {
+            if (is_start[g]) { merged = steps; break; }
+            g = TOKEN(g)->end; steps++;
+        }
+        r[CP_GUESS_MERGE] = merged;
+        r[CP_GUESS_EXIT] = merged == CP_NEVER ? g : r[CP_EXIT];
+        ctr[CC_MERGE + (merged == CP_NEVER ? 5 : merged >= 5 ? 4 : merged >= 3 ? 3 : merged)]++;
+        if (merged == CP_NEVER && !r[CP_EMPTY]) { if (++never_run > ctr[CC_NEVER_RUN_MAX]) ctr[CC_NEVER_RUN_MAX] = never_run; }
+        else never_run = 0;
+        if (!r[CP_EMPTY] && r[CP_ENTRY] != k * seg)
+            ctr[r[CP_GUESS_EXIT] != r[CP_EXIT] ? CC_FIX_CHANGES_EXIT : CC_FIX_KEEPS_EXIT]++;
+    }
+
+    /* ---- the host's rounds (stream_compress_piece: the loop over `round`), c_first = 0 */
+    size_t nr = 0;
+    for (size_t k = 0; k < nseg; k++) { entry[k] = (uint32_t)(k * seg); dirty[k] = 1; exitp[k] = entry[k]; }
+    for (size_t ndirty = nseg; ndirty; nr++) {
+        for (size_t k = 0; k < nseg; k++) {
+            if (!dirty[k]) continue;
+            const size_t e = SEG_END(k);
+            size_t c = entry[k];
+            while (c < e) c = TOKEN(c)->end;          /* (entered at or behind its end: it leaves where it was entered) */
+            exitp[k] = (uint32_t)c;
+            if (nr) s[k * CP_FIELDS + CP_REDONE]++;
+        }
+        ndirty = 0; dirty[0] = 0;
+        for (size_t k = 1; k < nseg; k++) {
+            dirty[k] = exitp[k - 1] != entry[k];
+            if (dirty[k]) { entry[k] = exitp[k - 1]; ndirty++; }
+        }
+        if (rounds && nr < max_rounds) rounds[nr] = (uint32_t)ndirty;
+    }
+    if (nrounds) *nrounds = nr;
+    for (size_t k = 0; k < nseg; k++) s[k * CP_FIELDS + CP_ROUND_EXIT] = exitp[k];
+    if (nseg >= 2 && nr == 1) ctr[CC_ONE_ROUND]++;
+    if (nr > ctr[CC_ROUNDS_MAX]) ctr[CC_ROUNDS_MAX] = nr;
+
+    /* ---- what the records reach */
+    {
+        size_t   noversized = 0, last_full = nseg;          /* last_full: the non-empty segment before the one looked at */
+        uint64_t word = CP_NEVER, sharers = 0;
+        for (size_t k = 0; k < nseg; k++) {
+            const uint64_t *r = s + k * CP_FIELDS;
+            const int64_t  margin = (int64_t)r[CP_BITS] - (int64_t)slot_bits;
+            if (margin >= -8 && margin <= 8) ctr[CC_MARGIN + (margin + 8)]++;
+            if (margin > 4096) ctr[CC_MARGIN + 17]++;
+            if (r[CP_EMPTY]) continue;
+            const size_t border = (k + 1) * seg, c0 = (size_t)r[CP_ENTRY];
+            size_t       last = c0;                         /* the segment's last token */
+            while (TOKEN(last)->end < r[CP_EXIT]) last = TOKEN(last)->end;
+            const cp_tok_t *t = TOKEN(last), *f = TOKEN(c0);
+            size_t empties = 0;
+            while (k + 1 + empties < nseg && s[(k + 1 + empties) * CP_FIELDS + CP_EMPTY]) empties++;
+            if (border < n) {
+                const unsigned kind = !t->off ? CK_LIT : t->close == 0xFF ? (t->off <= SHORT_MAX ? CK_SHORT27 : CK_LONG27)
+                                    : t->nib15 == 0 ? CK_EXT0 : t->nib15 == 1 ? CK_EXT1 : t->nib15 == 2 ? CK_EXT2 : t->nib15 < 40 ? CK_EXT3_39 : CK_EXT40;
+                const size_t d = t->end - border;
+                const unsigned past = empties >= 3 ? 20 : empties == 2 ? 19 : empties == 1 ? 18 : d > 16 ? 17 : (unsigned)d;
+                ctr[CC_LAST + kind * CC_PAST + past]++;
+                if (t->close != 0xFF && d > 0) ctr[CC_LAST_CLOSE + (t->close == 0 ? 0 : t->close == 1 ? 1 : t->close == 14 ? 2 : 3)]++;
+                if (t->off) ctr[CC_LAST_START + (border - last <= 8 ? border - last : 0)]++;
+            }
+            if (c0 == SEG_END(k) - 1 && border <= n) ctr[CC_ONE_TOKEN_LAST_BYTE]++;
+            if (k >= 1) {
+                ctr[CC_ENTRY_MOD64 + (c0 & 63)]++;
+                if (f->off) {
+                    const size_t c64 = c0 & ~(size_t)63;
+                    const unsigned warm = c64 <= 2176 ? 0 : k <= 2176 / seg + 1 ? 1 : 2;
+                    const size_t from = c0 - f->off, to = from + (f->end - c0);
+                    for (int o = 0; o < 4; o++)
+                        if (f->off == first_offs[o]) ctr[CC_FIRST_OFF + 3 * o + warm]++;
+                    if ((to - 1) / seg != from / seg) ctr[CC_FIRST_STRADDLE]++;
+                    if (f->off == WINDOW && warm && (f->end - c0 == 2 || f->end - c0 == 3)) ctr[CC_FIRST_FAR_LEN + (f->end - c0 - 2)]++;
+                }
+            }
+            ctr[CC_BIT_AT_MOD32 + (r[CP_BIT_AT] & 31)]++;
+            ctr[CC_NBITS_MOD32 + (r[CP_BITS] & 31)]++;
+            if (r[CP_BITS] < 32) ctr[CC_UNDER_32]++;
+            /* the 32-bit words of the stream this segment puts bits into: its first may be the last of the segments before */
+            /* (word: that of the last bit so far; sharers: the segments with bits in it) */
+            const uint64_t first_word = r[CP_BIT_AT] >> 5, last_word = (r[CP_BIT_AT] + r[CP_BITS] - 1) >> 5;
+            if (first_word == word) {
+                sharers++;
+                if (last_full + 1 < k) ctr[CC_EMPTY_BETWEEN_SHARERS]++;
+            } else
+                sharers = 1;
+            if (sharers > ctr[CC_WORD_SHARE_MAX]) ctr[CC_WORD_SHARE_MAX] = sharers;
+            if (last_word != first_word) sharers = 1;
+            word = last_word;
+            last_full = k;
+            if (r[CP_OVERSIZED]) {
+                const uint64_t ph = r[CP_BIT_AT] & 2047;
+                noversized++;
+                ctr[CC_OVER_BIT_AT + (ph == 0 ? 0 : ph <= 31 ? 1 : ph >= 2017 ? 3 : 2)]++;
+                if (k == 0) ctr[CC_OVER_SEG0]++;
+                if (empties && k + 1 + empties < nseg && s[(k + 1 + empties) * CP_FIELDS + CP_TOKENS] == 1) ctr[CC_OVER_EMPTIES_ONE_TOKEN]++;
+            }
+        }
+        if (noversized >= 2) ctr[CC_OVER_TWO]++;
+        if (n) {
+            const uint64_t *r = s + (nseg - 1) * CP_FIELDS;
+            static const unsigned mods[5] = { 1, 63, 64, 255, 0 };
+            ctr[CC_TOTAL_MOD32 + (bit & 31)]++;
+            if (r[CP_EMPTY]) ctr[CC_MARKER_BEHIND_EMPTY]++;
+            if (last_full < nseg && s[last_full * CP_FIELDS + CP_OVERSIZED]) ctr[CC_MARKER_BEHIND_OVERSIZED]++;
+            for (int m = 0; m < 5; m++)
+                if (n % seg == mods[m]) ctr[CC_LEN_MOD + m]++;
+            /* the last token, and the one before it */
+            size_t last = 0, before = 0;
+            for (size_t c = 0; c < n; c = TOKEN(c)->end) { before = last; last = c; }
+            const cp_tok_t *t = TOKEN(last);
+            if (t->close == 0)  ctr[CC_END_CLOSE + 0]++;
+            if (t->close == 14) ctr[CC_END_CLOSE + 1]++;
+            if (!t->off && last && TOKEN(before)->off && last == n - 1) ctr[CC_END_ONE_SHORT]++;
+        }
+    }
+    for (size_t k = 0; k < nseg && k < max_seg; k++)
+        memcpy(rec + k * CP_FIELDS, s + k * CP_FIELDS, CP_FIELDS * sizeof(uint64_t));
+#undef TOKEN
+#undef SEG_END
+done:
+    free(memo); free(is_start); free(prev); free(head); free(s); free(entry); free(exitp); free(dirty);
+    return result;
+}
+
+/* The sizes of what lzs_oracle_compress_segments fills in: counters, words a segment, kinds, columns of the last-token matrix. */
+void lzs_oracle_compress_segments_layout(uint32_t *sizes)
+{
+    sizes[0] = CC_COUNTERS; sizes[1] = CP_FIELDS; sizes[2] = CK_KINDS; sizes[3] = CC_PAST;
 }
 
 /* The sizes of what lzs_oracle_scan_segments fills in: counters, words a segment, step kinds, columns of the straddle matrix. */
