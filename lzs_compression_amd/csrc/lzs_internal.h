@@ -5,7 +5,8 @@
  *   lzs_pipeline.c     large host batches with the three stages overlapped: the plan, the ring, a function per stage
  *   lzs_stream.c       one stream (or a small batch) spread over the device: segments + stitch,
  *                      scan / decode / resolve
- *   lzs_incremental.c  the reference's incremental interface on top of both
+ *   lzs_incremental.c  the reference's incremental interface on top of both: one loop over a call's stages per direction
+ *   lzs_hostcodec.c    the small calls' host route: the calling thread's own codec
  */
 #ifndef LZS_INTERNAL_H
 #define LZS_INTERNAL_H

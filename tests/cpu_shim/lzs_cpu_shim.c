@@ -71,25 +71,35 @@ static void shim_free(void *p, size_t *counter)
     __atomic_sub_fetch(&g_live, 1, __ATOMIC_RELAXED);
     free(p);
 }
-int lzs_hip_malloc(void **p, size_t bytes) { return shim_alloc(p, bytes, &g_dev_bytes); }
+/* What the calling thread asked of the "device", in order: one FNV-1a hash over (which call, its size) of the syncs, copies,
+ * fills, allocations and resume launches since the last reset -- a test can hold a host path to the calls it used to make. */
+static _Thread_local uint64_t g_call_hash = 0xCBF29CE484222325ull;
+static void called(unsigned which, uint64_t size)
+{
+    const uint64_t rec[2] = { which, size };
+    for (size_t i = 0; i < sizeof rec; i++) g_call_hash = (g_call_hash ^ ((const uint8_t *)rec)[i]) * 0x100000001B3ull;
+}
+uint64_t lzs_shim_call_hash(int reset) { const uint64_t h = g_call_hash; if (reset) g_call_hash = 0xCBF29CE484222325ull; return h; }
+
+int lzs_hip_malloc(void **p, size_t bytes) { called(1, bytes); return shim_alloc(p, bytes, &g_dev_bytes); }
 int lzs_hip_free(void *p) { shim_free(p, &g_dev_bytes); return 0; }
-int lzs_hip_host_malloc(void **p, size_t bytes) { return shim_alloc(p, bytes, &g_host_bytes); }
+int lzs_hip_host_malloc(void **p, size_t bytes) { called(2, bytes); return shim_alloc(p, bytes, &g_host_bytes); }
 int lzs_hip_host_malloc_staging(void **p, size_t bytes) { return shim_alloc(p, bytes, &g_host_bytes); }
 int lzs_hip_host_free(void *p) { shim_free(p, &g_host_bytes); return 0; }
 
 int lzs_hip_stream_create(void **s) { *s = malloc(8); return *s ? 0 : E_OUT_OF_MEMORY; }
 int lzs_hip_stream_destroy(void *s) { free(s); return 0; }
-int lzs_hip_stream_sync(void *s) { (void)s; return 0; }
+int lzs_hip_stream_sync(void *s) { (void)s; called(3, 0); return 0; }
 int lzs_hip_event_create(void **e) { *e = calloc(1, 8); return *e ? 0 : E_OUT_OF_MEMORY; }
 int lzs_hip_event_destroy(void *e) { free(e); return 0; }
 int lzs_hip_event_record(void *e, void *s) { (void)s; *(volatile int *)e = 1; return 0; }
 int lzs_hip_event_sync(void *e) { (void)e; return 0; }
 int lzs_hip_event_done(void *e) { (void)e; return 1; }
 int lzs_hip_stream_wait_event(void *s, void *e) { (void)s; (void)e; return 0; }
-int lzs_hip_h2d(void *d, const void *s, size_t n, void *st) { (void)st; if (n) memcpy(d, s, n); return 0; }
-int lzs_hip_d2h(void *d, const void *s, size_t n, void *st) { (void)st; if (n) memcpy(d, s, n); return 0; }
-int lzs_hip_d2d(void *d, const void *s, size_t n, void *st) { (void)st; if (n) memmove(d, s, n); return 0; }
-int lzs_hip_memset(void *d, int v, size_t n, void *st) { (void)st; if (n) memset(d, v, n); return 0; }
+int lzs_hip_h2d(void *d, const void *s, size_t n, void *st) { (void)st; called(4, n); if (n) memcpy(d, s, n); return 0; }
+int lzs_hip_d2h(void *d, const void *s, size_t n, void *st) { (void)st; called(5, n); if (n) memcpy(d, s, n); return 0; }
+int lzs_hip_d2d(void *d, const void *s, size_t n, void *st) { (void)st; called(6, n); if (n) memmove(d, s, n); return 0; }
+int lzs_hip_memset(void *d, int v, size_t n, void *st) { (void)st; called(7, n); if (n) memset(d, v, n); return 0; }
 int lzs_hip_words_to_host(uint32_t *h, const uint32_t *d, size_t nwords, void *st) { (void)st; if (nwords) memcpy(h, d, 4 * nwords); return launched(); }
 int lzs_hip_chain_mode(void *stream, int *mode) { (void)stream; *mode = 0; return 0; }
 int lzs_hip_load_check_state(int dev) { (void)dev; return 0; }
@@ -243,6 +253,7 @@ int lzs_hip_launch_extend_resume(void *d_out, uint32_t bit0, const void *d_in, u
 int lzs_hip_launch_decode_resume(lzs_dec_resume_t *st, const void *d_in, uint32_t n, void *d_out, uint32_t cap, void *stream)
 {
     (void)stream;
+    called(8, ((uint64_t)n << 32) | cap);
     const uint8_t *in = (const uint8_t *)d_in;
     uint8_t *out = (uint8_t *)d_out;
     /* the history and what is produced as one array, the way the kernel's ring sees them */

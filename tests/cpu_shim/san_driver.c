@@ -7,7 +7,7 @@
  *   degrade path (LZS_STAGING_FAIL_MB); one stream in segments with dirty-segment re-entry (runs and periods spanning
  *   many segments, cut capacities); the incremental interface in random pieces both ways on BOTH routes (device route:
  *   segments / stitch / extend-resume / decode-resume; host route: lzs_hostcodec.c) with 1-12 bytes of room for the
- *   low-memory block; the one-shot calls on both routes; decompression by many wavefronts ("streamdec": the scan rounds with
+ *   low-memory block, and what each of its calls does against a table ("inctrace"); the one-shot calls on both routes; decompression by many wavefronts ("streamdec": the scan rounds with
  *   their settle rule and all-0xFF shortcut, placement, one stream / concatenated streams / batches by segments / pieces of
  *   the incremental interface, each compared with the same call by one wavefront); the route decision and the pipeline's plan
  *   against a table ("routes"); the one-after-the-other route's copy layouts where they switch ("layouts").
@@ -280,6 +280,28 @@ static void one_shot_streams(void)
 }
 
 /* ---------------------------------------------------------------- the incremental interface in random pieces, both routes */
+/* What every call did ("inctrace"): a 64-bit FNV-1a over one record a call -- bytes returned, how far the two lengths and the two
+ * pointers moved, and the caller's block from offset 32 to its end (the status byte and reserved_, private bytes included; the
+ * pointers and lengths in front are left out as values because addresses differ from run to run). */
+typedef struct { uint64_t h; size_t calls, bytes; } trace_t;
+static trace_t *tracing;                 /* != NULL: encode_pieces() and decode_pieces() record their calls here */
+static void trace_call(trace_t *t, size_t made, const size_t before[4], const size_t after[4], const void *block, size_t block_size)
+{
+    uint64_t rec[5] = { made, before[0] - after[0], before[1] - after[1], after[2] - before[2], after[3] - before[3] };
+    const uint8_t *parts[2] = { (const uint8_t *)rec, (const uint8_t *)block + 32 };
+    const size_t lens[2] = { sizeof rec, block_size - 32 };
+    if (!t->calls) t->h = 0xCBF29CE484222325ull;
+    for (int k = 0; k < 2; k++)
+        for (size_t i = 0; i < lens[k]; i++) t->h = (t->h ^ parts[k][i]) * 0x100000001B3ull;
+    t->calls++; t->bytes += made;
+}
+/* (inLength, outLength, inPtr, outPtr of any of the three blocks: they start alike) */
+static void trace_moved(size_t v[4], const void *block)
+{
+    const LzsDecompressParameters_t *p = (const LzsDecompressParameters_t *)block;
+    v[0] = p->inLength; v[1] = p->outLength; v[2] = (size_t)p->inPtr; v[3] = (size_t)p->outPtr;
+}
+
 static size_t encode_pieces(const uint8_t *d, size_t n, uint8_t *out, size_t out_cap, uint32_t in_lo, uint32_t in_hi, uint32_t out_lo, uint32_t out_hi, int simple)
 {
     LzsCompressParameters_t *p = (LzsCompressParameters_t *)malloc(sizeof *p);
@@ -296,16 +318,20 @@ static size_t encode_pieces(const uint8_t *d, size_t n, uint8_t *out, size_t out
         }
         size_t room = rnd_in(out_lo, out_hi);
         if (room > out_cap - made) room = out_cap - made;
-        size_t got;
+        size_t got, before[4], after[4];
         if (simple) {
             q->inPtr = pend_ptr; q->inLength = pending; q->outPtr = out + made; q->outLength = room;
+            trace_moved(before, q);
             got = lzs_simple_compress_incremental(q, finish);
             pend_ptr = q->inPtr; pending = q->inLength; status = q->status;
         } else {
             p->inPtr = pend_ptr; p->inLength = pending; p->outPtr = out + made; p->outLength = room;
+            trace_moved(before, p);
             got = lzs_compress_incremental(p, finish);
             pend_ptr = p->inPtr; pending = p->inLength; status = p->status;
         }
+        trace_moved(after, simple ? (void *)q : (void *)p);
+        if (tracing) trace_call(tracing, got, before, after, simple ? (void *)q : (void *)p, simple ? sizeof *q : sizeof *p);
         made += got;
         if (status & LZS_C_STATUS_ERROR) { CHECK(0, "incremental compression reported ERROR: %s", lzs_last_error()); break; }
         if (++calls > 4000000) { CHECK(0, "incremental compression: no progress"); break; }
@@ -314,10 +340,9 @@ static size_t encode_pieces(const uint8_t *d, size_t n, uint8_t *out, size_t out
     return made;
 }
 
-static size_t decode_pieces(const uint8_t *s, size_t n, uint8_t *out, size_t out_cap, uint32_t in_lo, uint32_t in_hi, uint32_t out_lo, uint32_t out_hi, uint8_t *status)
+/* (on a block the caller keeps: what it learnt from one buffer is there for the next) */
+static size_t decode_pieces_on(LzsDecompressParameters_t *p, const uint8_t *s, size_t n, uint8_t *out, size_t out_cap, uint32_t in_lo, uint32_t in_hi, uint32_t out_lo, uint32_t out_hi)
 {
-    LzsDecompressParameters_t *p = (LzsDecompressParameters_t *)malloc(sizeof *p);
-    lzs_decompress_init(p);
     size_t pos = 0, made = 0, pending = 0, calls = 0;
     const uint8_t *pend_ptr = s;
     for (;;) {
@@ -325,12 +350,25 @@ static size_t decode_pieces(const uint8_t *s, size_t n, uint8_t *out, size_t out
         size_t room = rnd_in(out_lo, out_hi);
         if (room > out_cap - made) room = out_cap - made;
         p->inPtr = pend_ptr; p->inLength = pending; p->outPtr = out + made; p->outLength = room;
-        made += lzs_decompress_incremental(p);
+        size_t before[4], after[4];
+        trace_moved(before, p);
+        const size_t got = lzs_decompress_incremental(p);
+        trace_moved(after, p);
+        if (tracing) trace_call(tracing, got, before, after, p, sizeof *p);
+        made += got;
         pend_ptr = p->inPtr; pending = p->inLength;
         if (p->status & LZS_D_STATUS_ERROR) { CHECK(0, "incremental decompression reported ERROR: %s", lzs_last_error()); break; }
         if (!pending && pos >= n && (p->status & LZS_D_STATUS_INPUT_STARVED)) break;
         if (++calls > 4000000) { CHECK(0, "incremental decompression: no progress"); break; }
     }
+    return made;
+}
+
+static size_t decode_pieces(const uint8_t *s, size_t n, uint8_t *out, size_t out_cap, uint32_t in_lo, uint32_t in_hi, uint32_t out_lo, uint32_t out_hi, uint8_t *status)
+{
+    LzsDecompressParameters_t *p = (LzsDecompressParameters_t *)malloc(sizeof *p);
+    lzs_decompress_init(p);
+    const size_t made = decode_pieces_on(p, s, n, out, out_cap, in_lo, in_hi, out_lo, out_hi);
     if (status) *status = p->status;
     free(p);
     return made;
@@ -370,6 +408,198 @@ static void incremental(void)
     }
     unsetenv("LZS_ROUTE");
     free(t); free(low); free(mix);
+}
+
+/* ---------------------------------------------------------------- what every call of the incremental interface does, against a table
+ * The cases above compare the bytes of a whole stream; this one compares call by call (trace_call) how much each call produced
+ * and consumed, which flags it reported and what it left in the caller's block -- every byte of it.  The rows were recorded with
+ * this driver linked against lzs_incremental.c as it was BEFORE its stages became functions (both routes; the device route over
+ * the shim, by many wavefronts where the code sends a piece there), never from the code under test. */
+typedef struct { const char *name; size_t calls, bytes; uint64_t digest; } trace_row_t;
+static const trace_row_t trace_rows[2][17] = {
+    { /* LZS_ROUTE=device (with the hash of the shim calls made: on this route no row is the host route's) */
+        { "full/compress 1..60 into 3..60", 4499, 51125, 0x49178E3BCB15924Bull },
+        { "full/decode 1..60 into 3..180", 2226, 90000, 0xBDBE8C00F5D5B27Bull },
+        { "full/compress 100..5000 into 100..5000", 53, 51125, 0xC97BF946AD0CFEC8ull },
+        { "full/decode 100..5000 into 100..15000", 27, 90000, 0x2EDB536B2CE23E57ull },
+        { "full/compress 512..512 into 512..512", 265, 51125, 0x4EF2F224AA12DA0Cull },
+        { "full/decode 512..512 into 512..1536", 146, 90000, 0xE758CBA6C2F78E8Dull },
+        { "full/compress 20000..90000 into 20000..90000", 4, 51125, 0x40C11B12FAF75C73ull },
+        { "full/decode 20000..90000 into 20000..270000", 3, 90000, 0x127489AF31CBB11Aull },
+        { "simple/compress 1..300 into 1..12", 2085, 11194, 0x450E4BAFC997350Eull },
+        { "full/compress 30000..60000 into 1..200", 74, 7769, 0x0871EB276692A755ull },
+        { "three/decode 16384..16384 into 1048576..1048576", 8, 150000, 0x1E2A9690E512B8EBull },
+        { "three/decode 20000..90000 into 5000..400000", 5, 150000, 0xC51F35D97D2AC515ull },
+        { "big/decode 1.5..3 MiB into 8 MiB", 3, 5600000, 0xCE1D8B18846D757Eull },
+        { "shrink/decode the long stream, then three short ones and the long one in one piece", 8, 11350000, 0xCA79FAD221787533ull },
+        { "fail/decode: NULL input, then a call after the ERROR", 3, 254, 0x8D3171838FFBA717ull },
+        { "fail/compress: a block that was not initialised", 1, 0, 0x06E3D09CFAF921F4ull },
+    },
+    { /* LZS_ROUTE=host: no shim call at all; what the calls do is the device route's call by call -- the same contract -- but
+       * for the pass size, which only the device route learns.  That the many wavefronts ran there is the scan count's to say. */
+        { "full/compress 1..60 into 3..60", 4499, 51125, 0xE99202551398A8BEull },
+        { "full/decode 1..60 into 3..180", 2226, 90000, 0x0111F10AED5FBC26ull },
+        { "full/compress 100..5000 into 100..5000", 53, 51125, 0xEA740366AC5A9486ull },
+        { "full/decode 100..5000 into 100..15000", 27, 90000, 0x15F072017A954CFCull },
+        { "full/compress 512..512 into 512..512", 265, 51125, 0xB229E93F83AED434ull },
+        { "full/decode 512..512 into 512..1536", 146, 90000, 0x783A1EED04CC0115ull },
+        { "full/compress 20000..90000 into 20000..90000", 4, 51125, 0x80F021A4617DFC2Cull },
+        { "full/decode 20000..90000 into 20000..270000", 3, 90000, 0x25EC1E9B8AE3D189ull },
+        { "simple/compress 1..300 into 1..12", 2085, 11194, 0xAB6B967145181B1Aull },
+        { "full/compress 30000..60000 into 1..200", 74, 7769, 0xBE9A74C69828BE7Eull },
+        { "three/decode 16384..16384 into 1048576..1048576", 8, 150000, 0x37FBBC45D62BD9BAull },
+        { "three/decode 20000..90000 into 5000..400000", 5, 150000, 0xDBF068947C9315E7ull },
+        { "big/decode 1.5..3 MiB into 8 MiB", 3, 5600000, 0x8A70ED9C2EF552EAull },
+        { "shrink/decode the long stream, then three short ones and the long one in one piece", 8, 11350000, 0x3A2A8552E12ECCBFull },
+        { "fail/decode: NULL input, then a call after the ERROR", 3, 254, 0xFCB19CFF497AA940ull },
+        { "fail/compress: a block that was not initialised", 1, 0, 0x06E3D09CFAF921F4ull },
+    },
+};
+unsigned lzs_shim_scan_launches(void);
+uint64_t lzs_shim_call_hash(int reset);
+static int trace_print;                  /* "inctrace-rows": print the rows instead of comparing them */
+/* (every scenario draws its piece sizes from a seed of its own: a scenario that goes wrong leaves the others' pieces alone) */
+/* ... and starts with nothing kept by the thread, so that the shim's hash of the calls made -- folded into the digest at the end:
+ * the same syncs, copies, launches and allocations in the same order -- does not depend on what ran before) */
+static void trace_begin(trace_t *t, unsigned scenario)
+{
+    tracing = t; rng_state = 0x9E3779B97F4A7C15ull * (scenario + 1u);
+    lzs_release_thread_cache();
+    lzs_shim_call_hash(1);
+}
+static void trace_done(unsigned ri, const char *name, trace_t *t)
+{
+    tracing = NULL;
+    const uint64_t calls_made = lzs_shim_call_hash(1);
+    for (size_t i = 0; i < sizeof calls_made; i++) t->h = (t->h ^ ((const uint8_t *)&calls_made)[i]) * 0x100000001B3ull;
+    if (trace_print) { printf("        { \"%s\", %zu, %zu, 0x%016llXull },\n", name, t->calls, t->bytes, (unsigned long long)t->h); memset(t, 0, sizeof *t); return; }
+    const trace_row_t *row = NULL;
+    for (unsigned i = 0; i < 17 && trace_rows[ri][i].name; i++) if (!strcmp(trace_rows[ri][i].name, name)) row = &trace_rows[ri][i];
+    CHECK(row, "route %u, %s: no row in the table", ri, name);
+    if (row) CHECK(row->calls == t->calls && row->bytes == t->bytes && row->digest == t->h, "route %u, %s: %zu calls, %zu bytes, digest %016llx; recorded: %zu, %zu, %016llx",
+                   ri, name, t->calls, t->bytes, (unsigned long long)t->h, row->calls, row->bytes, (unsigned long long)row->digest);
+    memset(t, 0, sizeof *t);
+}
+
+/* the terminal failures: a NULL input with a length, then a good call on the same block; a block that was never initialised */
+static void trace_failures(unsigned ri, const uint8_t *stream, size_t n)
+{
+    trace_t t = { 0, 0, 0 };
+    size_t before[4], after[4];
+    uint8_t out[600];
+    LzsDecompressParameters_t *d = (LzsDecompressParameters_t *)malloc(sizeof *d);
+    lzs_decompress_init(d);
+    trace_begin(&t, 14);
+    for (int call = 0; call < 3; call++) {                          /* a good call, the bad one, a call after the ERROR */
+        d->inPtr = call == 1 ? NULL : stream + 100 * (call / 2); d->inLength = call == 1 ? 77 : 100; d->outPtr = out; d->outLength = sizeof out;
+        trace_moved(before, d);
+        const size_t got = lzs_decompress_incremental(d);
+        trace_moved(after, d);
+        trace_call(&t, got, before, after, d, sizeof *d);
+        CHECK(!(d->status & LZS_D_STATUS_ERROR) == (call != 1) && d->inLength == 0, "decode call %d: status %02x, %zu bytes of input left", call, d->status, d->inLength);
+    }
+    trace_done(ri, "fail/decode: NULL input, then a call after the ERROR", &t);
+    free(d);
+    LzsCompressParameters_t *c = (LzsCompressParameters_t *)malloc(sizeof *c);
+    memset(c, 0xFF, sizeof *c);
+    trace_begin(&t, 15);
+    c->inPtr = stream; c->inLength = n < 3000 ? n : 3000; c->outPtr = out; c->outLength = sizeof out;
+    trace_moved(before, c);
+    const size_t got = lzs_compress_incremental(c, false);
+    trace_moved(after, c);
+    trace_call(&t, got, before, after, c, sizeof *c);
+    CHECK(c->status == (LZS_C_STATUS_ERROR | LZS_C_STATUS_END_MARKER | LZS_C_STATUS_INPUT_STARVED | LZS_C_STATUS_INPUT_FINISHED) && c->inLength == 0 && c->inPtr == stream + (n < 3000 ? n : 3000),
+          "a block that was not initialised: status %02x", c->status);
+    trace_done(ri, "fail/compress: a block that was not initialised", &t);
+    free(c);
+}
+
+static void inctrace(void)
+{
+    enum { N_TEXT = 90000, N_SIMPLE = 20000, N_LOW = 200000, N_BIG = 5600000 };
+    uint8_t *text = sample(0, N_BIG, 61), *low = sample(1, N_LOW, 62), *rnd3 = sample(2, 30000, 63);
+    const size_t cap = LZS_COMPRESSED_MAX(N_BIG) + 64;
+    uint8_t *want = (uint8_t *)malloc(cap), *got = (uint8_t *)malloc(cap), *back = (uint8_t *)malloc(150000 + N_BIG + 64);
+    /* three streams back to back, each with its end marker: text, zeros and then text, random bytes */
+    uint8_t *three_plain = (uint8_t *)calloc(40000 + 80000 + 30000, 1), *three = (uint8_t *)malloc(LZS_COMPRESSED_MAX(150000) + 64);
+    memcpy(three_plain, text + 100000, 40000); memcpy(three_plain + 100000, text + 140000, 20000); memcpy(three_plain + 120000, rnd3, 30000);
+    size_t n_three = lzs_oracle_compress(three, LZS_COMPRESSED_MAX(40000), three_plain, 40000);
+    n_three += lzs_oracle_compress(three + n_three, LZS_COMPRESSED_MAX(80000), three_plain + 40000, 80000);
+    n_three += lzs_oracle_compress(three + n_three, LZS_COMPRESSED_MAX(30000), three_plain + 120000, 30000);
+    uint8_t *big = (uint8_t *)malloc(cap);
+    const size_t n_big = lzs_oracle_compress(big, cap, text, N_BIG);            /* ~3 MiB of compressed text */
+    CHECK(n_big > 2900000 && n_big < 3400000, "the long stream has %zu bytes", n_big);
+    uint8_t *mixed = (uint8_t *)malloc(n_three + n_big);
+    memcpy(mixed, three, n_three); memcpy(mixed + n_three, big, n_big);
+    const char *routes[] = { "device", "host" };
+    const uint64_t rng_before = rng_state;
+    unsetenv("LZS_ONE_WAVE");                                       /* the device route as a caller gets it: large pieces by many wavefronts */
+    for (unsigned ri = 0; ri < 2; ri++) {
+        setenv("LZS_ROUTE", routes[ri], 1);
+        if (trace_print) printf("    { /* LZS_ROUTE=%s */\n", routes[ri]);
+        trace_t t = { 0, 0, 0 };
+        char name[96];
+        /* the full block, 90 000 bytes of text: the ranges of "incremental" (on the device route: the box, staged copies, many wavefronts) */
+        const size_t w = lzs_oracle_compress(want, cap, text, N_TEXT);
+        const uint32_t ranges[][4] = { { 1, 60, 3, 60 }, { 100, 5000, 100, 5000 }, { 512, 512, 512, 512 }, { 20000, 90000, 20000, 90000 } };
+        for (unsigned k = 0; k < 4; k++) {
+            trace_begin(&t, 2 * k);
+            const size_t g = encode_pieces(text, N_TEXT, got, cap, ranges[k][0], ranges[k][1], ranges[k][2], ranges[k][3], 0);
+            CHECK(g == w && memcmp(got, want, w) == 0, "%s route: pieces of %u..%u: the stream differs", routes[ri], ranges[k][0], ranges[k][1]);
+            snprintf(name, sizeof name, "full/compress %u..%u into %u..%u", ranges[k][0], ranges[k][1], ranges[k][2], ranges[k][3]);
+            trace_done(ri, name, &t);
+            trace_begin(&t, 2 * k + 1);
+            const size_t b = decode_pieces(want, w, back, N_TEXT + 64, ranges[k][0], ranges[k][1], ranges[k][2], 3 * ranges[k][3], NULL);
+            CHECK(b == N_TEXT && memcmp(back, text, N_TEXT) == 0, "%s route: pieces of %u..%u: the text differs", routes[ri], ranges[k][0], ranges[k][1]);
+            snprintf(name, sizeof name, "full/decode %u..%u into %u..%u", ranges[k][0], ranges[k][1], ranges[k][2], 3 * ranges[k][3]);
+            trace_done(ri, name, &t);
+        }
+        /* the low-memory block, 1-12 bytes of room: the token-counted take, `stop`, the marker behind parked output */
+        const size_t w2 = lzs_oracle_compress(want, cap, text, N_SIMPLE);
+        trace_begin(&t, 8);
+        const size_t g2 = encode_pieces(text, N_SIMPLE, got, cap, 1, 300, 1, 12, 1);
+        CHECK(g2 == w2 && memcmp(got, want, w2) == 0, "%s route: the low-memory block: the stream differs", routes[ri]);
+        trace_done(ri, "simple/compress 1..300 into 1..12", &t);
+        /* the full block with less room than output: parked in the block, drained over several calls, the marker waiting */
+        const size_t w3 = lzs_oracle_compress(want, cap, low, N_LOW);
+        trace_begin(&t, 9);
+        const size_t g3 = encode_pieces(low, N_LOW, got, cap, 30000, 60000, 1, 200, 0);
+        CHECK(g3 == w3 && memcmp(got, want, w3) == 0, "%s route: little room: the stream differs", routes[ri]);
+        trace_done(ri, "full/compress 30000..60000 into 1..200", &t);
+        /* three streams back to back: markers inside pieces, a copy running at a piece border (short: the pass size stays) */
+        const uint32_t three_ranges[2][4] = { { 16384, 16384, 1u << 20, 1u << 20 }, { 20000, 90000, 5000, 400000 } };
+        const unsigned scans = lzs_shim_scan_launches();
+        for (unsigned k = 0; k < 2; k++) {
+            trace_begin(&t, 10 + k);
+            const size_t b = decode_pieces(three, n_three, back, 150000 + 64, three_ranges[k][0], three_ranges[k][1], three_ranges[k][2], three_ranges[k][3], NULL);
+            CHECK(b == 150000 && memcmp(back, three_plain, 150000) == 0, "%s route: three streams in pieces of %u..%u: %zu bytes", routes[ri], three_ranges[k][0], three_ranges[k][1], b);
+            snprintf(name, sizeof name, "three/decode %u..%u into %u..%u", three_ranges[k][0], three_ranges[k][1], three_ranges[k][2], three_ranges[k][3]);
+            trace_done(ri, name, &t);
+        }
+        /* ~3 MiB of compressed text in pieces of 1.5-3 MiB: the pass size of the many-wavefront path goes up and is remembered */
+        trace_begin(&t, 12);
+        const size_t b5 = decode_pieces(big, n_big, back, N_BIG + 64, 3u << 19, 3u << 20, 8u << 20, 8u << 20, NULL);
+        CHECK(b5 == N_BIG && memcmp(back, text, N_BIG) == 0, "%s route: the long stream: %zu bytes", routes[ri], b5);
+        trace_done(ri, "big/decode 1.5..3 MiB into 8 MiB", &t);
+        CHECK(ri == 1 ? lzs_shim_scan_launches() == scans : lzs_shim_scan_launches() >= scans + 8, "%s route: %u launches of the scan", routes[ri], lzs_shim_scan_launches() - scans);
+        /* ... and down again, on the same block: a buffer of the three short streams and then the long one, whole -- a pass of the size
+         * learnt meets an end marker in its first quarter, three times over; then the long stream makes it grow once more */
+        LzsDecompressParameters_t *keeps = (LzsDecompressParameters_t *)malloc(sizeof *keeps);
+        lzs_decompress_init(keeps);
+        trace_begin(&t, 13);
+        size_t b6 = decode_pieces_on(keeps, big, n_big, back, N_BIG + 64, 3u << 19, 3u << 20, 8u << 20, 8u << 20);
+        CHECK(b6 == N_BIG && memcmp(back, text, N_BIG) == 0, "%s route: the long stream on the kept block: %zu bytes", routes[ri], b6);
+        b6 = decode_pieces_on(keeps, mixed, n_three + n_big, back, 150000 + N_BIG + 64, 16u << 20, 16u << 20, 8u << 20, 8u << 20);
+        CHECK(b6 == 150000 + N_BIG && memcmp(back, three_plain, 150000) == 0 && memcmp(back + 150000, text, N_BIG) == 0, "%s route: short streams, then the long one: %zu bytes", routes[ri], b6);
+        trace_done(ri, "shrink/decode the long stream, then three short ones and the long one in one piece", &t);
+        free(keeps);
+        trace_failures(ri, big, n_big);
+        if (trace_print) printf("    },\n");
+    }
+    unsetenv("LZS_ROUTE");
+    setenv("LZS_ONE_WAVE", "1", 1);
+    rng_state = rng_before;
+    free(text); free(low); free(rnd3); free(want); free(got); free(back); free(three_plain); free(three); free(big); free(mixed);
 }
 
 /* ---------------------------------------------------------------- decompression by many wavefronts: scan rounds, settle rule, placement
@@ -682,6 +912,8 @@ int main(int argc, char **argv)
     if (!*only || !strcmp(only, "layouts")) layouts();
     if (!*only || !strcmp(only, "streams")) one_shot_streams();
     if (!*only || !strcmp(only, "incremental")) incremental();
+    trace_print = !strcmp(only, "inctrace-rows");
+    if (!*only || !strcmp(only, "inctrace") || trace_print) inctrace();
     if (!*only || !strcmp(only, "streamdec")) streamdec();
     if (!*only || !strcmp(only, "pipeline")) pipeline();
     if (!*only || !strcmp(only, "release")) release_cache();

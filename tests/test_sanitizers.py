@@ -8,7 +8,8 @@ c/src/liblzs/lzs-compression.c:329,349,437) are the reason to look.
   device memory is heap memory, the launches are backed by the oracle and by serial restatements of the kernels'
   contracts, the many-wavefront decompression's scan and decode among them) and driven by tests/cpu_shim/san_driver.c
   through the ragged-batch, truncation, >= 24 MiB pipeline, one-stream-in-segments, incremental-pieces and
-  many-wavefront-decompression ("streamdec": scan rounds, settle rule, placement) cases, the route decision and the
+  many-wavefront-decompression ("streamdec": scan rounds, settle rule, placement) cases, what every call of the incremental
+  interface does against a table ("inctrace": bytes produced and consumed, flags, every byte left in the caller's block), the route decision and the
   pipeline's plan against a table ("routes") and the serial route's copy layouts where they switch ("layouts"), under -fsanitize=address,undefined and under -fsanitize=thread.
 * The checkers themselves (oracle/lzs_oracle.c, cpu_bench.c, csrc/lzs_workload.c): tests/test_oracle.py against their
   ASan + UBSan builds.
@@ -42,7 +43,7 @@ def _run(exe, cases, env_extra, timeout):
 def test_host_sources_under_address_and_undefined_behaviour_sanitizers(built):
     # ("release": what a thread keeps between calls goes back on lzs_release_thread_cache(), on thread exit, and above
     # LZS_KEEP_MAX_MB -- the shim counts its outstanding "device" bytes; leak detection is on)
-    _run(os.path.join(built, "san_asan"), ["routes", "ragged", "layouts", "streams", "incremental", "streamdec", "pipeline", "release"],
+    _run(os.path.join(built, "san_asan"), ["routes", "ragged", "layouts", "streams", "incremental", "inctrace", "streamdec", "pipeline", "release"],
          {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, 900)
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Wall time per call of the many-wavefront decompression's host paths and of the host-buffer batches, this build against
-another build of liblzs.so.
+"""Wall time per call of the many-wavefront decompression's host paths, of the host-buffer batches and of the incremental
+interface, this build against another build of liblzs.so.
 
     python tools/stream_host_ab.py --other path/to/other/liblzs.so [--reps 10] [--shapes dec-1m,dec-64m,dev-1g,batch-256] [--out FILE]
 
@@ -9,7 +9,14 @@ Shapes (text): dec-1m / dec-64m  lzs_decompress of a stream that decodes to 1 / 
                batch-256         lzs_decompress_batch of 256 blocks of 64 KiB, host buffers (goes by segments);
                cbatch-2597 / dbatch-2597  lzs_compress_batch / lzs_decompress_batch of 2597 blocks of 64 KiB, host buffers
                                  (the overlapped route, lzs_pipeline.c);
-               cbatch-64         lzs_compress_batch of 64 blocks of 64 KiB, host buffers (one after the other).
+               cbatch-64         lzs_compress_batch of 64 blocks of 64 KiB, host buffers (one after the other);
+               inc-c-512 / inc-d-512  4 MiB through lzs_compress_incremental / lzs_decompress_incremental in calls of 512 bytes,
+                                 LZS_ROUTE=device (every call a launch: the pinned box, the collecting);
+               inc-c-1m          64 MiB through lzs_compress_incremental in pieces of 1 MiB;
+               inc-d-256k        the stream of 24 MiB of tests/test_gpu_incremental.py's
+                                 test_no_large_piece_is_left_to_one_wavefront in pieces of 256 KiB;
+               inc-d-4m          40 MiB through lzs_decompress_incremental in pieces of 4 MiB (one "call" of these five is the
+                                 whole stream, its block initialised first).
 Every shape gets two worker processes -- one per build, chosen by LZS_LIBRARY, each with its data made, checked and three calls
 warm -- and the two are timed in turn, one call each, `--reps` times: what one build sees of the machine the other sees too.
 The verdict per shape: this build's median is no more than the other's median plus the other's own spread (max - min).
@@ -24,12 +31,16 @@ import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 SHAPES = {"dec-1m": 16, "dec-64m": 1024, "dev-1g": 16384, "batch-256": 256,          # 64 KiB blocks of text
-          "cbatch-2597": 2597, "dbatch-2597": 2597, "cbatch-64": 64}
+          "cbatch-2597": 2597, "dbatch-2597": 2597, "cbatch-64": 64,
+          "inc-c-512": 64, "inc-d-512": 64, "inc-c-1m": 1024, "inc-d-256k": 384, "inc-d-4m": 640}
+INC_PIECE = {"inc-c-512": 512, "inc-d-512": 512, "inc-c-1m": 1 << 20, "inc-d-256k": 256 << 10, "inc-d-4m": 4 << 20}
 
 
 def worker(shape):
     """Prepare, check, warm up; then one timed call per line read from stdin, its milliseconds on stdout."""
     sys.path.insert(0, ROOT)
+    if shape.endswith("-512"):
+        os.environ["LZS_ROUTE"] = "device"
     import numpy as np
     import lzs_compression_amd as lzs
     from lzs_compression_amd import workload
@@ -51,6 +62,42 @@ def worker(shape):
             assert L.lzs_decompress_batch(out.ctypes.data, out.shape[1], out.shape[1], out_len.ctypes.data, comp.ctypes.data,
                                           comp.shape[1], lens.ctypes.data, comp.shape[1], len(x)) == 0
         check = lambda: bool((out_len == x.shape[1]).all()) and np.array_equal(out, x)
+    elif shape.startswith("inc-"):
+        # (ctypes calls on buffers made beforehand, as tests/dev/inc_time.py drives the interface)
+        from lzs_compression_amd import api
+        if shape == "inc-d-256k":
+            x = workload.fill("text", 1, 24 << 20, first_block=5)
+        plain, piece, got, addr = x.tobytes(), INC_PIECE[shape], [0], ctypes.addressof
+        if shape.startswith("inc-c-"):
+            want, src, dst = lzs.compress(plain), ctypes.create_string_buffer(plain, len(plain)), ctypes.create_string_buffer(lzs.compressed_max(len(plain)) + 64)
+
+            def call():
+                p, out = api.CompressParameters(), 0
+                L.lzs_compress_init_full(addr(p))
+                p.outPtr, p.outLength = addr(dst), len(dst)
+                for pos in range(0, len(plain), piece):
+                    p.inPtr, p.inLength = addr(src) + pos, min(piece, len(plain) - pos)
+                    out += L.lzs_compress_incremental(addr(p), False)
+                    assert p.inLength == 0 and not (p.status & api.STATUS_ERROR)
+                p.inLength = 0
+                got[0] = out + L.lzs_compress_incremental(addr(p), True)
+                assert p.status & api.STATUS_END_MARKER
+            check = lambda: dst.raw[:got[0]] == want
+        else:
+            comp = lzs.compress(plain)
+            src, dst = ctypes.create_string_buffer(comp, len(comp)), ctypes.create_string_buffer(len(plain) + 64)
+
+            def call():
+                p, out = api.DecompressParameters(), 0
+                L.lzs_decompress_init(addr(p))
+                p.outPtr, p.outLength = addr(dst), len(dst)
+                for pos in range(0, len(comp), piece):
+                    p.inPtr, p.inLength = addr(src) + pos, min(piece, len(comp) - pos)
+                    while p.inLength:
+                        out += L.lzs_decompress_incremental(addr(p))
+                        assert not (p.status & api.STATUS_ERROR)
+                got[0] = out
+            check = lambda: got[0] == len(plain) and dst.raw[:len(plain)] == plain
     elif shape == "dev-1g":
         import torch
         plain = torch.from_numpy(x.reshape(-1)).cuda()
