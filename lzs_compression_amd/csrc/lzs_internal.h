@@ -33,7 +33,7 @@ LZS_HIDDEN int require_device(void);
  * function goes on at `label`. */
 #define HIP_TRY_OR(label, call, what) do { e = (call); if (e) { rc = hip_fail(e, what); goto label; } } while (0)
 /* ... in a function with NOTHING TO UNDO (the stages of lzs_pipeline.c: all they touch belongs to the run, which
- * host_batch_pipelined() cleans up): it returns the LZS_E_* code at once.  A function that owns something takes HIP_TRY_OR. */
+ * host_batch_pipelined() cleans up; those of lzs_stream.c's compressor, whose call ends in one place): it returns the LZS_E_* code at once.  A function that owns something takes HIP_TRY_OR. */
 #define HIP_TRY_RET(call, what) do { const int e_ = (call); if (e_) return hip_fail(e_, what); } while (0)
 
 /* The development switches of the environment (tools/README.md), read ONCE per process by lzs_env() -- the
@@ -177,6 +177,10 @@ typedef struct {                    /* a piece of a stream for lzs_decompress_in
     uint32_t next_entry;        /* state word at the start of segment segs_done */
 } dec_piece_t;
 LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t *in, size_t n, int dev, int *status, piece_t *pc);
+/* two of its stages, host code only (tests/cpu_shim/san_driver.c asks them directly) */
+LZS_HIDDEN uint32_t settle_compress_entries(uint32_t *entry, uint8_t *dirty, const uint32_t *exits, uint32_t nseg);
+LZS_HIDDEN int open_match_take_back(const uint32_t *open, uint64_t *nbits, uint32_t nseg, uint32_t n, uint32_t c_first, uint32_t *c_exit,
+                                    uint32_t *ext_exit);
 LZS_HIDDEN size_t hostcodec_compress_piece(uint8_t *out, size_t cap, const uint8_t *in, size_t n, piece_t *pc);   /* the same on the host; SIZE_MAX: out of memory */
 LZS_HIDDEN void hostcodec_decode_resume(lzs_dec_resume_t *st, const uint8_t *in, uint32_t n, uint8_t *out, uint32_t cap);   /* lzs_decode_resume_kernel's contract */
 LZS_HIDDEN void hostcodec_decode_resume_fields(uint32_t *bitq, uint32_t *qlen, uint32_t *off, uint32_t *rem, uint32_t *extended,

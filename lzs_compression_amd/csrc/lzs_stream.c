@@ -6,6 +6,51 @@
  */
 #include "lzs_internal.h"
 
+/* (the clock of the LZS_STREAM_DEBUG lines) */
+LZS_HIDDEN double now_ms(void)
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+
+/* ------------------------------------------------ how a one-stream call begins and ends, compressing or decompressing */
+/* It begins with the device, this thread's staging, `tab_bytes` of its pinned memory for the per-segment tables (they travel every
+ * round) and its stream.  LZS_OK or the code reported. */
+static int stream_call_begins(const char *who, size_t tab_bytes, staging_t **st, void **tables)
+{
+    tls_error[0] = 0;
+    if (require_device() != LZS_OK) return LZS_E_HIP;
+    if (!(*st = staging_get()) || !(*tables = staging_host_tables(*st, tab_bytes))) return fail(LZS_E_NOMEM, "%s: out of host memory", who);
+    if (!(*st)->stream) HIP_TRY_RET(lzs_hip_stream_create(&(*st)->stream), "hipStreamCreate");
+    return LZS_OK;
+}
+
+/* in on the host: the prefix of a piece (pre bytes, or none) and the caller's input behind it make the n bytes at d_in */
+static int stream_copy_in(void *d_in, const uint8_t *prefix, size_t pre, const uint8_t *in, size_t n, void *stream)
+{
+    if (pre) HIP_TRY_RET(lzs_hip_h2d(d_in, prefix, pre, stream), "hipMemcpy H2D");
+    HIP_TRY_RET(lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
+    return LZS_OK;
+}
+
+/* It ends: a failed one (rc) gives 0 bytes, says so on stderr (host buffers: the reference's calls have no other way) and leaves
+ * nothing of its own in flight; the thread's staging is trimmed to what it may keep. */
+static size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status)
+{
+    staging_t *st = staging_get();
+    if (rc != LZS_OK) {
+        if (!dev) fprintf(stderr, "liblzs: %s failed: %s\n", who, tls_error);
+        if (st && st->stream) lzs_hip_stream_sync(st->stream);
+        /* (the runtime keeps a failed allocation as its "last error" until somebody fetches it, and every launcher returns the
+         * last error after its launch: fetched here, or this thread's next call reports this out-of-memory as its own) */
+        if (rc == LZS_E_NOMEM) lzs_hip_clear_error();
+    }
+    if (st) staging_trim(st);
+    if (status) *status = rc;
+    return rc != LZS_OK ? 0 : result;
+}
+
 /* ------------------------------------------------ one long stream on the whole device */
 /* lzs_compress() of a buffer too long for one workgroup to be worth waiting for.  The search is a
  * pure function of (input, position), so the stream is cut into segments (stream_seg()), one workgroup
@@ -19,13 +64,6 @@
  * of the bit counts on the host; (4) lzs_stitch_segments_kernel shifts every slot to its bit
  * offset in the zeroed output and appends the end marker.  Same bytes as one workgroup (or the
  * reference) produces. */
-LZS_HIDDEN double now_ms(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
-
 #define STREAM_SEG_MAX 65536u
 
 /* Segment size for a stream of n bytes: 64 KiB for long streams, much smaller for shorter ones so
@@ -39,7 +77,8 @@ LZS_HIDDEN double now_ms(void)
  *     1 MiB     15.08        0.357   0.340   0.358   0.417   0.777    1.233
  *     4 MiB                          0.985   0.916   0.925   1.230    2.684
  *    16 MiB                          4.032   3.854   3.785   3.961    5.132
- * (round 2 used 4 KiB up to 2 MiB: 64 KiB in 0.29 ms). */
+ * (round 2 used 4 KiB up to 2 MiB: 64 KiB in 0.29 ms).  A short piece of the incremental interface, whose block collects
+ * ~10 KiB, is all latency too: at 512-byte calls 41 MB/s in 4 KiB segments, 62 in 1 KiB, 67 in 512 B. */
 static uint32_t stream_seg(size_t n)
 {
     const uint32_t v = lzs_env()->stream_seg;
@@ -51,175 +90,188 @@ static uint32_t stream_seg(size_t n)
     return (uint32_t)(seg & ~(size_t)63u);
 }
 
-/* How a one-stream call ends, compressing or decompressing: a failed one (rc) gives 0 bytes, says so on stderr (host buffers: the
- * reference's calls have no other way) and leaves nothing of its own in flight; the thread's staging is trimmed to what it may keep. */
-static size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status)
+/* The segments of one stream as the segment compressor and the stitch see them: segment k is bytes [k seg, (k + 1) seg), and its
+ * bits go to slot k of d_slots (slot_stride bytes each) first.  A segment's share of either side: the bits it gave and the bit at
+ * which they begin in the output (64-bit), where it is entered and where its last token ends, the open-match report of a piece
+ * (two words: offset, start), a flag. */
+typedef struct {
+    uint32_t seg, nseg;
+    size_t   slot_stride;
+    uint64_t *nbits, *bit_at;   uint32_t *entry, *exits, *open;     uint8_t *dirty;         /* host side, in this order */
+    uint64_t *d_bit_at, *d_nbits; uint32_t *d_entry, *d_exit, *d_open; uint8_t *d_dirty;    /* device side, in this order */
+    void     *d_slots;
+} cseg_table_t;
+enum { CSEG_BYTES = 2 * 8 + 2 * 4 + 8 + 1 };
+static size_t csegtab_host_bytes(uint32_t nseg) { return ((size_t)nseg + 16u) * CSEG_BYTES; }
+static size_t csegtab_dev_bytes(uint32_t nseg) { return (size_t)nseg * CSEG_BYTES + 64; }
+
+/* (t->nseg is set; h: csegtab_host_bytes() of pinned memory, d: csegtab_dev_bytes() of device memory) */
+static void csegtab_lay_out(cseg_table_t *t, void *h, void *d)
 {
-    staging_t *st = staging_get();
-    if (rc != LZS_OK) {
-        if (!dev) fprintf(stderr, "liblzs: %s failed: %s\n", who, tls_error);
-        if (st && st->stream) lzs_hip_stream_sync(st->stream);
-    }
-    if (st) staging_trim(st);
-    if (status) *status = rc;
-    return rc != LZS_OK ? 0 : result;
+    const size_t n = t->nseg;
+    t->nbits = (uint64_t *)h; t->bit_at = t->nbits + n; t->entry = (uint32_t *)(t->bit_at + n); t->exits = t->entry + n; t->open = t->exits + n;
+    t->dirty = (uint8_t *)(t->open + 2 * n);
+    t->d_bit_at = (uint64_t *)d; t->d_nbits = t->d_bit_at + n; t->d_entry = (uint32_t *)(t->d_nbits + n); t->d_exit = t->d_entry + n; t->d_open = t->d_exit + n;
+    t->d_dirty = (uint8_t *)(t->d_open + 2 * n);
 }
 
-/* in/out on the host (dev == 0: staged through this thread's device buffers) or on the device */
-/* A piece of a stream for lzs_compress_incremental(): the data is `prefix` (history and the
+/* A piece that begins inside a long match (pc->ext_off): its length nibbles first, behind bit *total of d_out (d_exit as scratch).
+ * *c_first: where the tokens start behind them; *ext_now: the match is still open -- it covers all the data there is; *total
+ * grows by the bits written.  LZS_OK or the error reported. */
+static int resume_open_match(const cseg_table_t *t, const piece_t *pc, void *d_out, const void *d_in, uint32_t n, void *stream,
+                             const char *who, uint32_t *c_first, uint32_t *ext_now, uint64_t *total)
+{
+    uint32_t res[4];
+    /* (pc->stop: the data is known to end at n -- the run is closed like in a last piece, only the marker waits) */
+    HIP_TRY_RET(lzs_hip_launch_extend_resume(d_out, pc->bit0, d_in, n, pc->c0, pc->ext_off, pc->last || pc->stop, t->d_exit, stream), who);
+    HIP_TRY_RET(lzs_hip_d2h(res, t->d_exit, sizeof(res), stream), "hipMemcpy D2H");
+    HIP_TRY_RET(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+    *c_first = res[0];
+    *ext_now = res[1] ? pc->ext_off : 0;
+    *total += ((uint64_t)res[3] << 32) | res[2];
+    return LZS_OK;
+}
+
+/* After a round: a segment is entered where the one before stopped (segment 0 where the call says), and those for which that is
+ * news are compressed again.  Host code only.  Returns how many are dirty now. */
+LZS_HIDDEN uint32_t settle_compress_entries(uint32_t *entry, uint8_t *dirty, const uint32_t *exits, uint32_t nseg)
+{
+    uint32_t ndirty = 0;
+    dirty[0] = 0;
+    for (uint32_t k = 1; k < nseg; k++) {
+        dirty[k] = exits[k - 1] != entry[k];
+        if (dirty[k]) { entry[k] = exits[k - 1]; ndirty++; }
+    }
+    return ndirty;
+}
+
+/* The entry rounds: every segment entered at its own start (no token starts before c_first), then those whose predecessor ended
+ * elsewhere again from there, until all agree.  `lim`: no token starts at or behind it; `open_info`: a piece wants the open-match
+ * reports; `ext_now`: a match still open after its nibbles covers all the data -- the tables are set for the stages behind, but
+ * this piece has no tokens and no round.  Then the bit counts (and reports) are fetched.  LZS_OK or the error reported. */
+static int entry_rounds(cseg_table_t *t, void *stream, const char *who, const void *d_in, uint32_t n, uint32_t c_first, uint32_t lim,
+                        int open_info, uint32_t ext_now, double *t0)
+{
+    const int debug = lzs_env()->stream_debug;
+    const uint32_t nseg = t->nseg;
+    for (uint32_t k = 0; k < nseg; k++) {
+        t->entry[k] = k * t->seg > c_first ? k * t->seg : c_first;
+        t->dirty[k] = 1; t->exits[k] = t->entry[k]; t->nbits[k] = 0; t->open[2 * k] = t->open[2 * k + 1] = 0;
+    }
+    for (uint32_t round = 0, ndirty = ext_now ? 0 : nseg; ndirty; round++) {
+        HIP_TRY_RET(lzs_hip_h2d(t->d_entry, t->entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_RET(lzs_hip_h2d(t->d_dirty, t->dirty, nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_RET(lzs_hip_launch_compress_segments(t->d_slots, t->slot_stride, d_in, n, t->seg, nseg, t->d_entry, t->d_dirty, t->d_exit, t->d_nbits,
+                                                     NULL, NULL, lim, open_info ? t->d_open : NULL, stream), who);
+        HIP_TRY_RET(lzs_hip_d2h(t->exits, t->d_exit, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
+        HIP_TRY_RET(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+        const uint32_t was = ndirty;
+        ndirty = settle_compress_entries(t->entry, t->dirty, t->exits, nseg);
+        if (debug) { const double t1 = now_ms(); fprintf(stderr, "liblzs stream: round %u compressed %u segments in %.2f ms; %u to redo\n", round, was, t1 - *t0, ndirty); *t0 = t1; }
+    }
+    if (ext_now) return LZS_OK;
+    /* what every segment gave */
+    HIP_TRY_RET(lzs_hip_d2h(t->nbits, t->d_nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy D2H");
+    if (open_info) HIP_TRY_RET(lzs_hip_d2h(t->open, t->d_open, sizeof(uint32_t) * 2 * nseg, stream), "hipMemcpy D2H");
+    HIP_TRY_RET(lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+    return LZS_OK;
+}
+
+/* The last token of a piece that is not the last may be a match that reaches the end of the data so far (c_exit >= n, in a piece
+ * that had tokens: n > c_first): it may go on in the next piece.  Its full groups of 15 stand; the closing nibble is taken back
+ * and the bytes it covered wait for more data (state COMPRESS_EXTENDED, :750-758).  Host code only.  0: no such match.  1: four
+ * bits less for the last segment that reports an open match -- nbits[] has changed --, *c_exit and *ext_exit say from where and
+ * at which offset the match goes on.  -1: no segment reports one, or that one has no nibble to give. */
+LZS_HIDDEN int open_match_take_back(const uint32_t *open, uint64_t *nbits, uint32_t nseg, uint32_t n, uint32_t c_first, uint32_t *c_exit,
+                                    uint32_t *ext_exit)
+{
+    if (*c_exit < n || n <= c_first) return 0;
+    uint32_t k = nseg;
+    while (k > 0 && open[2 * (k - 1)] == 0) k--;
+    if (k == 0 || nbits[k - 1] < 4) return -1;
+    const uint32_t off = open[2 * (k - 1)], start = open[2 * (k - 1) + 1];
+    nbits[k - 1] -= 4;
+    *c_exit = n - (n - start - 8u) % 15u;
+    *ext_exit = off;
+    return 1;
+}
+
+/* Where every segment's bits go -- the prefix sum of the bit counts from bit *total on, which it leaves at the end of them -- and
+ * the stitch that shifts the slots there (none if the piece had no tokens: ext_now).  Segments whose bits did not fit their slot
+ * (a match running on for more than ~120 KB past the segment) are compressed once more, ORed straight into place. */
+static int place_and_stitch(cseg_table_t *t, void *stream, const char *who, void *d_out, const void *d_in, uint32_t n, uint32_t lim,
+                            uint32_t ext_now, int end_marker, uint64_t *total, double *t0)
+{
+    const uint32_t nseg = t->nseg;
+    uint32_t nbig = 0;
+    for (uint32_t k = 0; k < nseg; k++) { t->bit_at[k] = *total; *total += t->nbits[k]; }
+    HIP_TRY_RET(lzs_hip_h2d(t->d_bit_at, t->bit_at, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
+    if (!ext_now)
+        HIP_TRY_RET(lzs_hip_launch_stitch_segments(d_out, t->d_slots, t->slot_stride, t->d_bit_at, t->d_nbits, nseg, end_marker, stream), who);
+    for (uint32_t k = 0; k < nseg; k++) { t->dirty[k] = t->nbits[k] > 8u * (uint64_t)t->slot_stride; nbig += t->dirty[k]; }
+    if (nbig) {
+        HIP_TRY_RET(lzs_hip_h2d(t->d_dirty, t->dirty, nseg, stream), "hipMemcpy H2D");
+        HIP_TRY_RET(lzs_hip_launch_compress_segments(t->d_slots, t->slot_stride, d_in, n, t->seg, nseg, t->d_entry, t->d_dirty, t->d_exit, t->d_nbits,
+                                                     d_out, t->d_bit_at, lim, NULL, stream), who);
+    }
+    if (lzs_env()->stream_debug) { lzs_hip_stream_sync(stream); const double t1 = now_ms(); fprintf(stderr, "liblzs stream: stitch %.2f ms\n", t1 - *t0); *t0 = t1; }
+    return LZS_OK;
+}
+
+/* in/out on the host (dev == 0: staged through this thread's device buffers) or on the device.
+ * With pc, a piece of a stream for lzs_compress_incremental(): the data is `prefix` (history and the
  * bytes the call before could not encode yet) followed by `in`; encoding starts at c0, inside a
  * long match if ext_off is set, at bit bit0 of the first output byte (whose earlier bits are in
  * `first`).  Unless `last`, it stops where the tokens are no longer decided by the data so far. */
-
-LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t *in, size_t n, int dev, int *status,
-                                    piece_t *pc)
+LZS_HIDDEN size_t stream_compress_piece(uint8_t *out, size_t cap, const uint8_t *in, size_t n, int dev, int *status, piece_t *pc)
 {
     const char *who = pc ? "lzs_compress_incremental" : dev ? "lzs_compress_stream_device" : "lzs_compress";
-    /* (a short piece of the incremental interface, whose block collects ~10 KiB, is all latency too:
-     * at 512-byte calls 41 MB/s in 4 KiB segments, 62 in 1 KiB, 67 in 512 B) */
-    const uint32_t STREAM_SEG = stream_seg(n);
-    const uint32_t nseg = n ? (uint32_t)((n + STREAM_SEG - 1) / STREAM_SEG) : 1u;
+    cseg_table_t t = { .seg = stream_seg(n) };
+    const uint32_t nseg = t.nseg = n ? (uint32_t)((n + t.seg - 1) / t.seg) : 1u;
+    t.slot_stride = (LZS_COMPRESSED_MAX((size_t)t.seg) + 15u) & ~(size_t)15u;
     const size_t worst = LZS_COMPRESSED_MAX(n - (pc ? pc->c0 : 0)) + 8;
-    const int end_marker = !pc || pc->last;
+    const int end_marker = !pc || pc->last, debug = lzs_env()->stream_debug;      /* LZS_STREAM_DEBUG: stage times on stderr */
     uint32_t lim = end_marker ? (uint32_t)n : (n > LZS_MAX_LOOK_AHEAD_LEN ? (uint32_t)n - LZS_MAX_LOOK_AHEAD_LEN : 0u);
     if (pc && !pc->last && pc->stop) lim = pc->stop < n ? pc->stop : (uint32_t)n;       /* (the caller vouches that the data ends at n) */
+    uint32_t c_first = pc ? pc->c0 : 0, ext_now = 0;
+    uint64_t total = pc ? pc->bit0 : 0;
     size_t result = 0;
-    int e = 0, rc = LZS_OK;
-    void *d_in = NULL, *d_out = NULL, *d_aux = NULL, *d_slots = NULL;
-    const size_t slot_stride = (LZS_COMPRESSED_MAX((size_t)STREAM_SEG) + 15u) & ~(size_t)15u;
-    uint32_t *entry = NULL, *exitp = NULL, *openi = NULL;
-    uint64_t *nbits = NULL, *bitat = NULL;
-    uint8_t *dirty = NULL;
-    tls_error[0] = 0;
-    if (require_device() != LZS_OK) goto failed;
-    staging_t *st = staging_get();
-    if (!st) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
-    /* the per-segment tables, in pinned memory (they travel every round) */
-    nbits = (uint64_t *)staging_host_tables(st, ((size_t)nseg + 16u) * (2u * 8u + 4u * 4u + 1u));
-    if (!nbits) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
-    bitat = nbits + nseg; entry = (uint32_t *)(bitat + nseg); exitp = entry + nseg; openi = exitp + nseg;
-    dirty = (uint8_t *)(openi + 2 * (size_t)nseg);
-
-    if (!st->stream) HIP_TRY_OR(failed, lzs_hip_stream_create(&st->stream), "hipStreamCreate");
+    int e = 0, rc, took = 0;
+    void *d_in = NULL, *d_out = NULL, *d_aux = NULL, *tables = NULL;
+    staging_t *st = NULL;
+    /* ---- set-up: the stream and its output on the device, the segment table; in, and the output cleared */
+    if ((rc = stream_call_begins(who, csegtab_host_bytes(nseg), &st, &tables)) != LZS_OK) goto done;
     void *stream = st->stream;
-    /* device arrays in one allocation: bit_at, nbits (8 B each), entry, exit, open info (4 + 4 + 8 B), dirty */
-    const size_t aux_bytes = (size_t)nseg * (8 + 8 + 4 + 4 + 8 + 1) + 64;
-    if (dev) { d_in = (void *)in; d_out = out; }
-    else {
-        e = staging_reserve(st, BUF_IN, n + 64, &d_in);
-        if (!e) e = staging_reserve(st, BUF_OUT, worst + 1024, &d_out);
-    }
-    if (!e) e = staging_reserve(st, BUF_AUX, aux_bytes, &d_aux);
-    if (!e) e = staging_reserve(st, BUF_KEEP, slot_stride * nseg + 64, &d_slots);
-    if (e) { fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
-    uint64_t *d_bitat = (uint64_t *)d_aux;
-    uint64_t *d_nbits = d_bitat + nseg;
-    uint32_t *d_entry = (uint32_t *)(d_nbits + nseg);
-    uint32_t *d_exit = d_entry + nseg;
-    uint32_t *d_open = d_exit + nseg;
-    uint8_t *d_dirty = (uint8_t *)(d_open + 2 * (size_t)nseg);
-
-    const int debug = lzs_env()->stream_debug;      /* LZS_STREAM_DEBUG: stage times on stderr */
+    if (dev) { d_in = (void *)in; d_out = out; } else e = staging_reserve(st, BUF_IN, n + 64, &d_in);
+    if (!e && !dev) e = staging_reserve(st, BUF_OUT, worst + 1024, &d_out);
+    if (!e) e = staging_reserve(st, BUF_AUX, csegtab_dev_bytes(nseg), &d_aux);
+    if (!e) e = staging_reserve(st, BUF_KEEP, t.slot_stride * nseg + 64, &t.d_slots);
+    if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto done; }
+    csegtab_lay_out(&t, tables, d_aux);
     double t0 = debug ? now_ms() : 0, t1;
-    if (!dev) {
-        const size_t pre = pc ? pc->prefix_len : 0;
-        if (pre) HIP_TRY_OR(failed, lzs_hip_h2d(d_in, pc->prefix, pre, stream), "hipMemcpy H2D");
-        HIP_TRY_OR(failed, lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
-    }
+    if (!dev && (rc = stream_copy_in(d_in, pc ? pc->prefix : NULL, pc ? pc->prefix_len : 0, in, n, stream)) != LZS_OK) goto done;
     /* (a caller's device buffer is cleared only as far as it was promised: LZS_COMPRESSED_MAX(n) + 1024) */
-    HIP_TRY_OR(failed, lzs_hip_memset(d_out, 0, dev && worst + 1024 > cap ? cap : worst + 1024, stream), "hipMemset");
+    HIP_TRY_OR(done, lzs_hip_memset(d_out, 0, dev && worst + 1024 > cap ? cap : worst + 1024, stream), "hipMemset");
     if (debug) { lzs_hip_stream_sync(stream); t1 = now_ms(); fprintf(stderr, "liblzs stream: %zu B, %u segments; H2D + memset %.2f ms\n", n, nseg, t1 - t0); t0 = t1; }
-    uint32_t c_first = 0, ext_now = 0;
-    uint64_t total = 0;
+    /* ---- the tokens: behind the bits of the call before, [the nibbles of the match it left open], the entry rounds */
+    if (pc && pc->bit0) HIP_TRY_OR(done, lzs_hip_h2d(d_out, &pc->first, 1, stream), "hipMemcpy H2D");
+    if (pc && pc->ext_off && (rc = resume_open_match(&t, pc, d_out, d_in, (uint32_t)n, stream, who, &c_first, &ext_now, &total)) != LZS_OK) goto done;
+    if ((rc = entry_rounds(&t, stream, who, d_in, (uint32_t)n, c_first, lim, pc != NULL, ext_now, &t0)) != LZS_OK) goto done;
     if (pc) {
-        c_first = pc->c0;
-        total = pc->bit0;
-        if (pc->bit0) HIP_TRY_OR(failed, lzs_hip_h2d(d_out, &pc->first, 1, stream), "hipMemcpy H2D");
-        if (pc->ext_off) {
-            /* the piece begins inside a long match: its length nibbles first (d_exit as scratch) */
-            uint32_t res[4];
-            /* (pc->stop: the data is known to end at n -- the run is closed like in a last piece, only the marker waits) */
-            HIP_TRY_OR(failed, lzs_hip_launch_extend_resume(d_out, pc->bit0, d_in, (uint32_t)n, pc->c0, pc->ext_off, pc->last || pc->stop, d_exit, stream), who);
-            HIP_TRY_OR(failed, lzs_hip_d2h(res, d_exit, sizeof(res), stream), "hipMemcpy D2H");
-            HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-            c_first = res[0];
-            ext_now = res[1] ? pc->ext_off : 0;
-            total += ((uint64_t)res[3] << 32) | res[2];
-        }
-    }
-    for (uint32_t k = 0; k < nseg; k++) {
-        entry[k] = k * STREAM_SEG > c_first ? k * STREAM_SEG : c_first;
-        dirty[k] = 1; exitp[k] = entry[k]; nbits[k] = 0; openi[2 * k] = openi[2 * k + 1] = 0;
-    }
-    /* (a match still open after the nibbles covers all the data there is: no tokens in this piece) */
-    for (uint32_t round = 0, ndirty = ext_now ? 0 : nseg; ndirty; round++) {
-        HIP_TRY_OR(failed, lzs_hip_h2d(d_entry, entry, sizeof(uint32_t) * nseg, stream), "hipMemcpy H2D");
-        HIP_TRY_OR(failed, lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY_OR(failed, lzs_hip_launch_compress_segments(d_slots, slot_stride, d_in, (uint32_t)n, STREAM_SEG, nseg,
-                                                 d_entry, d_dirty, d_exit, d_nbits, NULL, NULL, lim, pc ? d_open : NULL, stream), who);
-        HIP_TRY_OR(failed, lzs_hip_d2h(exitp, d_exit, sizeof(uint32_t) * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-        /* a segment is entered where the one before stopped (its own start for segment 0) */
-        const uint32_t was = ndirty;
-        ndirty = 0;
-        dirty[0] = 0;
-        for (uint32_t k = 1; k < nseg; k++) {
-            dirty[k] = exitp[k - 1] != entry[k];
-            if (dirty[k]) { entry[k] = exitp[k - 1]; ndirty++; }
-        }
-        if (debug) { t1 = now_ms(); fprintf(stderr, "liblzs stream: round %u compressed %u segments in %.2f ms; %u to redo\n", round, was, t1 - t0, ndirty); t0 = t1; }
-    }
-    if (!ext_now) {
-        HIP_TRY_OR(failed, lzs_hip_d2h(nbits, d_nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy D2H");
-        if (pc) HIP_TRY_OR(failed, lzs_hip_d2h(openi, d_open, sizeof(uint32_t) * 2 * nseg, stream), "hipMemcpy D2H");
-        HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-    }
-    if (pc) {
-        pc->c_exit = ext_now ? c_first : exitp[nseg - 1];
+        pc->c_exit = ext_now ? c_first : t.exits[nseg - 1];
         pc->ext_exit = ext_now;
-        if (!pc->last && !pc->stop && !ext_now && pc->c_exit >= n && n > c_first) {
-            /* The last token is a match that reaches the end of the data so far: it may go on in
-             * the next piece.  Its full groups of 15 stand; the closing nibble is taken back and
-             * the bytes it covered wait for more data (state COMPRESS_EXTENDED, :750-758). */
-            uint32_t k = nseg;
-            while (k > 0 && openi[2 * (k - 1)] == 0) k--;
-            if (k == 0 || nbits[k - 1] < 4) {
-                rc = fail(LZS_E_HIP, "%s: inconsistent state from the device (piece of %zu bytes from %u ends at %u, no open match reported)",
-                          who, n, c_first, pc->c_exit);
-                goto failed;
-            }
-            const uint32_t off = openi[2 * (k - 1)], start = openi[2 * (k - 1) + 1];
-            const uint32_t rest = ((uint32_t)n - start - 8u) % 15u;
-            nbits[k - 1] -= 4;
-            HIP_TRY_OR(failed, lzs_hip_h2d(d_nbits, nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
-            pc->c_exit = (uint32_t)n - rest;
-            pc->ext_exit = off;
-        }
+        if (!pc->last && !pc->stop && !ext_now) took = open_match_take_back(t.open, t.nbits, nseg, (uint32_t)n, c_first, &pc->c_exit, &pc->ext_exit);
     }
-    for (uint32_t k = 0; k < nseg; k++) { bitat[k] = total; total += nbits[k]; }
+    if (took < 0) { rc = fail(LZS_E_HIP, "%s: inconsistent state from the device (piece of %zu bytes from %u ends at %u, no open match reported)", who, n, c_first, pc->c_exit); goto done; }
+    if (took > 0) HIP_TRY_OR(done, lzs_hip_h2d(t.d_nbits, t.nbits, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
+    if ((rc = place_and_stitch(&t, stream, who, d_out, d_in, (uint32_t)n, lim, ext_now, end_marker, &total, &t0)) != LZS_OK) goto done;
     if (pc) pc->nbits = total;
-    HIP_TRY_OR(failed, lzs_hip_h2d(d_bitat, bitat, sizeof(uint64_t) * nseg, stream), "hipMemcpy H2D");
-    if (!ext_now)
-        HIP_TRY_OR(failed, lzs_hip_launch_stitch_segments(d_out, d_slots, slot_stride, d_bitat, d_nbits, nseg, end_marker, stream), who);
-    /* segments whose bits did not fit their slot (a match running on for more than ~120 KB past
-     * the segment): once more, ORed straight into place */
-    uint32_t nbig = 0;
-    for (uint32_t k = 0; k < nseg; k++) { dirty[k] = nbits[k] > 8u * (uint64_t)slot_stride; nbig += dirty[k]; }
-    if (nbig) {
-        HIP_TRY_OR(failed, lzs_hip_h2d(d_dirty, dirty, nseg, stream), "hipMemcpy H2D");
-        HIP_TRY_OR(failed, lzs_hip_launch_compress_segments(d_slots, slot_stride, d_in, (uint32_t)n, STREAM_SEG, nseg,
-                                                 d_entry, d_dirty, d_exit, d_nbits, d_out, d_bitat, lim, NULL, stream), who);
-    }
-    if (debug) { lzs_hip_stream_sync(stream); t1 = now_ms(); fprintf(stderr, "liblzs stream: stitch %.2f ms\n", t1 - t0); t0 = t1; }
-    result = end_marker ? (size_t)((total + 9 + 7) / 8)        /* end marker, padded to a byte */
-                        : (size_t)((total + 7) / 8);            /* a piece: the last byte may be partial */
+    result = (size_t)((total + (end_marker ? 9 : 0) + 7) / 8);  /* (the end marker, padded to a byte; a piece: the last byte may be partial) */
     if (result > cap) result = cap;                            /* cut at the capacity, prefix unchanged */
-    if (!dev) HIP_TRY_OR(failed, lzs_hip_d2h(out, d_out, result, stream), "hipMemcpy D2H");
-    HIP_TRY_OR(failed, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
-    return stream_call_ends(result, LZS_OK, dev, who, status);
-
-failed:
-    return stream_call_ends(0, rc == LZS_OK ? LZS_E_HIP : rc, dev, who, status);
+    if (!dev) HIP_TRY_OR(done, lzs_hip_d2h(out, d_out, result, stream), "hipMemcpy D2H");
+    HIP_TRY_OR(done, lzs_hip_stream_sync(stream), "hipStreamSynchronize");
+done:
+    return stream_call_ends(result, rc, dev, who, status);
 }
 
 LZS_HIDDEN size_t stream_compress(uint8_t *out, size_t cap, const uint8_t *in, size_t n, int dev, int *status)
@@ -451,29 +503,20 @@ LZS_HIDDEN size_t stream_decompress(uint8_t *out, size_t cap, const uint8_t *in,
     const char *who = dp ? "lzs_decompress_incremental" : dev ? "lzs_decompress_stream_device" : concat ? "lzs_decompress_concat" : "lzs_decompress";
     seg_table_t t = { .label = "stream decode", .seg = stream_dec_seg(n) };
     const uint32_t nseg = t.nseg = (uint32_t)((n + t.seg - 1) / t.seg);
-    int e = 0, rc = LZS_OK;
-    void *d_in = NULL, *d_out = NULL, *d_aux = NULL, *d_origin = NULL, *d_marks = NULL;
-    tls_error[0] = 0;
-    /* ---- set-up: the stream on the device, the segment table (the host side in pinned memory: it travels every round) */
-    if (require_device() != LZS_OK) goto failed;
-    staging_t *st = staging_get();
-    if (!st) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
-    void *tables = staging_host_tables(st, ((size_t)nseg + 16u) * (5u * 4u + 2u));
-    if (!tables) { fail(LZS_E_NOMEM, "%s: out of host memory", who); goto failed; }
-    if (!st->stream) HIP_TRY_OR(failed, lzs_hip_stream_create(&st->stream), "hipStreamCreate");
+    int e = 0, rc;
+    void *d_in = NULL, *d_out = NULL, *d_aux = NULL, *d_origin = NULL, *d_marks = NULL, *tables = NULL;
+    staging_t *st = NULL;
+    /* ---- set-up: the stream on the device, the segment table */
+    if ((rc = stream_call_begins(who, ((size_t)nseg + 16u) * (5u * 4u + 2u), &st, &tables)) != LZS_OK) goto failed;
     void *stream = st->stream;
     if (dev) d_in = (void *)in; else e = staging_reserve(st, BUF_IN, n + 64, &d_in);
     if (!e) e = staging_reserve(st, BUF_AUX, (size_t)nseg * (4 * 4 + 2) + 128, &d_aux);
     if (!e) e = staging_reserve(st, BUF_MARKS, (size_t)nseg * LZS_SCAN_MARK_WORDS * 4u, &d_marks);
-    if (e) { fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
+    if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
     segtab_lay_out(&t, (uint32_t *)tables, (uint32_t *)d_aux, 0);
     const int debug = lzs_env()->stream_debug;
     double t0 = debug ? now_ms() : 0, t1;
-    if (!dev) {
-        const size_t pre = dp ? dp->prefix_len : 0;
-        if (pre) HIP_TRY_OR(failed, lzs_hip_h2d(d_in, dp->prefix, pre, stream), "hipMemcpy H2D");
-        HIP_TRY_OR(failed, lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
-    }
+    if (!dev && (rc = stream_copy_in(d_in, dp ? dp->prefix : NULL, dp ? dp->prefix_len : 0, in, n, stream)) != LZS_OK) goto failed;
     /* ---- SCAN */
     if ((rc = scan_rounds(&t, stream, who, d_in, (uint32_t)n, (uint32_t)n, dp ? dp->entry0 : 0u, concat, (uint32_t *)d_marks, &t0)) != LZS_OK) goto failed;
     /* ---- placement: where every segment's output begins; how many segments a piece decodes, and in which state it goes on */
@@ -493,7 +536,7 @@ LZS_HIDDEN size_t stream_decompress(uint8_t *out, size_t cap, const uint8_t *in,
         /* ---- DECODE, behind the history (final bytes: origin "clean" = all ones) */
         if (dev) d_out = out; else e = staging_reserve(st, BUF_OUT, (size_t)before + produce + 64, &d_out);
         if (!e) e = staging_reserve(st, BUF_KEEP, 4 * ((size_t)before + produce) + 64, &d_origin);
-        if (e) { fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
+        if (e) { rc = fail(LZS_E_NOMEM, "%s: device allocation failed: %s", who, lzs_hip_strerror(e)); goto failed; }
         if (before) {
             HIP_TRY_OR(failed, lzs_hip_h2d(d_out, dp->hist, before, stream), "hipMemcpy H2D");
             HIP_TRY_OR(failed, lzs_hip_memset(d_origin, 0xFF, 4 * (size_t)before, stream), "hipMemset");
@@ -515,7 +558,7 @@ LZS_HIDDEN size_t stream_decompress(uint8_t *out, size_t cap, const uint8_t *in,
     return stream_call_ends(produce, LZS_OK, dev, who, status);
 
 failed:
-    return stream_call_ends(0, rc == LZS_OK ? LZS_E_HIP : rc, dev, who, status);
+    return stream_call_ends(0, rc, dev, who, status);
 }
 
 /* A batch of blocks decompressed like one long stream: every block is cut into segments of its

@@ -80,6 +80,15 @@ static void called(unsigned which, uint64_t size)
     for (size_t i = 0; i < sizeof rec; i++) g_call_hash = (g_call_hash ^ ((const uint8_t *)rec)[i]) * 0x100000001B3ull;
 }
 uint64_t lzs_shim_call_hash(int reset) { const uint64_t h = g_call_hash; if (reset) g_call_hash = 0xCBF29CE484222325ull; return h; }
+/* ... and, apart from it (the recorded digests of "inctrace" fold the hash above), what the compress side of lzs_stream.c launched:
+ * (which launch, five of its arguments) of the segment, stitch and extend-resume launches, in order ("streamtrace"). */
+static _Thread_local uint64_t g_launch_hash = 0xCBF29CE484222325ull;
+static void launch_noted(unsigned which, uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t e)
+{
+    const uint64_t rec[6] = { which, a, b, c, d, e };
+    for (size_t i = 0; i < sizeof rec; i++) g_launch_hash = (g_launch_hash ^ ((const uint8_t *)rec)[i]) * 0x100000001B3ull;
+}
+uint64_t lzs_shim_launch_hash(int reset) { const uint64_t h = g_launch_hash; if (reset) g_launch_hash = 0xCBF29CE484222325ull; return h; }
 
 int lzs_hip_malloc(void **p, size_t bytes) { called(1, bytes); return shim_alloc(p, bytes, &g_dev_bytes); }
 int lzs_hip_free(void *p) { shim_free(p, &g_dev_bytes); return 0; }
@@ -192,6 +201,9 @@ int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const vo
                                      void *d_out, const uint64_t *d_bit_at, uint32_t lim, uint32_t *d_open, void *stream)
 {
     (void)stream;
+    uint32_t ndirty = 0;
+    for (uint32_t k = 0; k < nseg; k++) ndirty += !d_dirty || d_dirty[k];
+    launch_noted(1, nseg, ndirty, d_out != NULL, lim, d_open != NULL);
     for (uint32_t k = 0; k < nseg; k++) {
         if (d_dirty && !d_dirty[k]) continue;
         const uint32_t s = k * seg;
@@ -215,6 +227,7 @@ int lzs_hip_launch_stitch_segments(void *d_out, const void *d_slots, size_t slot
                                    uint32_t nseg, int end_marker, void *stream)
 {
     (void)stream;
+    launch_noted(2, nseg, (uint64_t)end_marker, 0, 0, 0);
     for (uint32_t k = 0; k < nseg; k++) {
         if (d_nbits[k] > 8u * (uint64_t)slot_stride) continue;   /* (ORed in directly by the second segment launch) */
         const uint8_t *slot = (const uint8_t *)d_slots + (size_t)k * slot_stride;
@@ -232,6 +245,7 @@ int lzs_hip_launch_extend_resume(void *d_out, uint32_t bit0, const void *d_in, u
                                  uint32_t *d_result, void *stream)
 {
     (void)stream;
+    launch_noted(3, bit0, n, c0, off, (uint64_t)last);
     const uint8_t *in = (const uint8_t *)d_in;
     uint32_t c = c0;
     while (c < n && in[c] == in[c - off]) c++;

@@ -10,7 +10,8 @@
  *   low-memory block, and what each of its calls does against a table ("inctrace"); the one-shot calls on both routes; decompression by many wavefronts ("streamdec": the scan rounds with
  *   their settle rule and all-0xFF shortcut, placement, one stream / concatenated streams / batches by segments / pieces of
  *   the incremental interface, each compared with the same call by one wavefront); the route decision and the pipeline's plan
- *   against a table ("routes"); the one-after-the-other route's copy layouts where they switch ("layouts").
+ *   against a table ("routes"); the one-after-the-other route's copy layouts where they switch ("layouts"); the segmented stream
+ *   compressor's host path call by call against a table ("streamtrace": results, calls and launches of one-shot calls and pieces).
  * Every result is compared with the oracle.  Exit code 0 = all cases passed (the sanitizers make it non-zero themselves).
  * TEST INFRASTRUCTURE ONLY.
  */
@@ -833,6 +834,240 @@ static void streamdec(void)
     unsetenv("LZS_ROUTE"); unsetenv("LZS_FORCE_STREAM");
 }
 
+/* ---------------------------------------------------------------- the segmented stream compressor's host path, against a table
+ * ("streamtrace": lzs_stream.c's stream_compress_piece() over the shim's segment, stitch and extend-resume launches, in segments
+ * of LZS_STREAM_SEG bytes).  A row is what one call gave -- bytes returned, the FNV-1a of the whole output buffer with its 0xA5
+ * guard, for a piece c_exit, ext_exit and nbits -- and what it asked of the "device": the shim's hash of its syncs, copies, fills
+ * and allocations with their sizes, and the hash of its launches with their arguments, each in order.  The rows were recorded
+ * with this driver linked against lzs_stream.c as it was BEFORE that function's stages became functions, never from the code
+ * under test ("streamtrace-rows" prints them).  Two of the stages are pure and have tables of their own, made by hand. */
+typedef struct { const char *name; size_t bytes; uint64_t out, calls, launches; uint32_t c_exit, ext_exit; uint64_t nbits; } stream_row_t;
+static const stream_row_t stream_rows[] = {
+    { "text of 6145, segments of the default size, into 6917", 3554, 0xA4290434FF54C793ull, 0xD2B6114263ED0D21ull, 0x70A287C3F2F5685Eull, 0, 0, 0 },
+    { "text of 20000, segments of 256, into 22503", 11314, 0xBF102CA850AD6F3Cull, 0x7BDF80FCFE03493Full, 0x7BCD1CA002B66CB6ull, 0, 0, 0 },
+    { "text of 20000, segments of 256, device buffers, into 23527", 11314, 0xA64C33631A17A40Full, 0x182777C91AE2A40Eull, 0x7BCD1CA002B66CB6ull, 0, 0, 0 },
+    { "text of 20000, segments of 512, into 22503", 11314, 0xBF102CA850AD6F3Cull, 0x71AA4F1B9DB94543ull, 0x22C37C5692CAE833ull, 0, 0, 0 },
+    { "text of 20000, segments of 512, device buffers, into 23527", 11314, 0xA64C33631A17A40Full, 0x9FA3FA37C7F6D39Aull, 0x22C37C5692CAE833ull, 0, 0, 0 },
+    { "an oversized segment, segments of 256, into 851", 329, 0x31E6A36409D52830ull, 0x8CB10756D7D1089Dull, 0x23247CE7C64ED221ull, 0, 0, 0 },
+    { "walks that never merge, segments of 256, into 9219", 6401, 0x94A0E5F4C80F05D7ull, 0xBE9D0FEB3D7BEC38ull, 0x167AB13B44D0D9E5ull, 0, 0, 0 },
+    { "a run and a period of 2, segments of the default size, into 101259", 29967, 0x8FD66CCD7309A3F4ull, 0x5B105169EC8A6C18ull, 0x43523FFFD20C472Cull, 0, 0, 0 },
+    { "text of 20000, segments of 256, into 0", 0, 0x7A1AD6AE7FF8A1F2ull, 0x902936067DECC239ull, 0x7BCD1CA002B66CB6ull, 0, 0, 0 },
+    { "text of 20000, segments of 256, into 1", 1, 0xF0C34B11233D83FBull, 0x18D4B3B2152C7C18ull, 0x7BCD1CA002B66CB6ull, 0, 0, 0 },
+    { "text of 20000, segments of 256, into 11313", 11313, 0xDC5CAC1E0289BAE5ull, 0x650BAE46DAFF29CCull, 0x7BCD1CA002B66CB6ull, 0, 0, 0 },
+    { "text of 20000, segments of 256, device buffers, into 22603", 11314, 0xB976EC1CDD34A2BFull, 0x2B04CBCBE3B06917ull, 0x7BCD1CA002B66CB6ull, 0, 0, 0 },
+    { "piece: bit0 = 3 behind a first byte, a prefix", 3071, 0xD3F0FE3DEC5509C9ull, 0x089264BD013B2837ull, 0xD8BBD6910891DD1Dull, 8986, 0, 24561 },
+    { "piece: resumes a match that ends inside it", 2452, 0x5129109D32FD4966ull, 0x661CD7A5C0D55A72ull, 0x7CF9B41ECFBE7BC5ull, 8986, 0, 19612 },
+    { "piece: resumes a match that covers all its data", 18, 0x281355E2FE749B6Eull, 0x6A8D477D69DDEF46ull, 0x32029BD522C3CF7Aull, 4695, 7, 137 },
+    { "piece: the last token reaches the end of the data", 2336, 0x3FE56F8CA5DD0CDAull, 0x4D7FFAE2B1E9B954ull, 0x1488DC19DEE52ABDull, 9398, 7, 18681 },
+    { "piece: stop below n", 1159, 0xD353C7A0709ACDE8ull, 0x7963F5598B533E62ull, 0xD1ADF9987A3E229Eull, 7003, 0, 9265 },
+    { "piece: last, with an empty tail", 2, 0xF3A98A2136F64D75ull, 0xF522C94BCC875F97ull, 0x8FA7BDC35AB3D00Bull, 3000, 0, 6 },
+};
+uint64_t lzs_shim_launch_hash(int reset);
+static uint64_t fnv1a(const uint8_t *p, size_t n)
+{
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (size_t i = 0; i < n; i++) h = (h ^ p[i]) * 0x100000001B3ull;
+    return h;
+}
+/* (every call starts with nothing kept by the thread: its allocations are part of what is recorded) */
+static void st_begin(const char *seg)
+{
+    if (seg) setenv("LZS_STREAM_SEG", seg, 1); else unsetenv("LZS_STREAM_SEG");
+    lzs_release_thread_cache();
+    lzs_shim_call_hash(1); lzs_shim_launch_hash(1);
+}
+static void st_done(const char *name, size_t bytes, const uint8_t *buf, size_t buf_len, const piece_t *pc)
+{
+    const stream_row_t got = { name, bytes, fnv1a(buf, buf_len), lzs_shim_call_hash(1), lzs_shim_launch_hash(1),
+                               pc ? pc->c_exit : 0, pc ? pc->ext_exit : 0, pc ? pc->nbits : 0 };
+    if (trace_print) {
+        printf("    { \"%s\", %zu, 0x%016llXull, 0x%016llXull, 0x%016llXull, %u, %u, %llu },\n", name, got.bytes, (unsigned long long)got.out,
+               (unsigned long long)got.calls, (unsigned long long)got.launches, got.c_exit, got.ext_exit, (unsigned long long)got.nbits);
+        return;
+    }
+    const stream_row_t *row = NULL;
+    for (unsigned i = 0; i < sizeof stream_rows / sizeof stream_rows[0] && stream_rows[i].name; i++) if (!strcmp(stream_rows[i].name, name)) row = &stream_rows[i];
+    CHECK(row, "%s: no row in the table", name);
+    if (row) CHECK(row->bytes == got.bytes && row->out == got.out && row->calls == got.calls && row->launches == got.launches &&
+                   row->c_exit == got.c_exit && row->ext_exit == got.ext_exit && row->nbits == got.nbits,
+                   "%s: %zu bytes, output %016llx, calls %016llx, launches %016llx, c_exit %u, ext_exit %u, %llu bits; recorded: %zu, %016llx, %016llx, %016llx, %u, %u, %llu",
+                   name, got.bytes, (unsigned long long)got.out, (unsigned long long)got.calls, (unsigned long long)got.launches, got.c_exit, got.ext_exit,
+                   (unsigned long long)got.nbits, row->bytes, (unsigned long long)row->out, (unsigned long long)row->calls, (unsigned long long)row->launches,
+                   row->c_exit, row->ext_exit, (unsigned long long)row->nbits);
+}
+
+/* one input through lzs_compress() into `cap` bytes (SIZE_MAX: all it may need) and, `dev`, through lzs_compress_stream_device()
+ * from and into "device" memory (heap memory here) of `dev_cap` bytes; both against the oracle as well */
+static void st_one_shot(const char *what, const char *seg, const uint8_t *d, size_t n, size_t cap, int dev, size_t dev_cap)
+{
+    const size_t most = LZS_COMPRESSED_MAX(n) + 1024;
+    uint8_t *want = (uint8_t *)malloc(most), *got = (uint8_t *)malloc(most + 8);
+    const size_t w = lzs_oracle_compress(want, most, d, n);
+    char name[128];
+    if (cap == SIZE_MAX) cap = LZS_COMPRESSED_MAX(n);
+    if (cap == SIZE_MAX - 1) cap = w - 1;
+    if (!dev) {
+        snprintf(name, sizeof name, "%s, segments of %s, into %zu", what, seg ? seg : "the default size", cap);
+        memset(got, 0xA5, most + 8);
+        st_begin(seg);
+        const size_t g = lzs_compress(got, cap, d, n);
+        st_done(name, g, got, most + 8, NULL);
+        CHECK(g == (w < cap ? w : cap) && memcmp(got, want, g) == 0 && got[g] == 0xA5, "%s: %zu bytes, the oracle %zu: %s", name, g, w, lzs_last_error());
+    } else {
+        snprintf(name, sizeof name, "%s, segments of %s, device buffers, into %zu", what, seg ? seg : "the default size", dev_cap);
+        uint8_t *room = (uint8_t *)malloc(dev_cap + 8);
+        size_t g = 0;
+        memset(room, 0xA5, dev_cap + 8);
+        st_begin(seg);
+        const int rc = lzs_compress_stream_device(room, dev_cap, &g, d, n);
+        st_done(name, g, room, dev_cap + 8, NULL);
+        CHECK(rc == 0 && g == w && memcmp(room, want, w) == 0 && room[dev_cap] == 0xA5, "%s: status %d, %zu bytes, the oracle %zu: %s", name, rc, g, w, lzs_last_error());
+        free(room);
+    }
+    free(want); free(got);
+}
+
+/* one direct call of stream_compress_piece() on a hand-made piece: `data` is the prefix and then the input, n bytes in all */
+static void st_piece(const char *name, const uint8_t *data, size_t n, piece_t pc)
+{
+    const size_t cap = LZS_COMPRESSED_MAX(n - pc.c0) + 16;
+    uint8_t *got = (uint8_t *)malloc(cap + 8);
+    int rc = LZS_OK;
+    memset(got, 0xA5, cap + 8);
+    pc.prefix = data;
+    st_begin("256");
+    const size_t g = stream_compress_piece(got, cap, data + pc.prefix_len, n, 0, &rc, &pc);
+    st_done(name, g, got, cap + 8, &pc);
+    CHECK(rc == LZS_OK && g <= cap && pc.c_exit <= n && pc.c_exit >= pc.c0 && got[cap] == 0xA5, "%s: status %d, %zu bytes, ends at %u: %s", name, rc, g, pc.c_exit, lzs_last_error());
+    free(got);
+}
+
+/* B(k, 3): every 3-gram over k symbols once (Lyndon words, as tests/stream_compress_programs.py's de_bruijn) */
+static void st_db(unsigned t, unsigned p, unsigned k, unsigned *a, uint8_t *seq, size_t *len)
+{
+    if (t > 3) { if (3 % p == 0) for (unsigned i = 1; i <= p; i++) seq[(*len)++] = (uint8_t)a[i]; return; }
+    a[t] = a[t - p];
+    st_db(t + 1, p, k, a, seq, len);
+    for (unsigned j = a[t - p] + 1; j < k; j++) { a[t] = j; st_db(t + 1, t, k, a, seq, len); }
+}
+
+static void st_pure_tables(void)
+{
+    /* settle_compress_entries(): segments of 256; segment 1's last token is a match that ends at 1030, and the walks from 512 and
+     * 768 are inside it: after round 0 segments 2, 3 and 4 are entered there (2 and 3 lie behind it: skipped), 5 where 4 left */
+    uint32_t entry[6] = { 0, 256, 512, 768, 1024, 1280 };
+    uint8_t dirty[6] = { 1, 1, 1, 1, 1, 1 };
+    const uint32_t exits0[6] = { 256, 1030, 1030, 1030, 1285, 1536 }, entry1[6] = { 0, 256, 1030, 1030, 1030, 1285 };
+    const uint8_t dirty1[6] = { 0, 0, 1, 1, 1, 1 }, clean[6] = { 0, 0, 0, 0, 0, 0 };
+    uint32_t nd = settle_compress_entries(entry, dirty, exits0, 6);
+    CHECK(nd == 4 && !memcmp(entry, entry1, sizeof entry) && !memcmp(dirty, dirty1, 6), "settle_compress_entries: a long match over two segments: %u to redo", nd);
+    /* round 1: 2 and 3 entered behind their end leave where they were entered, 4 merges with its first walk: all clean */
+    nd = settle_compress_entries(entry, dirty, exits0, 6);
+    CHECK(nd == 0 && !memcmp(entry, entry1, sizeof entry) && !memcmp(dirty, clean, 6), "settle_compress_entries: all clean: %u to redo", nd);
+    dirty[0] = 1; entry[0] = 7;                                     /* segment 0 is entered where the piece says, and never again */
+    nd = settle_compress_entries(entry, dirty, exits0, 1);
+    CHECK(nd == 0 && entry[0] == 7 && dirty[0] == 0, "settle_compress_entries: one segment");
+    /* open_match_take_back(): the match of offset 77 that starts at 1000 -- in segment 3 of 8, empty segments behind it -- reaches
+     * the end of the data at n: 8 bytes, full groups of 15 and a closing nibble of (n - 1008) % 15, which is taken back */
+    for (uint32_t r = 0; r < 15; r++) {
+        const uint32_t n = 1000 + 8 + 15 * (40 + r) + r, open[16] = { 0, 0, 0, 0, 5, 400, 77, 1000, 0, 0, 0, 0, 0, 0, 0, 0 };
+        uint64_t nbits[8] = { 2304, 2000, 1800, 900, 0, 0, 0, 0 };
+        uint32_t c_exit = n, ext_exit = 0;
+        const int took = open_match_take_back(open, nbits, 8, n, 3, &c_exit, &ext_exit);
+        CHECK(took == 1 && c_exit == n - r && ext_exit == 77 && nbits[3] == 896 && nbits[2] == 1800 && nbits[4] == 0, "open_match_take_back: residue %u: %d, ends at %u of %u, offset %u, %llu bits",
+              r, took, c_exit, n, ext_exit, (unsigned long long)nbits[3]);
+    }
+    {
+        const uint32_t none[4] = { 0, 0, 0, 0 }, one[4] = { 0, 0, 9, 300 };
+        uint64_t nbits[2] = { 500, 3 };
+        uint32_t c_exit = 600, ext_exit = 0;
+        CHECK(open_match_take_back(none, nbits, 2, 600, 0, &c_exit, &ext_exit) == -1, "open_match_take_back: no open match reported");
+        CHECK(open_match_take_back(one, nbits, 2, 600, 0, &c_exit, &ext_exit) == -1 && nbits[1] == 3 && c_exit == 600 && ext_exit == 0, "open_match_take_back: fewer than 4 bits");
+        /* not the case at all: the last token ends before the data does; the piece had no token (it began behind its data) */
+        c_exit = 599; nbits[1] = 40;
+        CHECK(open_match_take_back(one, nbits, 2, 600, 0, &c_exit, &ext_exit) == 0 && nbits[1] == 40 && c_exit == 599, "open_match_take_back: a token that ends before n");
+        c_exit = 600;
+        CHECK(open_match_take_back(one, nbits, 2, 600, 600, &c_exit, &ext_exit) == 0 && nbits[1] == 40 && ext_exit == 0, "open_match_take_back: a piece without tokens");
+    }
+}
+
+static void streamtrace(void)
+{
+    setenv("LZS_ROUTE", "device", 1);
+    setenv("LZS_FORCE_STREAM", "1", 1);
+    if (trace_print) printf("static const stream_row_t stream_rows[] = {\n");
+    uint8_t *t = sample(0, 100000, 7), *r = sample(2, 10000, 9);
+    st_one_shot("text of 6145", NULL, t, 6145, SIZE_MAX, 0, 0);
+    for (int k = 0; k < 2; k++) {
+        const char *seg = k ? "512" : "256";
+        st_one_shot("text of 20000", seg, t, 20000, SIZE_MAX, 0, 0);
+        st_one_shot("text of 20000", seg, t, 20000, 0, 1, LZS_COMPRESSED_MAX(20000) + 1024);
+    }
+    /* tests/test_stream_compress_model.py, test_model_on_three_inputs_followed_by_hand (2): segment 0 overflows its slot by four bits */
+    uint8_t big[753];
+    for (unsigned i = 0; i < 753; i++) big[i] = i < 255 ? (uint8_t)i : i < 733 ? 254 : (uint8_t)(100 - (i - 733));
+    st_one_shot("an oversized segment", "256", big, sizeof big, SIZE_MAX, 0, 0);
+    /* ... and (3): B(16, 3) twice, walks that never merge -- fourteen rounds */
+    uint8_t *db = (uint8_t *)malloc(8192);
+    unsigned a[8] = { 0 };
+    size_t ndb = 0;
+    st_db(1, 1, 16, a, db, &ndb);
+    CHECK(ndb == 4096, "B(16, 3) has %zu bytes", ndb);
+    memcpy(db + 4096, db, 4096);
+    st_one_shot("walks that never merge", "256", db, 8192, SIZE_MAX, 0, 0);
+    /* one_shot_streams' mix, at a third of its size: a run and a period of 2 over many segments */
+    const size_t n_mix = 15000 + 25000 + 15000 + 25000 + 10000 + 5;
+    uint8_t *mix = (uint8_t *)calloc(n_mix, 1);
+    memcpy(mix, t, 15000); memcpy(mix + 40000, t + 15000, 15000);
+    for (size_t i = 0; i < 25000; i++) mix[55000 + i] = "ab"[i & 1];
+    memcpy(mix + 80000, r, 10000);
+    st_one_shot("a run and a period of 2", NULL, mix, n_mix, SIZE_MAX, 0, 0);
+    /* cut capacities: none, one byte, one byte less than the stream; a device buffer shorter than it was promised */
+    st_one_shot("text of 20000", "256", t, 20000, 0, 0, 0);
+    st_one_shot("text of 20000", "256", t, 20000, 1, 0, 0);
+    st_one_shot("text of 20000", "256", t, 20000, SIZE_MAX - 1, 0, 0);
+    st_one_shot("text of 20000", "256", t, 20000, 0, 1, LZS_COMPRESSED_MAX(20000) + 100);
+
+    /* pieces, as lzs_compress_incremental() hands them over.  Text with planted copies at offset 7: [4000, 4700) and [9000, 9400) */
+    uint8_t *p = (uint8_t *)malloc(12000);
+    memcpy(p, t + 30000, 12000);
+    for (unsigned i = 4000; i < 4700; i++) p[i] = p[i - 7];
+    p[4700] = (uint8_t)(p[4693] ^ 0x55);
+    for (unsigned i = 9000; i < 9400; i++) p[i] = p[i - 7];
+    p[9400] = (uint8_t)(p[9393] ^ 0x55);
+    st_piece("piece: bit0 = 3 behind a first byte, a prefix", p, 9000, (piece_t){ .prefix_len = 3000, .c0 = 2990, .bit0 = 3, .first = 0xA0 });
+    st_piece("piece: resumes a match that ends inside it", p, 9000, (piece_t){ .prefix_len = 2304, .c0 = 4200, .ext_off = 7, .bit0 = 5, .first = 0xB8 });
+    st_piece("piece: resumes a match that covers all its data", p, 4700, (piece_t){ .prefix_len = 2304, .c0 = 4200, .ext_off = 7, .bit0 = 5, .first = 0xB8 });
+    st_piece("piece: the last token reaches the end of the data", p, 9400, (piece_t){ .prefix_len = 5000, .c0 = 4990, .bit0 = 1, .first = 0x80 });
+    st_piece("piece: stop below n", p, 9000, (piece_t){ .prefix_len = 5000, .c0 = 4990, .stop = 7000 });
+    st_piece("piece: last, with an empty tail", p, 3000, (piece_t){ .prefix_len = 3000, .c0 = 3000, .bit0 = 6, .first = 0xFC, .last = 1 });
+    if (!trace_print) {
+        st_pure_tables();
+        /* a full device: both directions report LZS_E_NOMEM before any launch, and the thread's next call works */
+        const size_t n = (size_t)2 << 20, most = LZS_COMPRESSED_MAX(n) + 1024;
+        uint8_t *x = sample(1, n, 30), *room = (uint8_t *)malloc(most);
+        size_t g = 1;
+        setenv("LZS_STAGING_FAIL_MB", "1", 1);
+        st_begin(NULL);
+        const uint64_t no_launch = lzs_shim_launch_hash(0);
+        const unsigned scans = lzs_shim_scan_launches();
+        int rc = lzs_compress_stream_device(room, most, &g, x, n);
+        CHECK(rc == LZS_E_NOMEM && g == 0 && lzs_shim_launch_hash(0) == no_launch, "a full device: lzs_compress_stream_device gives %d (%s)", rc, lzs_last_error());
+        g = 1;
+        rc = lzs_decompress_stream_device(room, most, &g, x, n);
+        CHECK(rc == LZS_E_NOMEM && g == 0 && lzs_shim_scan_launches() == scans, "a full device: lzs_decompress_stream_device gives %d (%s)", rc, lzs_last_error());
+        unsetenv("LZS_STAGING_FAIL_MB");
+        rc = lzs_compress_stream_device(room, most, &g, t, 20000);
+        uint8_t *want = (uint8_t *)malloc(most);
+        const size_t w = lzs_oracle_compress(want, most, t, 20000);
+        CHECK(rc == 0 && g == w && memcmp(room, want, w) == 0, "the call after a full device: status %d, %zu bytes (%zu)", rc, g, w);
+        free(x); free(room); free(want);
+    }
+    if (trace_print) printf("};\n");
+    free(t); free(r); free(db); free(mix); free(p);
+    unsetenv("LZS_ROUTE"); unsetenv("LZS_FORCE_STREAM"); unsetenv("LZS_STREAM_SEG");
+}
+
 /* ---------------------------------------------------------------- what a thread keeps, and giving it back
  * The reference keeps nothing after return (lzs.h:218,229); this build keeps a thread's staging for its next call -- at most
  * LZS_KEEP_MAX_MB in sum -- until the thread exits or calls lzs_release_thread_cache(). */
@@ -914,6 +1149,9 @@ int main(int argc, char **argv)
     if (!*only || !strcmp(only, "incremental")) incremental();
     trace_print = !strcmp(only, "inctrace-rows");
     if (!*only || !strcmp(only, "inctrace") || trace_print) inctrace();
+    trace_print = !strcmp(only, "streamtrace-rows");
+    if (!*only || !strcmp(only, "streamtrace") || trace_print) streamtrace();
+    trace_print = 0;
     if (!*only || !strcmp(only, "streamdec")) streamdec();
     if (!*only || !strcmp(only, "pipeline")) pipeline();
     if (!*only || !strcmp(only, "release")) release_cache();

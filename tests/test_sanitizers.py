@@ -43,7 +43,7 @@ def _run(exe, cases, env_extra, timeout):
 def test_host_sources_under_address_and_undefined_behaviour_sanitizers(built):
     # ("release": what a thread keeps between calls goes back on lzs_release_thread_cache(), on thread exit, and above
     # LZS_KEEP_MAX_MB -- the shim counts its outstanding "device" bytes; leak detection is on)
-    _run(os.path.join(built, "san_asan"), ["routes", "ragged", "layouts", "streams", "incremental", "inctrace", "streamdec", "pipeline", "release"],
+    _run(os.path.join(built, "san_asan"), ["routes", "ragged", "layouts", "streams", "incremental", "inctrace", "streamtrace", "streamdec", "pipeline", "release"],
          {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"}, 900)
 
 

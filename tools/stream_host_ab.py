@@ -6,7 +6,9 @@ interface, this build against another build of liblzs.so.
 
 Shapes (text): dec-1m / dec-64m  lzs_decompress of a stream that decodes to 1 / 64 MiB, host buffers;
                dev-1g            lzs_decompress_stream_device of 1 GiB;
-               batch-256         lzs_decompress_batch of 256 blocks of 64 KiB, host buffers (goes by segments);
+               comp-1m / comp-64m  lzs_compress of 1 / 64 MiB, host buffers (one stream in segments);
+               cdev-1g           lzs_compress_stream_device of 1 GiB;
+               batch-256        lzs_decompress_batch of 256 blocks of 64 KiB, host buffers (goes by segments);
                cbatch-2597 / dbatch-2597  lzs_compress_batch / lzs_decompress_batch of 2597 blocks of 64 KiB, host buffers
                                  (the overlapped route, lzs_pipeline.c);
                cbatch-64         lzs_compress_batch of 64 blocks of 64 KiB, host buffers (one after the other);
@@ -31,6 +33,7 @@ import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 SHAPES = {"dec-1m": 16, "dec-64m": 1024, "dev-1g": 16384, "batch-256": 256,          # 64 KiB blocks of text
+          "comp-1m": 16, "comp-64m": 1024, "cdev-1g": 16384,
           "cbatch-2597": 2597, "dbatch-2597": 2597, "cbatch-64": 64,
           "inc-c-512": 64, "inc-d-512": 64, "inc-c-1m": 1024, "inc-d-256k": 384, "inc-d-4m": 640}
 INC_PIECE = {"inc-c-512": 512, "inc-d-512": 512, "inc-c-1m": 1 << 20, "inc-d-256k": 256 << 10, "inc-d-4m": 4 << 20}
@@ -98,6 +101,24 @@ def worker(shape):
                         assert not (p.status & api.STATUS_ERROR)
                 got[0] = out
             check = lambda: got[0] == len(plain) and dst.raw[:len(plain)] == plain
+    elif shape.startswith("comp-"):
+        plain = x.reshape(-1)
+        want = np.frombuffer(lzs.compress(plain.tobytes()), dtype=np.uint8)
+        out, got = np.zeros(lzs.compressed_max(plain.size), dtype=np.uint8), [0]
+
+        def call():
+            got[0] = L.lzs_compress(out.ctypes.data, out.size, plain.ctypes.data, plain.size)
+        check = lambda: got[0] == want.size and np.array_equal(out[:got[0]], want)
+    elif shape == "cdev-1g":
+        import torch
+        plain = torch.from_numpy(x.reshape(-1)).cuda()
+        want, want_len = lzs.compress_stream(plain)
+        out, got = torch.empty_like(want), ctypes.c_size_t(0)
+        torch.cuda.synchronize()
+
+        def call():
+            assert L.lzs_compress_stream_device(out.data_ptr(), out.numel(), ctypes.byref(got), plain.data_ptr(), plain.numel()) == 0
+        check = lambda: got.value == want_len and bool(torch.equal(out[:got.value], want[:want_len]))
     elif shape == "dev-1g":
         import torch
         plain = torch.from_numpy(x.reshape(-1)).cuda()
