@@ -143,6 +143,20 @@ constexpr int kSubsteps = LZS_SUBSTEPS;
 #define LZS_HOPS_HERE LZS_HOPS
 #endif
 constexpr int kHops = LZS_HOPS_HERE;
+//   LZS_WGV_HOP_END                 the block and packed entries' SEARCH lets a hop pass over the LAST candidate inside the window too
+//                                   (wg_search<true>: the rule and why it is exact stand at the hop), and runs LZS_WGV_HOPS_LAST hops
+//                                   (default: as many as the others) in front of the last full step of a pass.  The default variant
+//                                   alone: 2 + 3 hops, +2 % on text (profiles/r07/README.md).  The segments entry keeps the plain rule
+#ifdef LZS_WGV_HOP_END
+constexpr bool kHopEnd = true;
+#else
+constexpr bool kHopEnd = false;
+#endif
+#ifdef LZS_WGV_HOPS_LAST
+constexpr int kHopsLast = LZS_WGV_HOPS_LAST;
+#else
+constexpr int kHopsLast = kHops;
+#endif
 constexpr uint32_t kExtMax     = 59;              // longest extension resolved in SEARCH
 constexpr uint32_t kOpenStep   = 4080;            // bytes of an open match per step: 255 threads x 16 = 272 nibbles of 15
 #ifndef LZS_RUN_ROUNDS
@@ -559,6 +573,7 @@ struct Walk {
     // yet" (only a length >= 3 beats it), 0x1000 = "2-byte chain, nothing yet".
     int32_t key;
     uint32_t cap;                // length that ends the walk: min(remaining, 12), or 2 on the 2-byte chain; 0 while the lane is idle
+                                 // (wg_search<true>, LZS_WGV_HOP_END: stale while idle, and masked by the step -- see there)
     uint32_t nfirst2;            // MINUS the distance where the 2-byte chain starts (-kNoLink: nowhere)
     const uint16_t *links;       // link array being followed
     uint16_t *resp;              // where the result goes once the walk has ended; the dummy word when there is none to store
@@ -574,6 +589,7 @@ constexpr int32_t kKeyNone3 = 0x2000, kKeyNone2 = 0x1000;
 // The longest walk of a pool (about 30 steps in text, against 5.5 on average) then no longer
 // holds up 255 other lanes at the end of every pool.  Results are stored as raw keys; EXTEND
 // turns them into off | len << 11 | ext << 15.
+template <bool HE>
 __device__ __forceinline__ void wg_search(BlkLds &L, Walk &W, uint32_t Pb, uint32_t pend, uint32_t n, uint32_t lane, bool lit, bool drain SEARCH_PROF_PARAMS)
 {
     const uint32_t slot0 = wg_slot_base(Pb);
@@ -687,13 +703,32 @@ __device__ __forceinline__ void wg_search(BlkLds &L, Walk &W, uint32_t Pb, uint3
             // equal mine.  Up to LZS_HOPS candidates that fail this one-byte test are passed over
             // here (a link read and a byte read each, a quarter of a full step) -- but never the
             // last one inside the window: the full step below ends the walk on it.
+            // HE (LZS_WGV_HOP_END, round 7): the last one inside the window is passed over as well.  Exact for the same
+            // reason: a candidate whose byte at offset best-length differs cannot be strictly longer than the best, wherever
+            // it stands in the window, and the nearest-first order of the others is untouched.  With no candidate left the
+            // lane goes to its own position (nback = 0, the idle marker) with its cap still set, and the hop holds no end
+            // logic: the full step below masks the cap of a lane that stands on its own position to 0, so that it compares
+            // nothing, beats no key and satisfies len == cap -- the end logic there runs as it always did, store-on-next-take
+            // and the restart on the 2-byte chain included.  What this relies on: hops are ALWAYS followed by a full step
+            // before the loop looks at idle lanes again (the refill pass and the test for leaving stand at the top of a
+            // pass); a lane taken between a hop and its step would lose the restart.  A later hop of the same sub-step
+            // finds the lane's own byte equal to the probe and leaves it where it is.
+            // The two predicates are consumed by a select each instead of an AND of lane masks (see above struct Walk): with
+            // the step's cap held by a v_min_u16 instead of a select that alone is 1.5 % on text, for four vector
+            // instructions a pass more (profiles/r07/ab_search_shape.txt).
+            const int nhops = (HE && sub == kSubsteps - 1) ? kHopsLast : kHops;
 #pragma unroll
-            for (int hop = 0; hop < kHops; hop++) {
+            for (int hop = 0; hop < nhops; hop++) {
                 const uint32_t cb = ring8[(pb + nback) & vRM];
                 const uint32_t ax = myslot + nback;
                 const uint32_t nnx = nback - links[wg_link_slot(ax)];
-                const bool skip = cb != probe && nnx > nreach;
-                nback = skip ? nnx : nback;
+                if constexpr (HE) {
+                    const uint32_t nto = nnx > nreach ? nnx : 0u;
+                    nback = cb != probe ? nto : nback;
+                } else {
+                    const bool skip = cb != probe && nnx > nreach;
+                    nback = skip ? nnx : nback;
+                }
             }
 #endif
             // One step = one candidate, for all 64 lanes alike.
@@ -710,12 +745,16 @@ __device__ __forceinline__ void wg_search(BlkLds &L, Walk &W, uint32_t Pb, uint3
             const uint32_t nd = links[wg_link_slot(at)];
             uint32_t len = lcp12(w0 ^ t0, w1 ^ t1, w2 ^ t2);
             // ("all equal" is 0x1FFFFFFF: 0xFFFF in 16 bits, still more than any cap)
-            asm("v_min_u16 %0, %1, %2" : "=v"(len) : "v"(len), "v"(cap));
+            // (HE: a lane on its own position compares with a cap of 0 whatever its cap is -- nback is 0 or minus a distance of
+            // 1 .. 2047: in 16 bits 0, or more than any cap)
+            uint32_t capm = cap;
+            if constexpr (HE) asm("v_min_u16 %0, %1, %2" : "=v"(capm) : "v"(cap), "v"(nback));
+            asm("v_min_u16 %0, %1, %2" : "=v"(len) : "v"(len), "v"(capm));
             const int32_t cand = (int32_t)((len << 12) + nback);
             key = key > cand ? key : cand;
             // the walk ends at the cap, or on the last candidate inside the window (:337-345)
             const uint32_t nnext = nback - nd;
-            const int32_t kend = opaque((len == cap || !(nnext > nreach)) ? key : 0);
+            const int32_t kend = opaque((len == capm || !(nnext > nreach)) ? key : 0);
             // nothing on the 3-byte chain: restart on the 2-byte chain, if there is one in the window
             const bool fallback = !kNo3 && kend == kKeyNone3 && nfirst2 > nreach;
             const int32_t kfin = opaque(fallback ? 0 : kend);
@@ -723,8 +762,19 @@ __device__ __forceinline__ void wg_search(BlkLds &L, Walk &W, uint32_t Pb, uint3
             cap = fallback ? 2u : cap;
             links = fallback ? L.link2 : links;
             const uint32_t nwalk = fallback ? nfirst2 : nnext;
-            cap = kfin != 0 ? 0u : cap;                        // ended for good: the lane is idle -- what it compares with itself from now on is
-                                                               // no match (its key waits to be stored) ...
+            // (HE: the cap of a lane whose walk has ended is NOT cleared -- the step masks the cap of every lane that stands on
+            // its own position itself, capm above, so such a lane compares nothing and beats no key while it stays there, and
+            // struct Walk's "cap: 0 while the lane is idle" holds for the plain rule only.  Inside one call of wg_search the ring
+            // does not change and every step re-reads the probe, so a hop finds an idle lane's own byte equal to its probe and
+            // leaves it.  ACROSS calls the ring is refilled: an idle lane carried into the next pool may find another byte under
+            // its stale probe, be moved by a hop along stale links and compare with its stale cap, where the plain rule's idle
+            // lane wanders the same way with a cap of 0 and ends at once.  That is harmless for one reason only: the key of a
+            // walk that has ended is stored on the way out of the call it ended in, and resp is the dummy word from then on
+            // until the lane's next take, which resets all of its state; the wandering lane ends on the window like any walk.)
+            if constexpr (!HE) {
+                cap = kfin != 0 ? 0u : cap;                    // ended for good: the lane is idle -- what it compares with itself from now
+                                                               // on is no match (its key waits to be stored) ...
+            }
             nback = kfin != 0 ? 0u : nwalk;                    // ... and it stands on its own position
 #if LZS_HOPS_HERE
             pb = p + (((uint32_t)key + vFFF) >> 12);
@@ -804,7 +854,8 @@ __device__ __forceinline__ u32x4 wg_view_read16(const WgJob &job, uint32_t q)
 
 // (ENTRY changes nothing in the code: the packed entries below take instance 1, so that every strided entry stays the only caller
 // of the instance it had -- as a second caller of that one they moved the strided kernels' instructions; DESIGN.md 3.15)
-template <int ENTRY = 0>
+// (HE: SEARCH with LZS_WGV_HOP_END's rule -- the block and packed entries of a variant that asks for it; the segments entry does not)
+template <int ENTRY = 0, bool HE = false>
 __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgOut o)
 {
     const uint32_t tid  = threadIdx.x;
@@ -932,7 +983,7 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
 #ifdef LZS_WGV_PRIO          // SEARCH is where the time goes and every wave has work in it; the short phases between barriers, where
         __builtin_amdgcn_s_setprio(0);   // some waves of the workgroup wait for others, go first on their SIMD (+0.9 % on text, ab_s13)
 #endif
-        wg_search(L, W, Sb, send, n, lane, lit_mode, run_mode && fresh SEARCH_PROF_ARGS);
+        wg_search<HE>(L, W, Sb, send, n, lane, lit_mode, run_mode && fresh SEARCH_PROF_ARGS);
 #ifdef LZS_WGV_PRIO
         __builtin_amdgcn_s_setprio(2);
 #endif
@@ -1402,7 +1453,7 @@ void lzs_compress_blocks_wg_kernel(uint8_t *__restrict__ out, size_t out_stride,
     o.cap = out_cap;
     o.aligned4 = ((uintptr_t)o.dst & 3u) == 0;
     o.limit = out_cap; o.ored = false;
-    wg_compress_job(L, job, o);
+    wg_compress_job<0, kHopEnd>(L, job, o);
 }
 
 // The same from PACKED blocks to rooms (include/lzs/lzs_batch.h "PACKED streams"; DESIGN.md 3.15): block b lies at in + in_off[b] and
@@ -1445,7 +1496,7 @@ void lzs_compress_packed_wg_kernel(uint8_t *__restrict__ out, const uint64_t *__
     o.cap = room;
     o.aligned4 = ((uintptr_t)o.dst & 3u) == 0;
     o.limit = room; o.ored = false;
-    wg_compress_job<1>(L, job, o);
+    wg_compress_job<1, kHopEnd>(L, job, o);
 }
 #endif  // !LZS_WGV_CHANNELS
 
@@ -1641,6 +1692,8 @@ void lzs_compress_channels_packed_wg_kernel(uint8_t *__restrict__ out, const uin
 #undef LZS_WGV_HEAD2
 #undef LZS_WGV_SUBSTEPS
 #undef LZS_WGV_HOPS
+#undef LZS_WGV_HOP_END
+#undef LZS_WGV_HOPS_LAST
 #undef LZS_HOPS_HERE
 #undef LZS_WGV_CHAIN_SAFE
 #undef LZS_WGV_SEGMENTS

@@ -55,6 +55,8 @@ namespace {
 // order-independent CHAIN for a device that fails the LDS ordering check, and the two a block's class may ask for.
 namespace wgv_text {
 #define LZS_WGV_SEGMENTS 1
+#define LZS_WGV_HOP_END 1        // (round 7: hops may end a walk, 2 + 3 hops a pass -- the block and packed entries; profiles/r07/README.md)
+#define LZS_WGV_HOPS_LAST 3
 #include "kernels/wgv_text_shape.inc"
 #include "kernels/compress_wg.inc"
 }
