@@ -59,6 +59,9 @@ int lzs_hip_chain_mode(void *stream, int *mode);
  * 2 read (a failure switches the device to the order-independent chain build, loudly).  LZS_VERIFY=N in the
  * environment: every N-th compress launch is re-run in the order-independent form and compared on the device. */
 int lzs_hip_load_check_state(int dev);
+/* What LZS_VARIANT (development, read once per process) forces on every block of a compress launch: 0 nothing -- the blocks'
+ * classes decide --, 1 the default (text) variant, 2 few distinct grams, 3 nearly all literals.  For tests: proof of what ran. */
+int lzs_hip_forced_variant(void);
 int lzs_hip_launch_compress(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                             const void *d_in, size_t in_stride, const uint32_t *d_in_len,
                             uint32_t in_len, uint32_t nblocks, void *stream);

@@ -383,6 +383,8 @@ static int forced_variant(void)
     }();
     return forced;
 }
+// (for tests: what LZS_VARIANT forces in this process -- 0 none, 1 text, 2 few, 3 lit)
+int lzs_hip_forced_variant(void) { return forced_variant(); }
 
 // The variants recent launches had blocks for (all three while nothing is known) as `allow`, bit c for class c; a block of another class
 // goes to `catch_all`: the default variant if that runs, else the first that does.  h_seen: where this launch's classifier leaves what

@@ -112,6 +112,7 @@ int lzs_hip_memset(void *d, int v, size_t n, void *st) { (void)st; called(7, n);
 int lzs_hip_words_to_host(uint32_t *h, const uint32_t *d, size_t nwords, void *st) { (void)st; if (nwords) memcpy(h, d, 4 * nwords); return launched(); }
 int lzs_hip_chain_mode(void *stream, int *mode) { (void)stream; *mode = 0; return 0; }
 int lzs_hip_load_check_state(int dev) { (void)dev; return 0; }
+int lzs_hip_forced_variant(void) { return 0; }
 unsigned lzs_hip_dec_segment_bytes(void) { return 8192; }
 
 /* ---- block launches: block b is the one-shot call on block b (the kernels' contract) */
