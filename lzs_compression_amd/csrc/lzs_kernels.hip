@@ -43,6 +43,7 @@
 #include <stdlib.h>
 
 #include "lzs_hip_shim.h"
+#include "lzs_launch_plan.h"       // which kernels a launcher runs: plain functions, held to a table on the CPU (tests/cpu_shim/plan_check.c)
 
 namespace {
 
@@ -386,98 +387,145 @@ static int forced_variant(void)
 // (for tests: what LZS_VARIANT forces in this process -- 0 none, 1 text, 2 few, 3 lit)
 int lzs_hip_forced_variant(void) { return forced_variant(); }
 
-// The variants recent launches had blocks for (all three while nothing is known) as `allow`, bit c for class c; a block of another class
-// goes to `catch_all`: the default variant if that runs, else the first that does.  h_seen: where this launch's classifier leaves what
-// it met, under `id`.
-static void variant_hint(void *stream, uint32_t &allow, uint32_t &catch_all, uint32_t *&h_seen, uint32_t &id)
+static_assert(kClassifyMinBlocks == 64u && (kClassCode & 0xFu) == 0u, "lzs_launch_plan.h and tests/cpu_shim/plan_check.c are written for these");
+
+// What lzs_plan_variants() decides from: the ids the last classifiers left per class, and whether the stream is being captured into
+// a graph (the guess would be frozen with it: every variant is launched, so that a replay on another class of data keeps its
+// variant -- ADVICE r05).  h_seen: where this launch's classifier leaves what it met, under `id`.
+static lzs_plan_variants_t variant_hint(void *stream, uint32_t *&h_seen, uint32_t &id)
 {
-    int dev = 0;
-    allow = 0xEu; catch_all = 1u; h_seen = nullptr;
+    int dev = 0, capturing = 0;
+    uint32_t seen[4] = { 0, 0, 0, 0 };
+    h_seen = nullptr;
     id = (uint32_t)__atomic_add_fetch(&g_hint_launch, 1u, __ATOMIC_RELAXED) | 0x80000000u;      // (never 0)
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && (h_seen = __atomic_load_n(&g_hint_seen[dev], __ATOMIC_ACQUIRE)) != nullptr) {
-        uint32_t s[4], newest = 0;
-        for (int c = 1; c <= 3; c++) { s[c] = __atomic_load_n(&h_seen[c], __ATOMIC_RELAXED); if (s[c] && (newest == 0 || (int32_t)(s[c] - newest) > 0)) newest = s[c]; }
-        // (while the stream is being captured into a graph the guess would be frozen with it: every variant is launched, so that
-        // a replay on another class of data keeps its variant -- ADVICE r05)
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-        if (stream && hipStreamIsCapturing((hipStream_t)stream, &capturing) != hipSuccess) { capturing = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-        if (newest && capturing == hipStreamCaptureStatusNone) {
-            allow = 0;
-            for (int c = 1; c <= 3; c++) if (s[c] && newest - s[c] <= 2u) allow |= 1u << c;       // (seen by one of the last three classifiers)
-            catch_all = (allow & 2u) ? 1u : ((allow & 4u) ? 2u : 3u);
-        }
+        for (int c = 1; c <= 3; c++) seen[c] = __atomic_load_n(&h_seen[c], __ATOMIC_RELAXED);
+        hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+        if (stream && hipStreamIsCapturing((hipStream_t)stream, &status) != hipSuccess) { status = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+        capturing = status != hipStreamCaptureStatusNone;
     }
+    return lzs_plan_variants(seen, h_seen != nullptr, capturing);
 }
+
+// A variant's namespace as a type, for the launchers' entry functors: its block entry, its packed entry, its workgroup.
+#define LZS_VARIANT_TAG(ns) \
+    struct ns##_tag { static constexpr auto blocks = ns::lzs_compress_blocks_wg_kernel; static constexpr auto packed = ns::lzs_compress_packed_wg_kernel; \
+                      static constexpr unsigned threads = ns::kWgThreads; }
+LZS_VARIANT_TAG(wgv_safe);
+LZS_VARIANT_TAG(wgv_text);
+#ifndef LZS_ONE_VARIANT
+LZS_VARIANT_TAG(wgv_few);
+LZS_VARIANT_TAG(wgv_lit);
+#endif
+#undef LZS_VARIANT_TAG
+
+// Which variant compresses a block, for the strided and the packed call alike (lzs_plan_compress): the order-independent CHAIN for
+// all of them on a device that needs it; otherwise the block's class decides, on the device (the classifier leaves a code in
+// out_len[b]; every allowed variant is launched over the whole grid and a workgroup whose block is another's returns at once: ~10 us
+// per empty grid of 16 384).  LZS_VARIANT=text|few|lit (development, read once) gives every block that one; small launches take the
+// default alone.
+//   earlier(&e)        true: the call was served by another kernel (LZS_KERNEL= of the A/B builds), e its result
+//   variant(tag, serve)  launches that variant's entry over the whole grid
+//   classify(v, h_seen, id)  launches the entry's classifier
+// *ordered: the ordered-exchange form was launched (what LZS_VERIFY samples).
+extern "C++" {
+template <class Earlier, class Variant, class Classify>
+static int compress_dispatch(uint32_t nblocks, void *stream, bool *ordered, const Earlier &earlier, const Variant &variant, const Classify &classify)
+{
+    *ordered = false;
+    if (nblocks == 0) return 0;
+    int chain_mode = 0;
+    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
+    { int e = 0; if (earlier(&e)) return e; }
+#ifdef LZS_ONE_VARIANT
+    const lzs_plan_compress_t plan = lzs_plan_compress(chain_mode, 0, nblocks, kClassifyMinBlocks, 1);
+#else
+    const lzs_plan_compress_t plan = lzs_plan_compress(chain_mode, forced_variant(), nblocks, kClassifyMinBlocks, 0);
+#endif
+    switch (plan.run) {
+    case LZS_RUN_SAFE: variant(wgv_safe_tag{}, 0u); break;
+#ifndef LZS_ONE_VARIANT
+    case LZS_RUN_FEW: variant(wgv_few_tag{}, 0u); break;
+    case LZS_RUN_LIT: variant(wgv_lit_tag{}, 0u); break;
+    case LZS_RUN_CLASSIFY: {
+        uint32_t *h_seen, id;
+        const lzs_plan_variants_t v = variant_hint(stream, h_seen, id);
+        classify(v, h_seen, id);
+        if (v.allow & 2u) variant(wgv_text_tag{}, kClassCode | 1u);
+        if (v.allow & 4u) variant(wgv_few_tag{}, kClassCode | 2u);
+        if (v.allow & 8u) variant(wgv_lit_tag{}, kClassCode | 3u);
+        break;
+    }
+#endif
+    default: variant(wgv_text_tag{}, 0u); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (plan.load_check) {
+        int dev = 0;
+        if (hipGetDevice(&dev) == hipSuccess) load_check_step(dev, plan.load_check_start != 0);     // (beside a launch that fills the device)
+        *ordered = true;
+    }
+    return 0;
+}
+}  // extern "C++"
+
+#ifdef LZS_WITH_VARIANTS
+// A/B builds only: LZS_KERNEL=chain (one wave per block) | scan (brute force) select the earlier kernels, wg8 | p256 the default
+// kernel in its two other shapes (round 6).  True: one of them served the call.
+static bool launch_earlier_kernel(int *result, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                                  const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len, uint32_t nblocks, hipStream_t stream)
+{
+    static const int variant = [] {
+        const char *v = getenv("LZS_KERNEL");
+        return !v ? 0 : (v[0] == 's' ? 2 : (v[0] == 'c' ? 1 : (v[0] == 'w' ? 3 : (v[0] == 'p' ? 4 : 0))));
+    }();
+    const uint32_t grid = (nblocks + kWavesPerWG - 1) / kWavesPerWG;
+    if (variant == 3)
+        hipLaunchKernelGGL(wgv_text8::lzs_compress_blocks_wg_kernel, dim3(nblocks), dim3(wgv_text8::kWgThreads), 0, stream, (uint8_t *)d_out,
+                           out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, 0u);
+    else if (variant == 4)
+        hipLaunchKernelGGL(wgv_pool256::lzs_compress_blocks_wg_kernel, dim3(nblocks), dim3(wgv_pool256::kWgThreads), 0, stream, (uint8_t *)d_out,
+                           out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, 0u);
+    else if (variant == 2)
+        hipLaunchKernelGGL(lzs_compress_blocks_scan_kernel, dim3(grid), dim3(kWavesPerWG * 64), 0, stream, (uint8_t *)d_out, out_stride, out_cap,
+                           d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks);
+    else if (variant == 1)
+        hipLaunchKernelGGL(lzs_compress_blocks_kernel, dim3(nblocks), dim3(64), 0, stream, (uint8_t *)d_out, out_stride, out_cap,
+                           d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks);
+    else
+        return false;
+    *result = (int)hipGetLastError();
+    return true;
+}
+#endif
 
 int lzs_hip_launch_compress(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                             const void *d_in, size_t in_stride, const uint32_t *d_in_len,
                             uint32_t in_len, uint32_t nblocks, void *stream)
 {
-    if (nblocks == 0) return 0;
-    int chain_mode = 0;
-    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
+    bool ordered = false;
+    const int e = compress_dispatch(nblocks, stream, &ordered,
+        [&](int *result) {
 #ifdef LZS_WITH_VARIANTS
-    const uint32_t grid = (nblocks + kWavesPerWG - 1) / kWavesPerWG;
-    // A/B builds only: LZS_KERNEL=chain (one wave per block) | scan (brute force) select the earlier kernels
-    static const int variant = [] {
-        const char *v = getenv("LZS_KERNEL");
-        return !v ? 0 : (v[0] == 's' ? 2 : (v[0] == 'c' ? 1 : (v[0] == 'w' ? 3 : (v[0] == 'p' ? 4 : 0))));
-    }();
-    if (variant == 3 || variant == 4) {        // the default kernel in its two other shapes (round 6)
-        if (variant == 3)
-            hipLaunchKernelGGL(wgv_text8::lzs_compress_blocks_wg_kernel, dim3(nblocks), dim3(wgv_text8::kWgThreads), 0, (hipStream_t)stream, (uint8_t *)d_out,
-                               out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, 0u);
-        else
-            hipLaunchKernelGGL(wgv_pool256::lzs_compress_blocks_wg_kernel, dim3(nblocks), dim3(wgv_pool256::kWgThreads), 0, (hipStream_t)stream, (uint8_t *)d_out,
-                               out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, 0u);
-        return (int)hipGetLastError();
-    }
-    if (variant == 2) {
-        hipLaunchKernelGGL(lzs_compress_blocks_scan_kernel, dim3(grid), dim3(kWavesPerWG * 64), 0,
-                           (hipStream_t)stream, (uint8_t *)d_out, out_stride, out_cap, d_out_len,
-                           (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks);
-        return (int)hipGetLastError();
-    }
-    if (variant == 1) {
-        hipLaunchKernelGGL(lzs_compress_blocks_kernel, dim3(nblocks), dim3(64), 0,
-                           (hipStream_t)stream, (uint8_t *)d_out, out_stride, out_cap, d_out_len,
-                           (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks);
-        return (int)hipGetLastError();
-    }
+            return launch_earlier_kernel(result, d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len, nblocks, (hipStream_t)stream);
+#else
+            (void)result;
+            return false;
 #endif
-    // Which variant compresses a block: the order-independent CHAIN for all of them on a device that needs it; otherwise the
-    // block's class decides, on the device (lzs_classify_blocks_kernel leaves a code in out_len[b]; every variant is launched
-    // over the whole grid and a workgroup whose block is another's returns at once: ~10 us per empty grid of 16 384).
-    // LZS_VARIANT=text|few|lit (development, read once) gives every block that one; small launches take the default alone.
-    const int forced = forced_variant();
-#define LZS_LAUNCH_VARIANT(ns, serve) \
-    hipLaunchKernelGGL(ns::lzs_compress_blocks_wg_kernel, dim3(nblocks), dim3(ns::kWgThreads), 0, (hipStream_t)stream, (uint8_t *)d_out, out_stride, \
-                       out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, serve)
-    if (chain_mode != 0) LZS_LAUNCH_VARIANT(wgv_safe, 0u);
-#ifndef LZS_ONE_VARIANT
-    else if (forced == 2) LZS_LAUNCH_VARIANT(wgv_few, 0u);
-    else if (forced == 3) LZS_LAUNCH_VARIANT(wgv_lit, 0u);
-    else if (forced == 0 && nblocks >= kClassifyMinBlocks) {
-        uint32_t allow, catch_all, *h_seen, id;
-        variant_hint(stream, allow, catch_all, h_seen, id);
-        hipLaunchKernelGGL(lzs_classify_blocks_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_out_len,
-                           (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, allow, catch_all, h_seen, id);
-        if (allow & 2u) LZS_LAUNCH_VARIANT(wgv_text, kClassCode | 1u);
-        if (allow & 4u) LZS_LAUNCH_VARIANT(wgv_few, kClassCode | 2u);
-        if (allow & 8u) LZS_LAUNCH_VARIANT(wgv_lit, kClassCode | 3u);
-    }
-#endif
-    else LZS_LAUNCH_VARIANT(wgv_text, 0u);
-#undef LZS_LAUNCH_VARIANT
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (chain_mode == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) load_check_step(dev, nblocks >= 256u);     // (beside a launch that fills the device)
-        const int every = verify_every();
-        if (every && (__atomic_add_fetch(&g_launch_count, 1u, __ATOMIC_RELAXED) % (unsigned)every) == 0u)
-            return verify_launch(d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len, nblocks, (hipStream_t)stream);
-    }
+        },
+        [&](auto v, uint32_t serve) {
+            hipLaunchKernelGGL(decltype(v)::blocks, dim3(nblocks), dim3(decltype(v)::threads), 0, (hipStream_t)stream, (uint8_t *)d_out, out_stride,
+                               out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, serve);
+        },
+        [&](const lzs_plan_variants_t &v, uint32_t *h_seen, uint32_t id) {
+            hipLaunchKernelGGL(lzs_classify_blocks_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_out_len,
+                               (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, v.allow, v.catch_all, h_seen, id);
+        });
+    if (e || !ordered) return e;
+    const int every = verify_every();
+    if (every && (__atomic_add_fetch(&g_launch_count, 1u, __ATOMIC_RELAXED) % (unsigned)every) == 0u)
+        return verify_launch(d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len, nblocks, (hipStream_t)stream);
     return 0;
 }
 
@@ -491,44 +539,23 @@ int lzs_hip_classify_blocks(uint32_t *d_codes, const void *d_in, size_t in_strid
     return (int)hipGetLastError();
 }
 
-// Packed compression (lzs_packed.c checks the arguments): lzs_hip_launch_compress() once more with every block's
-// place, length and room read from the offset arrays by the kernels -- the same decisions in the same order (chain_mode, LZS_VARIANT,
-// kClassifyMinBlocks, allow / catch_all from what recent launches saw, all variants while capturing); the A/B kernels of
-// LZS_KERNEL= have no packed entry.  NOT covered by the sampled self-check: LZS_VERIFY (verify_every) compares strided slots, and
-// a packed launch neither counts towards its sample nor is run again.
+// Packed compression (lzs_packed.c checks the arguments): compress_dispatch() with every block's place, length and
+// room read from the offset arrays by the kernels; the A/B kernels of LZS_KERNEL= have no packed entry.  NOT covered by the sampled
+// self-check: LZS_VERIFY (verify_every) compares strided slots, and a packed launch neither counts towards its sample nor is run again.
 int lzs_hip_launch_compress_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                                    const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream)
 {
-    if (nblocks == 0) return 0;
-    int chain_mode = 0;
-    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
-    const int forced = forced_variant();
-#define LZS_LAUNCH_VARIANT(ns, serve) \
-    hipLaunchKernelGGL(ns::lzs_compress_packed_wg_kernel, dim3(nblocks), dim3(ns::kWgThreads), 0, (hipStream_t)stream, (uint8_t *)d_out, d_out_off, \
-                       d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, nblocks, serve)
-    if (chain_mode != 0) LZS_LAUNCH_VARIANT(wgv_safe, 0u);
-#ifndef LZS_ONE_VARIANT
-    else if (forced == 2) LZS_LAUNCH_VARIANT(wgv_few, 0u);
-    else if (forced == 3) LZS_LAUNCH_VARIANT(wgv_lit, 0u);
-    else if (forced == 0 && nblocks >= kClassifyMinBlocks) {
-        uint32_t allow, catch_all, *h_seen, id;
-        variant_hint(stream, allow, catch_all, h_seen, id);
-        hipLaunchKernelGGL(lzs_classify_packed_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_out_len, d_out_off,
-                           (const uint8_t *)d_in, d_in_off, d_in_len, nblocks, allow, catch_all, h_seen, id);
-        if (allow & 2u) LZS_LAUNCH_VARIANT(wgv_text, kClassCode | 1u);
-        if (allow & 4u) LZS_LAUNCH_VARIANT(wgv_few, kClassCode | 2u);
-        if (allow & 8u) LZS_LAUNCH_VARIANT(wgv_lit, kClassCode | 3u);
-    }
-#endif
-    else LZS_LAUNCH_VARIANT(wgv_text, 0u);
-#undef LZS_LAUNCH_VARIANT
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (chain_mode == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) load_check_step(dev, nblocks >= 256u);     // (beside a launch that fills the device)
-    }
-    return 0;
+    bool ordered = false;
+    return compress_dispatch(nblocks, stream, &ordered,
+        [](int *) { return false; },
+        [&](auto v, uint32_t serve) {
+            hipLaunchKernelGGL(decltype(v)::packed, dim3(nblocks), dim3(decltype(v)::threads), 0, (hipStream_t)stream, (uint8_t *)d_out, d_out_off,
+                               d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, nblocks, serve);
+        },
+        [&](const lzs_plan_variants_t &v, uint32_t *h_seen, uint32_t id) {
+            hipLaunchKernelGGL(lzs_classify_packed_kernel, dim3((nblocks + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_out_len, d_out_off,
+                               (const uint8_t *)d_in, d_in_off, d_in_len, nblocks, v.allow, v.catch_all, h_seen, id);
+        });
 }
 
 int lzs_hip_launch_compressed_bound_packed(uint32_t *d_bound, const uint64_t *d_in_off, const uint32_t *d_in_len, uint32_t nblocks, void *stream)
@@ -541,6 +568,8 @@ int lzs_hip_launch_compressed_bound_packed(uint32_t *d_bound, const uint64_t *d_
 
 #endif  // !LZS_TU_DECOMPRESS
 #ifndef LZS_TU_COMPRESS
+static_assert(kDecGroups == LZS_PLAN_DEC_GROUPS, "lzs_launch_plan.h: streams per wavefront of the grouped decoders");
+
 static int launch_decompress(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                              const void *d_in, size_t in_stride, const uint32_t *d_in_len,
                              uint32_t in_len, uint32_t nblocks, void *stream, uint32_t concat)
@@ -564,16 +593,11 @@ static int launch_decompress(void *d_out, size_t out_stride, uint32_t out_cap, u
 #endif
     // The kernel bounds a wavefront's input loads by one 32-bit extent over its streams.  Streams so
     // far apart that eight of them do not fit (strides of hundreds of MB) go one to a wavefront.
-    const unsigned long long longest = d_in_len ? 0xC0000400ull : in_len;
-    const uint32_t per_wave = (unsigned long long)in_stride * (kDecGroups - 1u) + longest < 0xFFFFFF00ull ? kDecGroups : 1u;
-    if (concat)
-        hipLaunchKernelGGL(lzs_decompress_blocks_grp_kernel<true>, dim3((nblocks + per_wave - 1) / per_wave), dim3(64), 0,
-                           (hipStream_t)stream, (uint8_t *)d_out, out_stride, out_cap, d_out_len,
-                           (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, concat, per_wave);
-    else
-        hipLaunchKernelGGL(lzs_decompress_blocks_grp_kernel<false>, dim3((nblocks + per_wave - 1) / per_wave), dim3(64), 0,
-                           (hipStream_t)stream, (uint8_t *)d_out, out_stride, out_cap, d_out_len,
-                           (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, concat, per_wave);
+    const uint32_t per_wave = lzs_plan_dec_per_wave_blocks(in_stride, d_in_len != nullptr, in_len);
+    hipLaunchKernelGGL(concat ? lzs_decompress_blocks_grp_kernel<true> : lzs_decompress_blocks_grp_kernel<false>,
+                       dim3((nblocks + per_wave - 1) / per_wave), dim3(64), 0,
+                       (hipStream_t)stream, (uint8_t *)d_out, out_stride, out_cap, d_out_len,
+                       (const uint8_t *)d_in, in_stride, d_in_len, in_len, nblocks, concat, per_wave);
     return (int)hipGetLastError();
 }
 
@@ -597,8 +621,7 @@ int lzs_hip_launch_decompress_channels(void *d_out, size_t out_stride, uint32_t 
 {
     if (npackets == 0) return 0;
     // (eight streams to a wavefront unless their input is too far apart for one 32-bit extent: launch_decompress's rule)
-    const unsigned long long longest = d_in_len ? 0xC0000400ull : in_len;
-    const uint32_t per_wave = (unsigned long long)in_stride * (kDecGroups - 1u) + longest < 0xFFFFFF00ull ? kDecGroups : 1u;
+    const uint32_t per_wave = lzs_plan_dec_per_wave_blocks(in_stride, d_in_len != nullptr, in_len);
     hipLaunchKernelGGL(lzs_decompress_channels_grp_kernel, dim3((npackets + per_wave - 1) / per_wave), dim3(64), 0, (hipStream_t)stream,
                        (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
                        d_channel, (uint8_t *)d_states, d_status, npackets, per_wave);
@@ -613,8 +636,7 @@ int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_
 {
     if (npackets == 0) return 0;
     // (a wavefront's runs take packets from anywhere in the input: eight runs to a wavefront if all of it is one 32-bit extent)
-    const unsigned long long longest = d_in_len ? 0xC0000400ull : in_len;
-    const uint32_t per_wave = (unsigned long long)in_stride * (npackets - 1u) + longest < 0xFFFFFF00ull ? kDecGroups : 1u;
+    const uint32_t per_wave = lzs_plan_dec_per_wave_runs(in_stride, npackets, d_in_len != nullptr, in_len);
     hipLaunchKernelGGL(lzs_decompress_runs_grp_kernel, dim3((npackets + per_wave - 1) / per_wave), dim3(64), 0, (hipStream_t)stream,
                        (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
                        d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets, per_wave);
@@ -623,6 +645,21 @@ int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_
 
 #endif  // !LZS_TU_COMPRESS
 #ifndef LZS_TU_DECOMPRESS
+// A kernel that exists in the default shape and in the order-independent CHAIN form only (segments, channel packets): the form
+// the device needs, over `grid` workgroups.  LZS_SAFE_OR_TEXT names the two instances of `kernel` in wgv_safe<suffix>, wgv_text<suffix>.
+extern "C++" {
+template <class Kernel, class... Args>
+static int launch_safe_or_text(Kernel safe, unsigned safe_threads, Kernel text, unsigned text_threads, uint32_t grid, void *stream, Args... args)
+{
+    int chain_mode = 0;
+    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
+    if (chain_mode != 0) hipLaunchKernelGGL(safe, dim3(grid), dim3(safe_threads), 0, (hipStream_t)stream, args...);
+    else hipLaunchKernelGGL(text, dim3(grid), dim3(text_threads), 0, (hipStream_t)stream, args...);
+    return (int)hipGetLastError();
+}
+}  // extern "C++"
+#define LZS_SAFE_OR_TEXT(suffix, kernel) wgv_safe##suffix::kernel, wgv_safe##suffix::kWgThreads, wgv_text##suffix::kernel, wgv_text##suffix::kWgThreads
+
 int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const void *d_in, uint32_t n,
                                      uint32_t seg, uint32_t nseg, const uint32_t *d_entry,
                                      const uint8_t *d_dirty, uint32_t *d_exit, uint64_t *d_nbits,
@@ -630,38 +667,21 @@ int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const vo
                                      void *stream)
 {
     if (nseg == 0) return 0;
-    int chain_mode = 0;
-    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
-    if (chain_mode != 0)
-        hipLaunchKernelGGL(wgv_safe::lzs_compress_segments_kernel, dim3(nseg), dim3(wgv_safe::kWgThreads), 0, (hipStream_t)stream,
-                           (uint8_t *)d_slots, slot_stride, (const uint8_t *)d_in, n, seg, nseg,
-                           d_entry, d_dirty, d_exit, (unsigned long long *)d_nbits,
-                           (uint8_t *)d_out, (const unsigned long long *)d_bit_at, lim, d_open);
-    else
-        hipLaunchKernelGGL(wgv_text::lzs_compress_segments_kernel, dim3(nseg), dim3(wgv_text::kWgThreads), 0, (hipStream_t)stream,
-                           (uint8_t *)d_slots, slot_stride, (const uint8_t *)d_in, n, seg, nseg,
-                           d_entry, d_dirty, d_exit, (unsigned long long *)d_nbits,
-                           (uint8_t *)d_out, (const unsigned long long *)d_bit_at, lim, d_open);
-    return (int)hipGetLastError();
+    return launch_safe_or_text(LZS_SAFE_OR_TEXT(, lzs_compress_segments_kernel), nseg, stream,
+                               (uint8_t *)d_slots, slot_stride, (const uint8_t *)d_in, n, seg, nseg,
+                               d_entry, d_dirty, d_exit, (unsigned long long *)d_nbits,
+                               (uint8_t *)d_out, (const unsigned long long *)d_bit_at, lim, d_open);
 }
 
-// Many channels, one packet each: the default shape, or the order-independent CHAIN where the device needs it (as above).
+// Many channels, one packet each.
 int lzs_hip_launch_compress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                                      const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                                      const uint32_t *d_channel, void *d_states, uint8_t *d_status, uint32_t npackets, void *stream)
 {
     if (npackets == 0) return 0;
-    int chain_mode = 0;
-    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
-    if (chain_mode != 0)
-        hipLaunchKernelGGL(wgv_safe_ch::lzs_compress_channels_wg_kernel, dim3(npackets), dim3(wgv_safe_ch::kWgThreads), 0, (hipStream_t)stream,
-                           (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
-                           d_channel, (uint8_t *)d_states, d_status, npackets);
-    else
-        hipLaunchKernelGGL(wgv_text_ch::lzs_compress_channels_wg_kernel, dim3(npackets), dim3(wgv_text_ch::kWgThreads), 0, (hipStream_t)stream,
-                           (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
-                           d_channel, (uint8_t *)d_states, d_status, npackets);
-    return (int)hipGetLastError();
+    return launch_safe_or_text(LZS_SAFE_OR_TEXT(_ch, lzs_compress_channels_wg_kernel), npackets, stream,
+                               (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
+                               d_channel, (uint8_t *)d_states, d_status, npackets);
 }
 
 // The same from packed packets to rooms (lzs_packed.c checks the arguments).
@@ -670,18 +690,11 @@ int lzs_hip_launch_compress_channels_packed(void *d_out, const uint64_t *d_out_o
                                             void *d_states, uint8_t *d_status, uint32_t npackets, void *stream)
 {
     if (npackets == 0) return 0;
-    int chain_mode = 0;
-    { const int e = lzs_hip_chain_mode(stream, &chain_mode); if (e) return e; }
-    if (chain_mode != 0)
-        hipLaunchKernelGGL(wgv_safe_ch::lzs_compress_channels_packed_wg_kernel, dim3(npackets), dim3(wgv_safe_ch::kWgThreads), 0, (hipStream_t)stream,
-                           (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, d_channel, (uint8_t *)d_states,
-                           d_status, npackets);
-    else
-        hipLaunchKernelGGL(wgv_text_ch::lzs_compress_channels_packed_wg_kernel, dim3(npackets), dim3(wgv_text_ch::kWgThreads), 0, (hipStream_t)stream,
-                           (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, d_channel, (uint8_t *)d_states,
-                           d_status, npackets);
-    return (int)hipGetLastError();
+    return launch_safe_or_text(LZS_SAFE_OR_TEXT(_ch, lzs_compress_channels_packed_wg_kernel), npackets, stream,
+                               (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len, d_channel, (uint8_t *)d_states,
+                               d_status, npackets);
 }
+#undef LZS_SAFE_OR_TEXT
 
 int lzs_hip_launch_extend_resume(void *d_out, uint32_t bit0, const void *d_in, uint32_t n, uint32_t c0,
                                  uint32_t off, int last, uint32_t *d_result, void *stream)
@@ -711,29 +724,25 @@ int lzs_hip_launch_scan_stream(const void *d_in, uint32_t n, uint32_t nseg, cons
                                const uint32_t *d_seg_base, const uint32_t *d_seg_end, uint32_t in_extent, void *stream)
 {
     if (nseg == 0) return 0;
-    static const int old_scan = [] { const char *v = getenv("LZS_SCAN"); return v && v[0] == 'w'; }();   // LZS_SCAN=wave: A/B
-    if (!old_scan && (d_all_ones || compare)) {
-        // a lane per segment; the first round with the all-0xFF flags, the later ones against its marks
-        static const int g8_scan = [] { const char *v = getenv("LZS_SCAN"); return v && v[0] == 'g'; }();   // LZS_SCAN=g8: A/B
-        if (d_all_ones)
-            hipLaunchKernelGGL(lzs_all_ones_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                               (const uint8_t *)d_in, n, nseg, d_all_ones, seg, d_seg_base, d_seg_end);
-#define LZS_LAUNCH_SCAN(L, C, GRID) hipLaunchKernelGGL((lzs_scan_stream_g8_kernel<L, C>), dim3(GRID), dim3(64), 0, (hipStream_t)stream, \
-                               (const uint8_t *)d_in, n, nseg, d_entry, d_dirty, d_exit, d_count, d_marks, compare ? 1u : 0u, seg, \
-                               concat ? 1u : 0u, d_seg_base, d_seg_end, in_extent)
-        if (g8_scan) {
-            if (concat) LZS_LAUNCH_SCAN(8, true, (nseg + 7) / 8); else LZS_LAUNCH_SCAN(8, false, (nseg + 7) / 8);
-        } else {
-            if (d_marks && !compare)     // no marks yet (one store per lane and mark otherwise: 128 scattered words a segment)
-                (void)hipMemsetAsync(d_marks, 0xFF, (size_t)nseg * kScanMarkWords * sizeof(uint32_t), (hipStream_t)stream);
-            if (concat) LZS_LAUNCH_SCAN(1, true, (nseg + 63) / 64); else LZS_LAUNCH_SCAN(1, false, (nseg + 63) / 64);
-        }
-#undef LZS_LAUNCH_SCAN
+    static const int scan_env = [] { const char *v = getenv("LZS_SCAN"); return !v ? 0 : (v[0] == 'w' ? 1 : (v[0] == 'g' ? 2 : 0)); }();   // LZS_SCAN=wave|g8: A/B
+    const lzs_plan_scan_t plan = lzs_plan_scan(d_all_ones != nullptr, compare, d_marks != nullptr, concat, scan_env);
+    if (plan.lanes == 0) {
+        hipLaunchKernelGGL(lzs_scan_stream_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                           (const uint8_t *)d_in, n, nseg, d_entry, d_dirty, d_exit, d_count, d_all_ones,
+                           d_marks, compare ? 1u : 0u, seg, concat ? 1u : 0u, d_seg_base, d_seg_end);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(lzs_scan_stream_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       (const uint8_t *)d_in, n, nseg, d_entry, d_dirty, d_exit, d_count, d_all_ones,
-                       d_marks, compare ? 1u : 0u, seg, concat ? 1u : 0u, d_seg_base, d_seg_end);
+    // a lane per segment; the first round with the all-0xFF flags, the later ones against its marks
+    if (plan.all_ones_first)
+        hipLaunchKernelGGL(lzs_all_ones_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                           (const uint8_t *)d_in, n, nseg, d_all_ones, seg, d_seg_base, d_seg_end);
+    if (plan.clear_marks)            // no marks yet (one store per lane and mark otherwise: 128 scattered words a segment)
+        (void)hipMemsetAsync(d_marks, 0xFF, (size_t)nseg * kScanMarkWords * sizeof(uint32_t), (hipStream_t)stream);
+#define LZS_SCAN_KERNEL(L) (plan.concat ? lzs_scan_stream_g8_kernel<L, true> : lzs_scan_stream_g8_kernel<L, false>)
+    hipLaunchKernelGGL(plan.lanes == 8 ? LZS_SCAN_KERNEL(8) : LZS_SCAN_KERNEL(1), dim3(plan.lanes == 8 ? (nseg + 7) / 8 : (nseg + 63) / 64), dim3(64), 0,
+                       (hipStream_t)stream, (const uint8_t *)d_in, n, nseg, d_entry, d_dirty, d_exit, d_count, d_marks, compare ? 1u : 0u, seg,
+                       concat ? 1u : 0u, d_seg_base, d_seg_end, in_extent);
+#undef LZS_SCAN_KERNEL
     return (int)hipGetLastError();
 }
 
@@ -745,32 +754,21 @@ int lzs_hip_launch_decode_stream(void *d_out, uint32_t cap, uint32_t *d_origin, 
 {
     if (nseg == 0) return 0;
     static const int old_decode = [] { const char *v = getenv("LZS_SEG_DECODE"); return v && v[0] == 'w'; }();   // LZS_SEG_DECODE=wave: A/B
-    // streams that expand more than sixfold are runs: there one wavefront per segment wins (60 bytes a step)
-    // (n == 0: a batch of blocks with segment tables -- the expansion is not known here)
-    if (!old_decode && (n == 0u || (unsigned long long)cap <= 6ull * n)) {
-        // between a quarter and nine tenths of its output a stream is mostly short matches (text: 0.57):
-        // there a second token per trip pays (lzs_decompress_blocks_grp has the numbers)
-        static const int one_token = [] { return getenv("LZS_DEC_ONE_TOKEN") != nullptr; }();
-        const bool two = !one_token && n != 0u && 4ull * n > cap && 10ull * n < 9ull * cap;
-        const bool wide = !one_token && n != 0u && 10ull * n >= 9ull * cap;      // mostly literals: the 96-bit buffer
-#define LZS_LAUNCH_G8(T, W, C) hipLaunchKernelGGL((lzs_decode_stream_g8_kernel<T, W, C>), dim3((nseg + 7) / 8), dim3(64), 0, (hipStream_t)stream, \
-                               (uint8_t *)d_out, cap, d_origin, d_tainted, (const uint8_t *)d_in, n, in_extent, nseg, d_entry, d_out_start, seg, concat ? 1u : 0u, \
-                               d_seg_base, d_seg_end, d_out_floor, d_out_limit)
-        if (concat) {
-            if (two) LZS_LAUNCH_G8(true, false, true);
-            else if (wide) LZS_LAUNCH_G8(false, true, true);
-            else LZS_LAUNCH_G8(false, false, true);
-        } else {
-            if (two) LZS_LAUNCH_G8(true, false, false);
-            else if (wide) LZS_LAUNCH_G8(false, true, false);
-            else LZS_LAUNCH_G8(false, false, false);
-        }
-#undef LZS_LAUNCH_G8
+    static const int one_token = [] { return getenv("LZS_DEC_ONE_TOKEN") != nullptr; }();
+    const int form = lzs_plan_decode_stream(n, cap, old_decode, one_token);
+    if (form == LZS_DECODE_WAVE) {
+        hipLaunchKernelGGL(lzs_decode_stream_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream,
+                           (uint8_t *)d_out, cap, d_origin, d_tainted, (const uint8_t *)d_in, n, nseg, d_entry, d_out_start, seg, concat ? 1u : 0u,
+                           d_seg_base, d_seg_end, d_out_floor, d_out_limit);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(lzs_decode_stream_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                       (uint8_t *)d_out, cap, d_origin, d_tainted, (const uint8_t *)d_in, n, nseg, d_entry, d_out_start, seg, concat ? 1u : 0u,
+    // eight segments per wavefront: a second token per trip, or the 96-bit buffer (lzs_decompress_blocks_grp has the numbers)
+#define LZS_G8_KERNEL(T, W) (concat ? lzs_decode_stream_g8_kernel<T, W, true> : lzs_decode_stream_g8_kernel<T, W, false>)
+    hipLaunchKernelGGL(form == LZS_DECODE_G8_TWO ? LZS_G8_KERNEL(true, false) : (form == LZS_DECODE_G8_WIDE ? LZS_G8_KERNEL(false, true) : LZS_G8_KERNEL(false, false)),
+                       dim3((nseg + 7) / 8), dim3(64), 0, (hipStream_t)stream,
+                       (uint8_t *)d_out, cap, d_origin, d_tainted, (const uint8_t *)d_in, n, in_extent, nseg, d_entry, d_out_start, seg, concat ? 1u : 0u,
                        d_seg_base, d_seg_end, d_out_floor, d_out_limit);
+#undef LZS_G8_KERNEL
     return (int)hipGetLastError();
 }
 
@@ -787,9 +785,7 @@ int lzs_hip_launch_resolve_stream(void *d_out, uint32_t *d_origin, uint32_t tota
                                   uint32_t *d_left, int last, void *stream)
 {
     if (total == 0) return 0;
-    uint32_t grid = (total / 4u + 255u) / 256u + 1u;          // four bytes a thread
-    if (grid > 65536u) grid = 65536u;
-    hipLaunchKernelGGL(lzs_resolve_stream_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(lzs_resolve_stream_kernel, dim3(lzs_plan_resolve_grid(total)), dim3(256), 0, (hipStream_t)stream,     // four bytes a thread
                        (uint8_t *)d_out, d_origin, total, round, d_left, last ? 1u : 0u);
     return (int)hipGetLastError();
 }
@@ -844,29 +840,32 @@ int lzs_hip_launch_scan_sizes(uint64_t *d_offsets, const uint32_t *d_size, uint3
 
 #endif  // !LZS_TU_COMPRESS
 #ifndef LZS_TU_DECOMPRESS
-int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
-                           size_t slot_stride, const uint32_t *d_len, uint32_t nblocks, void *stream)
-{
-    hipLaunchKernelGGL(lzs_scan_lengths_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream,
-                       d_offsets, d_len, nblocks);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || nblocks == 0) return (int)e;
-    hipLaunchKernelGGL(lzs_gather_slots_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream,
-                       (uint8_t *)d_dense, d_offsets, (const uint8_t *)d_slots, slot_stride, d_len,
-                       nblocks);
-    return (int)hipGetLastError();
-}
-
-// lzs_hip_launch_compact() with slot b at d_src + d_src_off[b]: the scan of the lengths, then the gather from the rooms.
-int lzs_hip_launch_compact_packed(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off,
-                                  const uint32_t *d_len, uint32_t nblocks, void *stream)
+// The scan of the lengths, then the gather: from slots slot_stride apart, or (d_src_off) from slot b at d_src + d_src_off[b].
+static int launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_src, size_t slot_stride, const uint64_t *d_src_off,
+                          const uint32_t *d_len, uint32_t nblocks, void *stream)
 {
     hipLaunchKernelGGL(lzs_scan_lengths_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_offsets, d_len, nblocks);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || nblocks == 0) return (int)e;
-    hipLaunchKernelGGL(lzs_gather_packed_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_dense, d_offsets,
-                       (const uint8_t *)d_src, d_src_off, d_len, nblocks);
+    if (d_src_off)
+        hipLaunchKernelGGL(lzs_gather_packed_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_dense, d_offsets,
+                           (const uint8_t *)d_src, d_src_off, d_len, nblocks);
+    else
+        hipLaunchKernelGGL(lzs_gather_slots_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, (uint8_t *)d_dense, d_offsets,
+                           (const uint8_t *)d_src, slot_stride, d_len, nblocks);
     return (int)hipGetLastError();
+}
+
+int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
+                           size_t slot_stride, const uint32_t *d_len, uint32_t nblocks, void *stream)
+{
+    return launch_compact(d_dense, d_offsets, d_slots, slot_stride, nullptr, d_len, nblocks, stream);
+}
+
+int lzs_hip_launch_compact_packed(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off,
+                                  const uint32_t *d_len, uint32_t nblocks, void *stream)
+{
+    return launch_compact(d_dense, d_offsets, d_src, 0, d_src_off, d_len, nblocks, stream);
 }
 
 int lzs_hip_launch_decode_resume(lzs_dec_resume_t *d_state, const void *d_in, uint32_t n,

@@ -1,0 +1,122 @@
+/* lzs_launch_plan.h -- which kernels a call of the launchers in lzs_kernels.hip runs, as plain functions of what the launcher knows.
+ *
+ * Plain C that also compiles as C++: no HIP, no globals, no getenv.  Every environment flag and every piece of device state
+ * comes in as an argument, so the rules stand where a CPU test reaches them: tests/cpu_shim/plan_check.c holds each of them
+ * to a table of literal rows (tests/test_launch_plan.py).  A launcher asks its plan and then launches; none keeps a copy of a rule.
+ */
+#ifndef LZS_LAUNCH_PLAN_H
+#define LZS_LAUNCH_PLAN_H
+
+#include <stdint.h>
+
+/* What lzs_kernels.hip holds equal to its kernels' constants with static_assert. */
+#define LZS_PLAN_DEC_GROUPS 8u             /* kDecGroups: streams per wavefront of the grouped decoders */
+/* A compress launch of this many blocks fills the device: the LDS ordering check may start beside it. */
+#define LZS_PLAN_LOAD_CHECK_BLOCKS 256u
+
+/* ---- compress: which variants of the kernel a classified launch runs ------------------------------------------------------
+ * seen[c], c = 1..3: the id of the last launch whose classifier met a block of class c (0: never; ids are never 0 and wrap).
+ * allow: bit c set = variant c is launched; a block of another class goes to catch_all -- the default variant (1) if that
+ * runs, else the first that does.  All three while nothing is known (no words, or no class seen yet), and while the stream is
+ * being captured into a graph: the guess would be frozen with it.  Otherwise the classes one of the last three classifiers met.
+ * An id is a launch counter with bit 31 set, so after 0xFFFFFFFF comes 0x80000000: ids are compared as serial numbers of 31 bits
+ * (a is later than b when it is ahead by less than 2^30), and an age is a difference of 31 bits. */
+typedef struct { uint32_t allow, catch_all; } lzs_plan_variants_t;
+
+static inline lzs_plan_variants_t lzs_plan_variants(const uint32_t seen[4], int have_seen, int capturing)
+{
+    lzs_plan_variants_t p = { 0xEu, 1u };
+    uint32_t newest = 0;
+    int c;
+    if (!have_seen || capturing) return p;
+    for (c = 1; c <= 3; c++)
+        if (seen[c] && (newest == 0 || (int32_t)((seen[c] - newest) << 1) > 0)) newest = seen[c];
+    if (newest == 0) return p;
+    p.allow = 0;
+    for (c = 1; c <= 3; c++)
+        if (seen[c] && ((newest - seen[c]) & 0x7FFFFFFFu) <= 2u) p.allow |= 1u << c;
+    p.catch_all = (p.allow & 2u) ? 1u : ((p.allow & 4u) ? 2u : 3u);
+    return p;
+}
+
+/* ---- compress: one variant for every block (serve 0), or the classifier and then the allowed variants ----------------------
+ * chain_mode != 0: the order-independent CHAIN for all blocks.  forced: LZS_VARIANT, 0 none, 1 text, 2 few, 3 lit.  A launch
+ * of fewer than classify_min blocks takes the default alone.  one_variant: a build with the default and the safe form only.
+ * The load check steps beside launches of the ordered form, and may start beside one that fills the device. */
+enum { LZS_RUN_SAFE = 0, LZS_RUN_FEW = 1, LZS_RUN_LIT = 2, LZS_RUN_TEXT = 3, LZS_RUN_CLASSIFY = 4 };
+typedef struct { int run; int load_check; int load_check_start; } lzs_plan_compress_t;
+
+static inline lzs_plan_compress_t lzs_plan_compress(int chain_mode, int forced, uint32_t nblocks, uint32_t classify_min, int one_variant)
+{
+    lzs_plan_compress_t p;
+    if (chain_mode != 0) p.run = LZS_RUN_SAFE;
+    else if (one_variant) p.run = LZS_RUN_TEXT;
+    else if (forced == 2) p.run = LZS_RUN_FEW;
+    else if (forced == 3) p.run = LZS_RUN_LIT;
+    else if (forced == 0 && nblocks >= classify_min) p.run = LZS_RUN_CLASSIFY;
+    else p.run = LZS_RUN_TEXT;
+    p.load_check = chain_mode == 0;
+    p.load_check_start = p.load_check && nblocks >= LZS_PLAN_LOAD_CHECK_BLOCKS;
+    return p;
+}
+
+/* ---- grouped decoders: streams per wavefront --------------------------------------------------------------------------------
+ * The kernels bound a wavefront's input loads by one 32-bit extent over its streams: eight streams to a wavefront unless
+ * `span` strides and the longest stream do not fit one (have_lens: lengths on the device, the longest a stream may be). */
+static inline uint32_t lzs_plan_dec_per_wave(uint64_t in_stride, uint32_t span, int have_lens, uint32_t in_len)
+{
+    const uint64_t longest = have_lens ? 0xC0000400ull : in_len;
+    return in_stride * span + longest < 0xFFFFFF00ull ? LZS_PLAN_DEC_GROUPS : 1u;
+}
+/* blocks and channel packets: a wavefront takes eight neighbours */
+static inline uint32_t lzs_plan_dec_per_wave_blocks(uint64_t in_stride, int have_lens, uint32_t in_len)
+{
+    return lzs_plan_dec_per_wave(in_stride, LZS_PLAN_DEC_GROUPS - 1u, have_lens, in_len);
+}
+/* runs of channel packets: a wavefront's runs take packets from anywhere in the input (npackets >= 1) */
+static inline uint32_t lzs_plan_dec_per_wave_runs(uint64_t in_stride, uint32_t npackets, int have_lens, uint32_t in_len)
+{
+    return lzs_plan_dec_per_wave(in_stride, npackets - 1u, have_lens, in_len);
+}
+
+/* ---- segments of a stream: the decode kernel's form -------------------------------------------------------------------------
+ * n bytes of input decode to at most cap (n == 0: a batch of blocks with segment tables, the expansion is not known).
+ * Streams that expand more than sixfold are runs: one wavefront per segment.  Otherwise eight segments per wavefront:
+ * between a quarter and nine tenths of its output a stream is mostly short matches (a second token per trip), from nine
+ * tenths mostly literals (the 96-bit buffer).  old_decode: LZS_SEG_DECODE=wave; one_token: LZS_DEC_ONE_TOKEN. */
+enum { LZS_DECODE_WAVE = 0, LZS_DECODE_G8_PLAIN = 1, LZS_DECODE_G8_TWO = 2, LZS_DECODE_G8_WIDE = 3 };
+
+static inline int lzs_plan_decode_stream(uint32_t n, uint32_t cap, int old_decode, int one_token)
+{
+    const uint64_t n64 = n, cap64 = cap;
+    if (old_decode || !(n == 0u || cap64 <= 6u * n64)) return LZS_DECODE_WAVE;
+    if (one_token || n == 0u) return LZS_DECODE_G8_PLAIN;
+    if (4u * n64 > cap64 && 10u * n64 < 9u * cap64) return LZS_DECODE_G8_TWO;
+    if (10u * n64 >= 9u * cap64) return LZS_DECODE_G8_WIDE;
+    return LZS_DECODE_G8_PLAIN;
+}
+
+/* ---- segments of a stream: the scan kernel's form ---------------------------------------------------------------------------
+ * scan_env: LZS_SCAN, 0 not set, 1 wave, 2 g8.  A lane per segment (lanes = 1; LZS_SCAN=g8: eight lanes) in the first round,
+ * which has the all-0xFF flags to fill first, and in the later ones, which compare against its marks; the wave kernel when
+ * neither holds or LZS_SCAN=wave asks for it.  With a lane per segment the marks start from 0xFF when there are none yet. */
+typedef struct { int lanes; int concat; int all_ones_first; int clear_marks; } lzs_plan_scan_t;    /* lanes 0: the wave kernel */
+
+static inline lzs_plan_scan_t lzs_plan_scan(int have_all_ones, int compare, int have_marks, int concat, int scan_env)
+{
+    lzs_plan_scan_t p = { 0, concat ? 1 : 0, 0, 0 };
+    if (scan_env == 1 || !(have_all_ones || compare)) return p;
+    p.lanes = scan_env == 2 ? 8 : 1;
+    p.all_ones_first = have_all_ones ? 1 : 0;
+    p.clear_marks = p.lanes == 1 && have_marks && !compare;
+    return p;
+}
+
+/* ---- origins resolved everywhere: four bytes a thread, 256 threads a workgroup, one workgroup more, 65536 at the most --------- */
+static inline uint32_t lzs_plan_resolve_grid(uint32_t total)
+{
+    const uint32_t grid = (total / 4u + 255u) / 256u + 1u;
+    return grid > 65536u ? 65536u : grid;
+}
+
+#endif
