@@ -198,7 +198,8 @@ int lzs_compact_device(void *d_dense, uint64_t *d_offsets, const void *d_slots, 
  * note on the very first call into the library applies).  Checked before the device is asked (LZS_E_ARG, the call's name in
  * lzs_last_error()): a required pointer that is NULL, an offset array that is not 8-byte aligned, d_out_len / d_size being the
  * array d_in_len, nblocks > 0x7FFFFFFF, limit > 0xFFFFFFFF, a bad align.  Offsets are uint64_t; a torch int64 tensor holds the
- * same bits.  Not offered: packed bursts, host-buffer entries.
+ * same bits.  Not offered: host-buffer entries.  Many packets
+ * per channel in one packed call: lzs_*_channels_burst_packed_device (lzs_channels.h).
  *
  * lzs_offsets_from_sizes_device: d_offsets[0] = 0, d_offsets[b + 1] = d_offsets[b] + round_up(d_size[b], align); nblocks + 1
  * entries, the total in d_offsets[nblocks]; nblocks == 0 writes d_offsets[0] = 0.  `align`: a power of two from 1 to 256 -- 16

@@ -102,7 +102,8 @@ int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_ca
  * in lzs_batch.h; d_states must be given and 4-byte aligned.  One packet per channel per call: the rule on repeated channels
  * above holds.  Every packet's bytes, d_out_len[b], d_status[b] and its channel's slot are byte for byte what
  * lzs_decompress_channels_device() gives for that packet alone with out_cap = its room; a slot with hist_len > 2047 gets ERROR
- * and d_out_len[b] = 0 as there.  lzs_decompressed_size_packed_device() sizes the rooms.  Packed bursts are not offered.
+ * and d_out_len[b] = 0 as there.  lzs_decompressed_size_packed_device() sizes the rooms.  Many packets per channel:
+ * lzs_decompress_channels_burst_packed_device() below.
  */
 int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                                           const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
@@ -116,7 +117,8 @@ int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off
  * INPUT_FINISHED | INPUT_STARVED = 0x07, or 0x0B with NO_OUTPUT_BUFFER_SPACE in END_MARKER's place where the room cut it) and its
  * channel's whole slot are those of lzs_compress_channels_device() for that packet alone with out_cap = its room.  A slot with
  * hist_len > 2047 gets ERROR and d_out_len[b] = 0, nothing changed; an entry that is not a block gets ERROR and d_out_len[b] = 0 and
- * its channel's slot is not touched.  lzs_compressed_bound_packed_device() sizes the rooms.  Packed bursts are not offered.
+ * its channel's slot is not touched.  lzs_compressed_bound_packed_device() sizes the rooms.  Many packets per channel:
+ * lzs_compress_channels_burst_packed_device() below.
  */
 int lzs_compress_channels_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                                         const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
@@ -164,6 +166,56 @@ int lzs_decompress_channels_burst_device(void *d_out, size_t out_stride, size_t 
                                          const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
                                          const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
                                          void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
+
+/*
+ * PACKED BURSTS: a drained queue compressed or decoded where it lies -- many packets per channel, as in the burst
+ * calls above, each addressed as in the packed calls: packet b lies at d_in + d_in_off[b] (d_in_len[b] bytes, or up to d_in_off[b + 1]
+ * with d_in_len NULL) and goes to d_out + d_out_off[b] with d_out_off[b + 1] - d_out_off[b] bytes of room, clamped to 0xFFFFFFFF;
+ * npackets + 1 output offsets are always read.  Addressing, containment -- a packet stores to [d_out_off[b], d_out_off[b] +
+ * d_out_len[b]) of d_out and to no other byte of it -- and the entries that are not a block (offsets that decrease, a length above
+ * LZS_BLOCK_MAX) are those of "PACKED streams" in lzs_batch.h.
+ *
+ * THE RESULT is the burst rule applied to the packed calls: split the call into ranks (rank k = the k-th packet of every channel, in
+ * ascending b) and make one call of lzs_compress_channels_packed_device / lzs_decompress_channels_packed_device per rank, in order;
+ * every packet's bytes, d_out_len[b] and d_status[b] and every channel's final slot are byte for byte what that gives.  So:
+ *   - an entry that is not a block gets ERROR and d_out_len[b] = 0; nothing of it is read or written, it adds nothing to its
+ *     channel's history, and the run goes on behind it with the history it had;
+ *   - a channel whose packets in this call are all not blocks keeps its slot untouched byte for byte, whatever lies behind hist_len;
+ *   - a slot with hist_len > 2047 gives every packet of that channel ERROR and d_out_len[b] = 0 and stays untouched, and so does
+ *     d_channel[b] >= nchannels for that packet;
+ *   - a compressed packet cut at its room has NO_OUTPUT_BUFFER_SPACE in END_MARKER's place (0x0B) and still advances the history; a
+ *     decoder copy cut at its room gives NO_OUTPUT_BUFFER_SPACE and advances the history by what was produced;
+ *   - a packet of no bytes is a block: the compressor writes its end marker, the history is as it was.
+ *
+ * SIZING THE ROOMS.  lzs_compressed_bound_packed_device() and lzs_decompressed_size_packed_device() (lzs_batch.h) apply unchanged: a
+ * packet's compressed bound depends on its length alone, and its decoded length and status never depend on its channel's history.
+ *
+ * THE WORK AREA is that of the burst calls: d_work 256-byte aligned, work_bytes at least lzs_channels_burst_work_bytes(npackets,
+ * nchannels), for both calls.  With at least lzs_channels_burst_packed_split_work_bytes(npackets, nchannels, out_bytes) bytes -- the
+ * burst size plus two bytes per byte of room, out_bytes being the sum of the rooms (d_out_off[npackets] - d_out_off[0] for offsets
+ * that ascend); SIZE_MAX where that does not fit a size_t -- the decoder may split long runs as above.  The offsets are on the device,
+ * so the device decides: if the sum of the (clamped) rooms does not fit what the work area holds behind the burst size, no run of that
+ * call is split.  The results are the same byte for byte whichever way a run is decoded, and nothing is written outside work_bytes.
+ * The compressor ignores the extra room.
+ *
+ * Arguments are checked before the device is asked (LZS_E_ARG): those of the packed calls -- d_out, d_in, d_out_off, d_in_off and
+ * d_out_len given, the offset arrays 8-byte aligned, d_out_len not the array d_in_len, npackets at most LZS_CHANNELS_MAX -- and those
+ * of the burst calls -- d_states given and 4-byte aligned, d_channel and d_work given, d_work 256-byte aligned, work_bytes no smaller
+ * than the burst size, nchannels not 0 when there are packets and at most LZS_CHANNELS_MAX.  npackets == 0 is LZS_OK and touches
+ * nothing; without a device a valid call returns LZS_E_NO_DEVICE.  No allocation and no synchronisation: safe to capture into a
+ * hipGraph, with the caveat of the calls above.
+ */
+size_t lzs_channels_burst_packed_split_work_bytes(size_t npackets, size_t nchannels, uint64_t out_bytes);
+
+int lzs_compress_channels_burst_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
+                                              const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                              const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
+                                              void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
+
+int lzs_decompress_channels_burst_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
+                                                const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                                const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
+                                                void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,8 @@ from .api import (STATUS_END_MARKER, STATUS_ERROR, STATUS_INPUT_FINISHED, STATUS
 from .api import decompress_blocks_dense, decompressed_sizes
 from .api import decompress_channels_packed, decompress_dense, decompress_packed, decompressed_sizes_packed, offsets_from_sizes
 from .api import compact_packed, compress_channels_packed, compress_dense, compress_packed, compressed_bounds_packed
+from .api import (channels_burst_packed_split_work_bytes, compress_channels_burst_packed, compress_channels_dense,
+                  decompress_channels_burst_packed, decompress_channels_dense)
 from . import workload
 
 __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_bytes", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
@@ -24,4 +26,6 @@ __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_byt
            "STATUS_END_MARKER", "STATUS_ERROR", "STATUS_INPUT_FINISHED", "STATUS_INPUT_STARVED", "STATUS_NO_OUTPUT_BUFFER_SPACE",
            "decompress_blocks_dense", "decompressed_sizes",
            "decompress_channels_packed", "decompress_dense", "decompress_packed", "decompressed_sizes_packed", "offsets_from_sizes",
-           "compact_packed", "compress_channels_packed", "compress_dense", "compress_packed", "compressed_bounds_packed"]
+           "compact_packed", "compress_channels_packed", "compress_dense", "compress_packed", "compressed_bounds_packed",
+           "channels_burst_packed_split_work_bytes", "compress_channels_burst_packed", "compress_channels_dense",
+           "decompress_channels_burst_packed", "decompress_channels_dense"]

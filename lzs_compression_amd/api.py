@@ -125,6 +125,12 @@ def lib() -> ctypes.CDLL:
             L.lzs_compress_channels_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
             L.lzs_compact_packed_device.restype = ctypes.c_int
             L.lzs_compact_packed_device.argtypes = [_vp, _vp, _vp, _vp, _vp, _sz, _vp]
+        if hasattr(L, "lzs_compress_channels_burst_packed_device"):      # (the same: packed bursts)
+            L.lzs_channels_burst_packed_split_work_bytes.restype = _sz
+            L.lzs_channels_burst_packed_split_work_bytes.argtypes = [_sz, _sz, ctypes.c_uint64]
+            for name in ("lzs_compress_channels_burst_packed_device", "lzs_decompress_channels_burst_packed_device"):
+                f = getattr(L, name)
+                f.restype, f.argtypes = ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp]
         _lib = L
     return _lib
 
@@ -832,6 +838,117 @@ def decompress_channels_burst(x, in_len, channels, states, out_capacity: int, ou
     Returns (out, lengths int32, status uint8: LZS_D_STATUS_* bits)."""
     return _device_burst(lib().lzs_decompress_channels_burst_device, x, in_len, channels, states, out_capacity, out, out_len,
                          status, work, stream, split=True)
+
+
+# ------------------------------- packed bursts: many packets per channel, addressed by offsets (lzs_channels.h; DESIGN.md 3.16)
+def channels_burst_packed_split_work_bytes(npackets: int, nchannels: int, out_bytes: int) -> int:
+    """lzs_channels_burst_packed_split_work_bytes(): the work area with which decompress_channels_burst_packed may split long runs
+    -- channels_burst_work_bytes() plus two bytes per byte of room, ``out_bytes`` being the sum of the rooms."""
+    return int(lib().lzs_channels_burst_packed_split_work_bytes(npackets, nchannels, out_bytes))
+
+
+def _device_burst_packed(fn, data, in_off, channels, states, out, out_off, in_len, out_len, status, work, stream, split):
+    import torch
+    nb = _packed_output(out, out_off)
+    _packed_input(data, in_off, in_len, nb)
+    assert channels is not None and channels.is_cuda and channels.dtype == torch.int32 and channels.is_contiguous() \
+        and channels.numel() == nb, "channels must be a contiguous CUDA int32 tensor [npackets]"
+    assert states.is_cuda and states.dtype == torch.uint8 and states.dim() == 2 and states.is_contiguous() \
+        and states.shape[1] == CHANNEL_STATE_BYTES, "states must be a contiguous CUDA uint8 tensor [nchannels, CHANNEL_STATE_BYTES]"
+    nch = states.shape[0]
+    if out_len is None:
+        out_len = torch.empty(nb, dtype=torch.int32, device=data.device)
+    assert out_len.is_cuda and out_len.dtype == torch.int32 and out_len.numel() == nb and out_len.is_contiguous()
+    if status is None:
+        status = torch.empty(nb, dtype=torch.uint8, device=data.device)
+    assert status.is_cuda and status.dtype == torch.uint8 and status.numel() == nb and status.is_contiguous()
+    if work is None:
+        # (the rooms lie in ``out``: its size stands for their sum, which only the device knows -- and it checks)
+        need = channels_burst_packed_split_work_bytes(nb, nch, out.numel()) if split else channels_burst_work_bytes(nb, nch)
+        work = _BURST_WORK.get(str(data.device))
+        if work is None or work.numel() < need:
+            work = torch.empty(max(need, 256), dtype=torch.uint8, device=data.device)
+            _BURST_WORK[str(data.device)] = work
+    assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous(), "work must be a contiguous CUDA uint8 tensor"
+    _check(fn(_ptr(out, out_off), out_off.data_ptr(), out_len.data_ptr(), _ptr(data, in_off), in_off.data_ptr(),
+              None if in_len is None else in_len.data_ptr(), channels.data_ptr(), states.data_ptr(), nch, status.data_ptr(),
+              work.data_ptr(), work.numel(), nb, _stream_handle(stream)))
+    return out, out_len, status
+
+
+def compress_channels_burst_packed(data, in_off, channels, states, out, out_off, in_len=None, out_len=None, status=None, work=None,
+                                   stream=None):
+    """lzs_compress_channels_burst_packed_device(): compress_channels_burst() from packed packets to packed rooms -- a drained
+    queue compressed where it lies.  Packet b is data[in_off[b]:in_off[b + 1]] (or ``in_len[b]`` bytes at in_off[b]) on channel
+    ``channels[b]`` (CUDA int32, required; ids may repeat, the packets of a channel are taken in order of b) and goes to
+    out[out_off[b]:out_off[b + 1]], its room.  ``work``: as for compress_channels_burst.  Returns (out, out_len int32, status uint8:
+    0x07, 0x0B where the room cut the packet, STATUS_ERROR for an entry that is not a block, an id >= len(states) or a slot that is
+    no state).  Asynchronous."""
+    return _device_burst_packed(lib().lzs_compress_channels_burst_packed_device, data, in_off, channels, states, out, out_off, in_len,
+                                out_len, status, work, stream, False)
+
+
+def decompress_channels_burst_packed(data, in_off, channels, states, out, out_off, in_len=None, out_len=None, status=None, work=None,
+                                     stream=None):
+    """lzs_decompress_channels_burst_packed_device(): the reverse, on the decompressor's states.  Arguments as
+    compress_channels_burst_packed.  The default work area has channels_burst_packed_split_work_bytes() bytes for rooms of
+    len(out) bytes, with which long runs are split over the device; a caller's ``work`` decides by its size (the results are the
+    same).  Returns (out, out_len int32, status uint8: LZS_D_STATUS_* bits)."""
+    return _device_burst_packed(lib().lzs_decompress_channels_burst_packed_device, data, in_off, channels, states, out, out_off, in_len,
+                                out_len, status, work, stream, True)
+
+
+def compress_channels_dense(data, in_off, channels, states, in_len=None, align: int = 16, stream=None):
+    """A drained packet queue compressed into ONE dense byte string of channel packets: compressed_bounds_packed(),
+    offsets_from_sizes() at ``align`` for the rooms, one host read of their total, one allocation of the rooms,
+    compress_channels_burst_packed() on ``states``, the scan of the lengths, one host read of the dense total, one allocation of
+    exactly that, compact_packed().  Returns (dense uint8 [total], offsets int64 [npackets + 1], status uint8 [npackets]); packet b's
+    stream is dense[offsets[b]:offsets[b + 1]] -- empty for a packet that got STATUS_ERROR --, and decompress_channels_dense(dense,
+    offsets, channels, peer_states) gives the packets back.  Peak device memory: as compress_dense(), and the burst work area."""
+    import torch
+    nb = _packed_input(data, in_off, in_len)
+    if nb == 0:
+        return (torch.empty(0, dtype=torch.uint8, device=data.device), torch.zeros(1, dtype=torch.int64, device=data.device),
+                torch.empty(0, dtype=torch.uint8, device=data.device))
+    size = compressed_bounds_packed(in_off, in_len, stream=stream)
+    room_off = offsets_from_sizes(size, align, stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        rooms = torch.empty(int(room_off[nb].cpu()), dtype=torch.uint8, device=data.device)          # the first host read
+        _, _, status = compress_channels_burst_packed(data, in_off, channels, states, rooms, room_off, in_len=in_len, out_len=size,
+                                                      stream=stream)                                 # (the lengths take the bounds' place)
+        offsets = offsets_from_sizes(size, 1, stream=stream)
+        dense = torch.empty(int(offsets[nb].cpu()), dtype=torch.uint8, device=data.device)           # the second host read
+    compact_packed(rooms, room_off, size, stream=stream, dense=dense, offsets=offsets)
+    return dense, offsets, status
+
+
+def decompress_channels_dense(data, in_off, channels, states, in_len=None, align: int = 1, stream=None):
+    """Packed channel packets decoded into ONE dense byte string by a caller who does not know their sizes:
+    decompressed_sizes_packed() -- a packet's size does not depend on its channel's history --, offsets_from_sizes(), one host read
+    -- the total, and the first packet that does not end in its end marker --, one allocation of exactly the total,
+    decompress_channels_burst_packed() on ``states``.  Returns (dense uint8 [total], offsets int64 [npackets + 1], status uint8
+    [npackets]); packet b is dense[offsets[b] : offsets[b] + size[b]].  Raises ValueError naming the first packet that does not end
+    in an end marker, before any state is touched."""
+    import torch
+    nb = _packed_input(data, in_off, in_len)
+    if nb == 0:
+        return (torch.empty(0, dtype=torch.uint8, device=data.device), torch.zeros(1, dtype=torch.int64, device=data.device),
+                torch.empty(0, dtype=torch.uint8, device=data.device))
+    size, status = decompressed_sizes_packed(data, in_off, in_len, None, stream=stream)
+    offsets = offsets_from_sizes(size, align, stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        bad = status != STATUS_END_MARKER
+        first = bad.to(torch.uint8).argmax()
+        top = torch.stack([offsets[nb], bad.any().to(torch.int64), first.to(torch.int64), status[first].to(torch.int64)]).cpu()   # the one host read
+        del bad, first
+    total, any_bad, first_bad, its_status = (int(v) for v in top)
+    del top
+    if any_bad:
+        raise ValueError(f"decompress_channels_dense: packet {first_bad} does not end in an end marker (status 0x{its_status:02x})")
+    dense = torch.empty(total, dtype=torch.uint8, device=data.device)
+    decompress_channels_burst_packed(data, in_off, channels, states, dense, offsets, in_len=in_len, out_len=size, status=status,
+                                     stream=stream)
+    return dense, offsets, status
 
 
 def _occurrence_rank(channels) -> np.ndarray:

@@ -129,6 +129,13 @@ __device__ __forceinline__ uint4 dec_ring_load16(const uint8_t *ring8, uint32_t 
                       __builtin_amdgcn_alignbyte(v[3], v[2], s), __builtin_amdgcn_alignbyte(v[4], v[3], s));
 }
 
+// (RUN) window position `start` + i, for i up to kDecRing
+__device__ __forceinline__ uint32_t dec_ring_at(uint32_t start, uint32_t i)
+{
+    const uint32_t r = start + i;
+    return r >= kDecRing ? r - kDecRing : r;
+}
+
 // PACKED (kernels/decompress_packed.inc; DESIGN.md 3.14): stream b lies at in + in_off[b] -- in_len[b] bytes, or up to
 // in_off[b + 1] without lengths -- and decodes to out + out_off[b] with out_off[b + 1] - out_off[b] bytes of room.
 struct DecPacked {
@@ -159,6 +166,31 @@ __device__ __forceinline__ bool dec_packed_entry(const DecPacked &pk, const uint
     return ok;
 }
 
+// (PACKED) the wavefront's input extent, from every group's first lane, as text for the two places of the decoder that need it (once
+// per wavefront; RUN: once per trip): pk_lo = the lowest first word of the streams that have bytes (`act`; src and n are theirs),
+// pk_rel = how far behind it this lane's stream's first word lies, pk_extent = where the last of them ends from there, pk_fits = that
+// is a 32-bit extent.  No stream has bytes: an empty extent at 0, nothing is read.  (A function gives the kernels of
+// kernels/decompress_packed.inc other instructions in the turn-taking path: profiles/r19/README.md.)
+#define LZS_DEC_PACKED_EXTENT(act_) \
+        const bool act = (act_); \
+        const uint64_t first = (uint64_t)(uintptr_t)src & ~(uint64_t)3; \
+        uint64_t lo = ~0ull, hi = 0; \
+        _Pragma("unroll") \
+        for (uint32_t gg = 0; gg < kDecGroups; gg++) { \
+            const int at = (int)(gg * kDecLanes); \
+            const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)(act ? 1u : 0u), at); \
+            const uint64_t f = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(first >> 32), at) << 32) | \
+                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at); \
+            const uint64_t e = f + (uint32_t)__builtin_amdgcn_readlane((int)(((uint32_t)(uintptr_t)src & 3u) + n), at);   /* (3 + LZS_BLOCK_MAX fits) */ \
+            if (a != 0u && f < lo) lo = f; \
+            if (a != 0u && e > hi) hi = e; \
+        } \
+        if (hi == 0) lo = 0;                                       /* (no stream has bytes: an empty extent, nothing is read) */ \
+        pk_lo = lo; \
+        pk_fits = hi - lo <= 0xFFFF0000ull; \
+        pk_rel = act ? (uint32_t)(first - lo) : 0u; \
+        pk_extent = (uint32_t)(hi - lo);
+
 // The decoder.  Its forms, picked per wavefront by what its streams' lengths say about them (the kernels below); a wavefront never
 // changes form on the way:
 // TWO: a second token in the same trip where that is possible.  Text is mostly short matches (3.4 bytes a token: one token a
@@ -184,7 +216,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
                                       DecPacked pk = DecPacked())
 {
     static_assert(CHAN || !RUN, "a run is a channel's");
-    static_assert(!PACKED || (!RUN && !CONCAT), "packed streams are single blocks or single packets");
+    static_assert(!PACKED || !CONCAT, "packed streams are single blocks, single packets or the packets of a run");
     const uint32_t lane = threadIdx.x;
     const uint32_t g = lane / kDecLanes, j = lane % kDecLanes;
     const uint32_t b = blockIdx.x * per_wave + g;                  // per_wave: kDecGroups, or 1 (see the launcher)
@@ -199,7 +231,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
     uint64_t pk_from = 0, pk_to = 0;                               // PACKED: the entry's offsets, its length and its room
     uint32_t pk_n = 0, pk_room = 0;
     bool pk_block = false;
-    if constexpr (PACKED) {
+    if constexpr (PACKED && !RUN) {
         if (b < nblocks) pk_block = dec_packed_entry(pk, in_len, b, pk_from, pk_n, pk_to, pk_room);
     }
     if constexpr (RUN) {
@@ -237,29 +269,12 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
     uint64_t pk_lo = 0;
     uint32_t pk_rel = 0, pk_extent = 0;
     bool pk_fits = true;
-    if constexpr (PACKED) {
+    if constexpr (PACKED && !RUN) {
         if (b < nblocks && !live && j == 0u) {
             out_len[b] = 0;
             if constexpr (CHAN) { if (ch.status) ch.status[b] = 0x10u; }
         }
-        const bool act = live && n != 0u;
-        const uint64_t first = (uint64_t)(uintptr_t)src & ~(uint64_t)3;
-        uint64_t lo = ~0ull, hi = 0;
-#pragma unroll
-        for (uint32_t gg = 0; gg < kDecGroups; gg++) {
-            const int at = (int)(gg * kDecLanes);
-            const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)(act ? 1u : 0u), at);
-            const uint64_t f = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(first >> 32), at) << 32) |
-                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at);
-            const uint64_t e = f + (uint32_t)__builtin_amdgcn_readlane((int)(((uint32_t)(uintptr_t)src & 3u) + n), at);   // (3 + LZS_BLOCK_MAX fits)
-            if (a != 0u && f < lo) lo = f;
-            if (a != 0u && e > hi) hi = e;
-        }
-        if (hi == 0) lo = 0;                                       // (no stream has bytes: an empty extent, nothing is read)
-        pk_lo = lo;
-        pk_fits = hi - lo <= 0xFFFF0000ull;
-        pk_rel = act ? (uint32_t)(first - lo) : 0u;
-        pk_extent = (uint32_t)(hi - lo);
+        LZS_DEC_PACKED_EXTENT(live && n != 0u)
     }
     const bool live_all = live;
     if constexpr (RUN) {                                           // a run that is not decoded: every packet of it is an ERROR
@@ -289,8 +304,40 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
     uint32_t run_pos = 0;                                          // (RUN) the window position after the packets so far
     uint32_t produced = 0;                                         // (RUN) output of the run so far
     uint32_t pb = b;                                               // the packet
+    // RUN && PACKED (lzs_decompress_runs_packed_grp_kernel; DESIGN.md 3.16): the packets of a trip are entries of the offset
+    // arrays, and what PACKED decides once per wavefront is decided per trip -- the entries that are not blocks (ERROR, length 0,
+    // nothing read or written, the window as it was), the extent, and where that is no 32-bit extent the groups' turns: trip rk
+    // is then kDecGroups passes of this loop, group `turn` alone in each.
+    uint32_t rk = 0, turn = 0, tk = 0;
+    bool any_block = false;                                        // (RUN && PACKED) some packet of the run was a block
     for (uint32_t k = 0;; k++) {
-        if constexpr (PACKED) {
+        if constexpr (RUN && PACKED) {
+            if (turn == 0u) {
+                const uint32_t at = r_at + rk;
+                const bool here = live_run && at < r_end;
+                if (__builtin_amdgcn_ballot_w64(here) == 0ull) break;
+                pb = here ? ch.sidx[at] : 0u;
+                pk_block = here && dec_packed_entry(pk, in_len, pb, pk_from, pk_n, pk_to, pk_room);
+                if (here && !pk_block && j == 0u) {
+                    out_len[pb] = 0;
+                    if (ch.status) ch.status[pb] = 0x10u;
+                }
+                if (!pk_block) { pk_from = 0; pk_to = 0; pk_n = 0u; pk_room = 0u; }
+                any_block = any_block || pk_block;
+                src = in + pk_from;
+                dst = out + pk_to;
+                dst16 = ((uintptr_t)dst & 15u) == 0;
+                n = pk_n;
+                LZS_DEC_PACKED_EXTENT(pk_block && pk_n != 0u)
+            }
+            tk = turn;
+            live = pk_block && (pk_fits || g == tk);
+            if (pk_fits || tk + 1u == kDecGroups) { rk++; turn = 0u; } else turn = tk + 1u;
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
+            n = live ? pk_n : 0u;
+            cap = live ? pk_room : 0u;
+        }
+        if constexpr (PACKED && !RUN) {
             if (k > 0u && (pk_fits || k == kDecGroups)) break;
             if (!pk_fits) {                                            // (too far apart: group k alone)
                 live = live_all && g == k;
@@ -299,7 +346,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
                 cap = live ? pk_room : 0u;
             }
         }
-        if constexpr (RUN) {
+        if constexpr (RUN && !PACKED) {
             const uint32_t at = r_at + k;
             live = live_run && at < r_end;
             if (__builtin_amdgcn_ballot_w64(live) == 0ull) break;
@@ -338,8 +385,8 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
                 in_lo = (uintptr_t)pk_lo;
                 wave_end = pk_extent;
                 pk_at = pk_rel;
-            } else {                                                   // group k's stream alone
-                const int at = (int)(k * kDecLanes);
+            } else {                                                   // group k's stream alone (RUN: group tk's)
+                const int at = (int)(((RUN && PACKED) ? tk : k) * kDecLanes);
                 const uintptr_t first = (uintptr_t)src & ~(uintptr_t)3;
                 in_lo = (uintptr_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)first >> 32), at) << 32) |
                                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, at));
@@ -429,7 +476,10 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
         uint32_t head_left = head;
         uint32_t count = 0, flushed = head, off = 0;
         uint32_t m_ext = 0;                                            // "a length nibble follows", as a mask
-        uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? run_pos : head;  // count and flushed modulo kDecRing
+        // (RUN: the packet's output starts at window position run_pos, its head bytes lie from there on)
+        const uint32_t head_pos = (RUN && kPackedHead) ? dec_ring_at(run_pos, head) : 0u;
+        uint32_t cpos = RUN ? run_pos : 0u, fpos = RUN ? (kPackedHead ? head_pos : run_pos) : head;  // count and flushed modulo kDecRing
+        const uint32_t fpos0 = cpos;                                   // (where the packet's output starts in the window)
         uint32_t m_done = live ? 0u : ~0u;                             // the stream has stopped, as a mask
         uint32_t m_eos = 0u;                                           // (CHAN) ... at an end marker
         uint32_t m_cut = 0u;                                           // (CHAN) a copy lost bytes to the room: no end marker counts after it
@@ -649,7 +699,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
             if (__builtin_amdgcn_ballot_w64(due) != 0ull) {
                 if (due) {
                     if constexpr (kPackedHead) {                       // (the first drain: the window has not wrapped yet)
-                        for (uint32_t i = j; i < head_left; i += kDecLanes) dst[i] = ring8[i];
+                        for (uint32_t i = j; i < head_left; i += kDecLanes) dst[i] = ring8[RUN ? dec_ring_at(fpos0, i) : i];
                         head_left = 0;
                     }
 #pragma unroll
@@ -674,7 +724,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
         }
 
         if constexpr (kPackedHead) {                                   // (no drain took them: the window has not wrapped)
-            for (uint32_t i = j; i < (head_left < count ? head_left : count); i += kDecLanes) dst[i] = ring8[i];
+            for (uint32_t i = j; i < (head_left < count ? head_left : count); i += kDecLanes) dst[i] = ring8[RUN ? dec_ring_at(fpos0, i) : i];
         }
         for (uint32_t i = flushed + j; i < count; i += kDecLanes) {
             uint32_t r = fpos + (i - flushed);
@@ -703,9 +753,10 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
         }
         if constexpr (!RUN && !PACKED) break;
     }
-    // (RUN) the run's history goes back once, at its end
+    // (RUN) the run's history goes back once, at its end (PACKED: not if no packet of the run was a block -- the slot stays as it is,
+    // byte for byte, as after the packed calls rank by rank, which look at no slot for such entries)
     if constexpr (RUN) {
-        if (live_run) {
+        if (live_run && (!PACKED || any_block)) {
             const uint32_t H = min(hlen + produced, kWindow);
             dec_put_history(cst, ring8, run_pos, H, j);
             if (j == 0u) *reinterpret_cast<uint32_t *>(cst) = H;

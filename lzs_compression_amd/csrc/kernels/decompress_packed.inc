@@ -39,6 +39,44 @@ void lzs_decompress_packed_grp_kernel(uint8_t *__restrict__ out, const uint64_t 
     else           lzs_decompress_blocks_grp<false, false, false, CHAN, false, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nblocks, 0u, kDecGroups, ch, pk);
 }
 
+// Packed bursts (include/lzs/lzs_channels.h, lzs_decompress_channels_burst_packed_device; DESIGN.md 3.16): lzs_decompress_runs_grp_kernel
+// with every packet's place, length and room taken from the offset arrays -- RUN and PACKED together.  Eight runs to a wavefront
+// always: where the packets of one trip lie is only known to the decoder, trip by trip.  room_ends[i] = the sum of the rooms of the
+// packets at sorted positions 0 .. i (an entry that is not a block has none): a run's rooms are a difference of two of them, which
+// gives the form as lzs_decompress_packed_grp_kernel picks it.
+__global__ __launch_bounds__(64)
+void lzs_decompress_runs_packed_grp_kernel(uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off,
+                                           uint32_t *__restrict__ out_len,
+                                           const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                           const uint32_t *__restrict__ in_len, const uint64_t *__restrict__ room_ends,
+                                           const uint32_t *__restrict__ run_key, const uint32_t *__restrict__ run_at,
+                                           const uint32_t *__restrict__ run_end, const uint32_t *__restrict__ skey,
+                                           const uint32_t *__restrict__ sidx, uint32_t nchannels, uint8_t *__restrict__ states,
+                                           uint8_t *__restrict__ status, uint32_t nruns)
+{
+    __shared__ DecGroupLds L;
+    uint64_t total = 0, full = 0;
+    const uint32_t b0 = blockIdx.x * kDecGroups;
+    if (b0 >= nruns || run_key[b0] == 0u) return;                 // (runs are sorted by weight: none from here on)
+    for (uint32_t g = 0; g < kDecGroups && b0 + g < nruns; g++) {
+        const uint32_t w = run_key[b0 + g];                        // 1 + the run's compressed bytes (saturated), 0: no run
+        if (w == 0u) break;
+        const uint32_t at = run_at[b0 + g];
+        total += w - 1u;
+        full += room_ends[run_end[at] - 1u] - (at ? room_ends[at - 1u] : 0u);
+    }
+    const bool two = uniform((4ull * total > full && 10ull * total < 9ull * full) ? 1u : 0u) != 0u;
+    const bool wide = uniform(10ull * total >= 9ull * full ? 1u : 0u) != 0u;
+    DecPacked pk;
+    pk.in_off = in_off; pk.out_off = out_off;
+    DecChan ch;
+    ch.states = states; ch.status = status;
+    ch.run_key = run_key; ch.run_at = run_at; ch.run_end = run_end; ch.skey = skey; ch.sidx = sidx; ch.nchannels = nchannels;
+    if (two)       lzs_decompress_blocks_grp<true, false, false, true, true, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nruns, 0u, kDecGroups, ch, pk);
+    else if (wide) lzs_decompress_blocks_grp<false, true, false, true, true, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nruns, 0u, kDecGroups, ch, pk);
+    else           lzs_decompress_blocks_grp<false, false, false, true, true, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nruns, 0u, kDecGroups, ch, pk);
+}
+
 // offsets[0] = 0, offsets[b + 1] = offsets[b] + size[b] rounded up to a multiple of pad + 1 (a power of two): lzs_scan_lengths_kernel
 // with the rounding, for lzs_offsets_from_sizes_device.
 __global__ __launch_bounds__(1024)

@@ -56,10 +56,6 @@ size_t lzs_channels_burst_split_work_bytes(size_t npackets, size_t nchannels, si
     return base + 2u * n * cap;
 }
 
-/* Runs of at least this many compressed bytes are split over the device where the work area allows it (DESIGN.md 3.12 has the
- * sweep: the crossover of both routes on queues with one long run); LZS_BURST_SPLIT_MIN overrides it. */
-#define BURST_SPLIT_MIN_DEFAULT 8192u
-
 /* Many packets per channel (lzs_channels_burst.hip): the checks of device_channels, and those of the ids and the work area. */
 static int device_burst(const char *who, int decompress, void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
                         const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len, const uint32_t *d_channel,

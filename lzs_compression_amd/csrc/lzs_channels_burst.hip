@@ -12,6 +12,10 @@
 // work area that has room for an origin per output byte the long runs are split instead: all their packets parsed at once,
 // what they copy from each other resolved per run afterwards (lzs_burst_parse_kernel, lzs_burst_resolve_kernel).
 //
+// Packed bursts (lzs_*_channels_burst_packed_device): the same with every packet and its room addressed by offset
+// arrays on the device.  The kernels that look at a packet's bytes exist in both forms from one body each (BurstIo, PACKED); the
+// compressor is lzs_hip_launch_compress_channels_packed, the run decoder lzs_hip_launch_decompress_runs_packed.
+//
 // (<cstring> and the HIP runtime before rocPRIM: its texture cache iterator uses memset in host code.)
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -21,13 +25,75 @@
 
 namespace {
 
-constexpr uint32_t kStateBytes = 2112u, kHistAt = 64u, kWindow = 2047u;   // a channel slot (lzs_channels.h)
+#include "kernels/common.inc"                  // kWindow, packed_entry
+
+constexpr uint32_t kStateBytes = 2112u, kHistAt = 64u;                    // a channel slot (lzs_channels.h)
 constexpr size_t kAlign = 256;
 constexpr size_t kSortSpareBytes = 65536;      // rocPRIM's temporary storage: this + 8 bytes a packet (checked at every call)
 
 __device__ __forceinline__ uint32_t burst_len(const uint32_t *in_len, uint32_t in_len_uniform, uint32_t p)
 {
     return in_len ? in_len[p] : in_len_uniform;
+}
+
+// Where the packets lie and where their output goes: slots a stride apart with one capacity (lzs_*_channels_burst_device), or --
+// PACKED -- entries of offset arrays, the rule of packed_entry (lzs_*_channels_burst_packed_device).  An entry that is not a block
+// has length 0 and room 0.  room_ends (PACKED, decompression): the inclusive scan of the rooms by sorted position -- where each
+// packet's origins end in the work area (split route), and a run's rooms as a difference.
+struct BurstIo {
+    const uint8_t *in;
+    uint8_t *out;
+    size_t in_stride, out_stride;
+    uint32_t out_cap;
+    const uint32_t *in_len;
+    uint32_t in_len_uniform;
+    const uint64_t *in_off, *out_off, *room_ends;
+};
+
+struct BurstPacket {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t n, cap;
+    bool block;
+};
+
+template <bool PACKED>
+__device__ __forceinline__ BurstPacket burst_packet(const BurstIo &io, uint32_t p)
+{
+    BurstPacket k;
+    if constexpr (PACKED) {
+        uint64_t from, to;
+        k.block = packed_entry(io.in_off, io.in_len, io.out_off, p, from, k.n, to, k.cap);
+        k.src = io.in + (k.block ? from : 0u);
+        k.dst = io.out + (k.block ? to : 0u);
+    } else {
+        k.block = true;
+        k.n = burst_len(io.in_len, io.in_len_uniform, p);
+        k.cap = io.out_cap;
+        k.src = io.in + (size_t)p * io.in_stride;
+        k.dst = io.out + (size_t)p * io.out_stride;
+    }
+    return k;
+}
+
+// where the origins of the packet at sorted position i begin (split route)
+template <bool PACKED>
+__device__ __forceinline__ size_t burst_origin_at(const BurstIo &io, uint32_t i)
+{
+    if constexpr (PACKED) return i ? (size_t)io.room_ends[i - 1u] : (size_t)0;
+    else return (size_t)i * io.out_cap;
+}
+
+__device__ __forceinline__ BurstIo burst_strided(const uint8_t *in, size_t in_stride, const uint32_t *in_len, uint32_t in_len_uniform,
+                                                 uint8_t *out = nullptr, size_t out_stride = 0, uint32_t out_cap = 0)
+{
+    return BurstIo{in, out, in_stride, out_stride, out_cap, in_len, in_len_uniform, nullptr, nullptr, nullptr};
+}
+
+__device__ __forceinline__ BurstIo burst_packed(const uint8_t *in, const uint64_t *in_off, const uint32_t *in_len, uint8_t *out,
+                                                const uint64_t *out_off, const uint64_t *room_ends = nullptr)
+{
+    return BurstIo{in, out, 0, 0, 0u, in_len, 0u, in_off, out_off, room_ends};
 }
 
 // the first sorted position in [0, hi) whose channel is not below `key`
@@ -70,6 +136,18 @@ __global__ __launch_bounds__(256) void lzs_burst_lens_kernel(const uint32_t *__r
     if (i < n) lens[i] = burst_len(in_len, in_len_uniform, sidx[i]);
 }
 
+// (PACKED) the same from the entries -- 0 for one that is not a block --, and rooms[i] (if given) = the packet's room, for room_ends
+__global__ __launch_bounds__(256) void lzs_burst_lens_packed_kernel(const uint32_t *__restrict__ sidx, const uint64_t *__restrict__ in_off,
+                                                                    const uint32_t *__restrict__ in_len, const uint64_t *__restrict__ out_off,
+                                                                    uint64_t *__restrict__ lens, uint64_t *__restrict__ rooms, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const BurstPacket k = burst_packet<true>(burst_packed(nullptr, in_off, in_len, nullptr, out_off), sidx[i]);
+    lens[i] = k.n;
+    if (rooms) rooms[i] = k.cap;
+}
+
 // One workgroup per sorted position i: the history packet p = sidx[i] is compressed with, into work slot p -- the last
 // H <= 2047 bytes of (the channel's slot | the packets at sorted positions [start, i)), where `start` begins the run.  With
 // ends[] the inclusive scan of the lengths, the run's earlier packets are the bytes [ends[start - 1], ends[i - 1]) of one
@@ -82,68 +160,64 @@ __global__ __launch_bounds__(256) void lzs_burst_gather_kernel(const uint8_t *__
                                                                const uint64_t *__restrict__ ends, const uint8_t *__restrict__ states,
                                                                uint32_t nchannels, uint8_t *__restrict__ work_slots)
 {
-    const uint32_t i = blockIdx.x, t = threadIdx.x;
-    const uint32_t key = skey[i], p = sidx[i];
-    uint32_t *const slot = reinterpret_cast<uint32_t *>(work_slots + (size_t)p * kStateBytes);
-    const uint8_t *const st = states + (size_t)(key < nchannels ? key : 0u) * kStateBytes;
-    const uint32_t hl = key < nchannels ? *reinterpret_cast<const uint32_t *>(st) : ~0u;
-    if (hl > kWindow) {
-        if (t == 0) slot[0] = ~0u;
-        return;
-    }
-    const uint32_t start = run_first(skey, i, key);
-    const uint64_t e = i ? ends[i - 1u] : 0u, s = start ? ends[start - 1u] : 0u;
-    const uint32_t hp = (uint32_t)(e - s < kWindow ? e - s : kWindow);     // from the run's earlier packets ...
-    const uint32_t hs = hl < kWindow - hp ? hl : kWindow - hp;              // ... and from the slot, in front of them
-    const uint32_t H = hs + hp;
-    uint32_t w[2] = {0u, 0u};
-    uint32_t q = start;                                                     // the packet that holds the byte, once found
-    bool found = false;
-    for (uint32_t k = 0; k < 8u; k++) {
-        const uint32_t x = 8u * t + k;
-        if (x >= H) break;
-        uint32_t v;
-        if (x < hs) {
-            v = st[kHistAt + hl - hs + x];
-        } else {
-            const uint64_t at = e - hp + (x - hs);                          // its place in the channel's string
-            if (!found) {
-                uint32_t lo = start, hi = i;                                // the first q in [start, i) with ends[q] > at
-                while (lo < hi) {
-                    const uint32_t mid = lo + (hi - lo) / 2u;
-                    if (ends[mid] <= at) lo = mid + 1u; else hi = mid;
-                }
-                q = lo;
-                found = true;
-            }
-            while (ends[q] <= at) q++;
-            const uint32_t pq = sidx[q];
-            const uint64_t begin = ends[q] - burst_len(in_len, in_len_uniform, pq);
-            v = in[(size_t)pq * in_stride + (size_t)(at - begin)];
-        }
-        w[k >> 2] |= v << (8u * (k & 3u));
-    }
-    uint32_t *const hist = slot + kHistAt / 4u;
-    hist[2u * t] = w[0];
-    hist[2u * t + 1u] = w[1];
-    if (t > 0 && t < kHistAt / 4u) slot[t] = 0u;
-    if (t == 0) slot[0] = H;
+#define BURST_LEN(p) burst_len(in_len, in_len_uniform, (p))
+#define BURST_SRC(p) (in + (size_t)(p) * in_stride)
+#include "kernels/burst_gather.inc"
+#undef BURST_LEN
+#undef BURST_SRC
+}
+
+__global__ __launch_bounds__(256) void lzs_burst_gather_packed_kernel(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                                                      const uint32_t *__restrict__ in_len, const uint64_t *__restrict__ out_off,
+                                                                      const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                                                      const uint64_t *__restrict__ ends, const uint8_t *__restrict__ states,
+                                                                      uint32_t nchannels, uint8_t *__restrict__ work_slots)
+{
+    const BurstIo io = burst_packed(in, in_off, in_len, nullptr, out_off);
+#define BURST_LEN(p) burst_packet<true>(io, (p)).n
+#define BURST_SRC(p) burst_packet<true>(io, (p)).src
+#include "kernels/burst_gather.inc"
+#undef BURST_LEN
+#undef BURST_SRC
 }
 
 // One workgroup per sorted position: the last packet of a run in range copies its work slot (the history after it, written by
 // the channel kernel, a packet cut at the capacity included) to its channel.  A slot marked ~0 (not a state) is not copied.
-__global__ __launch_bounds__(128) void lzs_burst_commit_kernel(const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
-                                                               const uint8_t *__restrict__ work_slots, uint32_t nchannels,
-                                                               uint8_t *__restrict__ states, uint32_t n)
+// PACKED: an entry that is not a block leaves its work slot as the gather wrote it -- the history behind the blocks before it --,
+// so the last slot is the run's whatever its last entry is; but a run with no block at all is not committed: its channel's slot
+// stays as it is byte for byte (the packed call looks at no slot for such an entry), not rewritten in canonical form.
+template <bool PACKED>
+__device__ __forceinline__ void burst_commit(const BurstIo &io, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                             const uint8_t *__restrict__ work_slots, uint32_t nchannels,
+                                             uint8_t *__restrict__ states, uint32_t n)
 {
     const uint32_t i = blockIdx.x;
     const uint32_t key = skey[i];
     if (key >= nchannels || (i + 1u < n && skey[i + 1u] == key)) return;
+    if constexpr (PACKED) {
+        for (uint32_t q = i; !burst_packet<true>(io, sidx[q]).block; q--)
+            if (q == 0u || skey[q - 1u] != key) return;
+    }
     const uint32_t *const from = reinterpret_cast<const uint32_t *>(work_slots + (size_t)sidx[i] * kStateBytes);
     if (from[0] > kWindow) return;
     uint32_t *const to = reinterpret_cast<uint32_t *>(states + (size_t)key * kStateBytes);
     for (uint32_t w = threadIdx.x; w < 512u; w += 128u) to[kHistAt / 4u + w] = from[kHistAt / 4u + w];
     if (threadIdx.x == 0) to[0] = from[0];
+}
+
+__global__ __launch_bounds__(128) void lzs_burst_commit_kernel(const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                                               const uint8_t *__restrict__ work_slots, uint32_t nchannels,
+                                                               uint8_t *__restrict__ states, uint32_t n)
+{
+    burst_commit<false>(BurstIo{}, skey, sidx, work_slots, nchannels, states, n);
+}
+
+__global__ __launch_bounds__(128) void lzs_burst_commit_packed_kernel(const uint64_t *__restrict__ in_off, const uint32_t *__restrict__ in_len,
+                                                                      const uint64_t *__restrict__ out_off, const uint32_t *__restrict__ skey,
+                                                                      const uint32_t *__restrict__ sidx, const uint8_t *__restrict__ work_slots,
+                                                                      uint32_t nchannels, uint8_t *__restrict__ states, uint32_t n)
+{
+    burst_commit<true>(burst_packed(nullptr, in_off, in_len, nullptr, out_off), skey, sidx, work_slots, nchannels, states, n);
 }
 
 // For the decoder: at the first sorted position of each run, its weight (1 + its compressed bytes, saturated) and its end;
@@ -180,10 +254,10 @@ __device__ __forceinline__ bool run_is_heavy(uint32_t weight, uint32_t split_min
 // The runs sorted by weight, heaviest first: the heavy ones are a prefix.  *nheavy = its length; light_w / light_at = the
 // tables without it -- the first light run at index 0, zeros behind the last -- for the run decoder, which takes a first
 // weight of 0 in a wavefront for "none from here on".
-__global__ __launch_bounds__(256) void lzs_burst_split_plan_kernel(const uint32_t *__restrict__ weight, const uint32_t *__restrict__ at,
-                                                                   uint32_t split_min, uint32_t *__restrict__ light_w,
-                                                                   uint32_t *__restrict__ light_at, uint32_t *__restrict__ nheavy,
-                                                                   uint32_t n)
+__device__ __forceinline__ void burst_split_plan(const uint32_t *__restrict__ weight, const uint32_t *__restrict__ at,
+                                                 uint32_t split_min, uint32_t *__restrict__ light_w,
+                                                 uint32_t *__restrict__ light_at, uint32_t *__restrict__ nheavy,
+                                                 uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     uint32_t lo = 0, hi = n;                                               // the first run that is not heavy
@@ -198,6 +272,26 @@ __global__ __launch_bounds__(256) void lzs_burst_split_plan_kernel(const uint32_
     light_at[i] = in ? at[i + lo] : 0u;
 }
 
+__global__ __launch_bounds__(256) void lzs_burst_split_plan_kernel(const uint32_t *__restrict__ weight, const uint32_t *__restrict__ at,
+                                                                   uint32_t split_min, uint32_t *__restrict__ light_w,
+                                                                   uint32_t *__restrict__ light_at, uint32_t *__restrict__ nheavy,
+                                                                   uint32_t n)
+{
+    burst_split_plan(weight, at, split_min, light_w, light_at, nheavy, n);
+}
+
+// PACKED: the host does not know the rooms, so whether their origins fit the work area is seen here -- origin_cap 16-bit origins
+// behind the burst part against the sum of the rooms.  If they do not fit no run is heavy (no weight reaches a threshold of ~0):
+// PARSE and RESOLVE return at once and write nothing, the run decoder takes every run.
+__global__ __launch_bounds__(256) void lzs_burst_split_plan_packed_kernel(const uint32_t *__restrict__ weight, const uint32_t *__restrict__ at,
+                                                                          uint32_t split_min, const uint64_t *__restrict__ room_ends,
+                                                                          uint64_t origin_cap, uint32_t *__restrict__ light_w,
+                                                                          uint32_t *__restrict__ light_at, uint32_t *__restrict__ nheavy,
+                                                                          uint32_t n)
+{
+    burst_split_plan(weight, at, room_ends[n - 1u] <= origin_cap ? split_min : ~0u, light_w, light_at, nheavy, n);
+}
+
 // PARSE: one wavefront per sorted position i whose run is heavy.  The tokens are parsed once for the wavefront (all of it
 // wave-uniform: the bit buffer is filled from a 64-byte piece of the packet held a byte a lane, the next piece requested a
 // piece ahead, and bounded by the packet's length), the bytes of a copy are produced a lane each.  The ring keeps the last
@@ -206,6 +300,9 @@ __global__ __launch_bounds__(256) void lzs_burst_split_plan_kernel(const uint32_
 // The rules are those of lzs_decompress_channels_grp_kernel: an end marker needs no room and counts unless a copy was cut
 // at out_cap before it -- also behind the closing length nibble 0 of a copy that filled the output --, a token short of its
 // bits or of any room stops the packet, a long offset of 0 copies nothing and clears the offset.
+// PACKED: the packet, its room (out_cap) and where its origins lie come from the entries; one that is not a block is answered like
+// a slot that is no state, with rec[i] = {0, 1} -- no packet has more open bytes than bytes -- so that RESOLVE knows it from a
+// packet of no bytes.
 __global__ __launch_bounds__(64) void lzs_burst_parse_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
                                                              uint32_t *__restrict__ out_len, const uint8_t *__restrict__ in,
                                                              size_t in_stride, const uint32_t *__restrict__ in_len,
@@ -216,111 +313,52 @@ __global__ __launch_bounds__(64) void lzs_burst_parse_kernel(uint8_t *__restrict
                                                              uint16_t *__restrict__ origins, uint2 *__restrict__ rec,
                                                              const uint32_t *__restrict__ nheavy, uint32_t split_min)
 {
-    __shared__ uint8_t val[kParseRing];
-    __shared__ uint16_t org[kParseRing];
-    if (*nheavy == 0u) return;
-    const uint32_t i = blockIdx.x, lane = threadIdx.x;
-    const uint32_t key = skey[i];
-    const uint32_t start = run_first(skey, i, key);
-    const uint32_t end = run_end[start];
-    const uint64_t bytes = ends[end - 1u] - (start ? ends[start - 1u] : 0u);
-    if (!run_is_heavy((uint32_t)(bytes < 0xFFFFFFFEull ? bytes : 0xFFFFFFFEull) + 1u, split_min)) return;
-    const uint32_t p = sidx[i];
-    const uint32_t hl = key < nchannels ? *reinterpret_cast<const uint32_t *>(states + (size_t)key * kStateBytes) : ~0u;
-    if (hl > kWindow) {                                                    // not a channel, not a state
-        if (lane == 0) {
-            out_len[p] = 0;
-            if (status) status[p] = 0x10u;
-            rec[i] = make_uint2(0u, 0u);
-        }
-        return;
-    }
-    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)burst_len(in_len, in_len_uniform, p));
-    const uint8_t *const src = in + (size_t)p * in_stride;
-    uint8_t *const dst = out + (size_t)p * out_stride;
-    uint16_t *const og = origins + (size_t)i * out_cap;
-    const auto piece = [&](uint32_t k) { const uint32_t x = 64u * k + lane; return x < n ? (uint32_t)src[x] : 0u; };
-    uint32_t cur = piece(0), nxt = piece(1);
-    uint64_t acc = 0;                                                      // the bit buffer, left-aligned
-    uint32_t have = 0, fed = 0;                                            // bits in it; bytes of the packet fed
-    uint32_t count = 0, off = 0, opens = 0;
-    bool ext = false, cut = false, eos = false;
-    for (;;) {
-        while (have <= 56u && fed < n) {
-            const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)cur, (int)(fed & 63u));
-            acc |= (uint64_t)b << (56u - have);
-            have += 8u;
-            fed++;
-            if ((fed & 63u) == 0u) { cur = nxt; nxt = piece((fed >> 6) + 1u); }
-        }
-        // (with fewer than 57 bits in the buffer the packet has no more: `have` is all that is left of it)
-        const uint32_t top = (uint32_t)(acc >> 32);
-        const uint32_t room = out_cap - count;
-        uint32_t need, ncopy;
-        if (ext) {                                                         // a length nibble
-            const uint32_t e = top >> 28;
-            if (!cut && e == 0u && have >= 13u && ((top >> 19) & 0x1FFu) == 0x180u) eos = true;
-            if (have < 4u || room == 0u) break;
-            need = 4u; ncopy = e; ext = e == 15u;
-        } else if ((top >> 31) == 0u) {                                    // a literal
-            if (have < 9u || room == 0u) break;
-            const uint32_t b = (top >> 23) & 0xFFu;
-            if (lane == 0) {
-                val[count & (kParseRing - 1u)] = (uint8_t)b;
-                org[count & (kParseRing - 1u)] = 0;
-                dst[count] = (uint8_t)b;
-                og[count] = 0;
-            }
-            count++;
-            acc <<= 9u; have -= 9u;
-            continue;
-        } else {
-            const bool shrt = ((top >> 30) & 1u) != 0u;
-            const uint32_t used = shrt ? 9u : 13u;
-            const uint32_t o = shrt ? (top >> 23) & 0x7Fu : (top >> 19) & 0x7FFu;
-            if (o == 0u) {
-                if (shrt) {                                                // the end marker
-                    if (have >= 9u && !cut) eos = true;
-                    break;
-                }
-                if (have < 13u || room == 0u) break;                       // long offset 0
-                off = 0u;
-                acc <<= 13u; have -= 13u;
-                continue;
-            }
-            const uint32_t code = (top << used) >> 28;
-            const uint32_t len = code < 12u ? (code >> 2) + 2u : code - 7u;
-            need = used + (code < 12u ? 2u : 4u);
-            if (have < need || room == 0u) break;
-            off = o; ncopy = len; ext = len == 8u;
-        }
-        acc <<= need; have -= need;
-        const uint32_t m = ncopy < room ? ncopy : room;                    // at most 15
-        if (m < ncopy) cut = true;
-        if (m != 0u) {
-            // byte x of the copy is byte x mod off of it (x < 16: the quotient by a float, half a unit from any doubt)
-            const uint32_t x = lane & 15u;
-            const uint32_t k = x - off * (uint32_t)(((float)x + 0.5f) * __frcp_rn((float)off));
-            const int64_t s = (int64_t)count + k - off;                    // its source in the packet; < 0: in front of it
-            uint32_t v = 0, g = 0;
-            if (lane < m) {
-                if (s >= 0) { v = val[(uint32_t)s & (kParseRing - 1u)]; g = org[(uint32_t)s & (kParseRing - 1u)]; }
-                else g = kOpen | (uint32_t)(-s);
-                const uint32_t w = count + lane;
-                val[w & (kParseRing - 1u)] = (uint8_t)v;
-                org[w & (kParseRing - 1u)] = (uint16_t)g;
-                dst[w] = (uint8_t)v;
-                og[w] = (uint16_t)g;
-            }
-            opens += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(g != 0u));
-            count += m;
-        }
-    }
-    if (lane == 0) {
-        out_len[p] = count;
-        if (status) status[p] = (uint8_t)(eos ? 0x04u : (count >= out_cap ? 0x08u : 0x03u));
-        rec[i] = make_uint2(count, opens);
-    }
+#define BURST_PACKET(p)
+#define BURST_LEN(p) burst_len(in_len, in_len_uniform, (p))
+#define BURST_SRC(p) (in + (size_t)(p) * in_stride)
+#define BURST_DST(p) (out + (size_t)(p) * out_stride)
+#define BURST_ORIGIN_AT(i) ((size_t)(i) * out_cap)
+#include "kernels/burst_parse.inc"
+#undef BURST_PACKET
+#undef BURST_LEN
+#undef BURST_SRC
+#undef BURST_DST
+#undef BURST_ORIGIN_AT
+}
+
+__global__ __launch_bounds__(64) void lzs_burst_parse_packed_kernel(uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off,
+                                                                    uint32_t *__restrict__ out_len, const uint8_t *__restrict__ in,
+                                                                    const uint64_t *__restrict__ in_off, const uint32_t *__restrict__ in_len,
+                                                                    const uint64_t *__restrict__ room_ends, const uint32_t *__restrict__ skey,
+                                                                    const uint32_t *__restrict__ sidx, const uint64_t *__restrict__ ends,
+                                                                    const uint32_t *__restrict__ run_end, const uint8_t *__restrict__ states,
+                                                                    uint32_t nchannels, uint8_t *__restrict__ status,
+                                                                    uint16_t *__restrict__ origins, uint2 *__restrict__ rec,
+                                                                    const uint32_t *__restrict__ nheavy, uint32_t split_min)
+{
+    const BurstIo io = burst_packed(in, in_off, in_len, out, out_off, room_ends);
+    // (one that is not a block: nothing of it is read or written)
+#define BURST_PACKET(p) \
+    const BurstPacket pkt = burst_packet<true>(io, (p)); \
+    if (!pkt.block) { \
+        if (lane == 0) { \
+            out_len[p] = 0; \
+            if (status) status[p] = 0x10u; \
+            rec[i] = make_uint2(0u, 1u); \
+        } \
+        return; \
+    } \
+    const uint32_t out_cap = (uint32_t)__builtin_amdgcn_readfirstlane((int)pkt.cap);
+#define BURST_LEN(p) pkt.n
+#define BURST_SRC(p) pkt.src
+#define BURST_DST(p) pkt.dst
+#define BURST_ORIGIN_AT(i) burst_origin_at<true>(io, (i))
+#include "kernels/burst_parse.inc"
+#undef BURST_PACKET
+#undef BURST_LEN
+#undef BURST_SRC
+#undef BURST_DST
+#undef BURST_ORIGIN_AT
 }
 
 // RESOLVE: one workgroup per heavy run walks its packets in order with the run's last 2047 final bytes in an LDS ring --
@@ -332,12 +370,14 @@ __global__ __launch_bounds__(64) void lzs_burst_parse_kernel(uint8_t *__restrict
 // (packet, length, open bytes) of 256 packets at a time go through LDS half a table ahead.  A longer packet is gathered
 // first, its last 2048 bytes kept aside, and appended after a barrier.  At the end the ring's last min(2047, history +
 // produced) bytes are the channel's new history (COMMIT).  Runs that are not a state's were answered by PARSE: not touched.
-__global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
-                                                                const uint32_t *__restrict__ run_at, const uint32_t *__restrict__ run_end,
-                                                                const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
-                                                                uint8_t *__restrict__ states, uint32_t nchannels,
-                                                                const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
-                                                                const uint32_t *__restrict__ nheavy)
+// PACKED: a packet's output and its origins are found through the entries, and a run none of whose entries is a block (rec = {0, 1}
+// throughout) is not committed: its slot stays as it is byte for byte.
+template <bool PACKED>
+__device__ __forceinline__ void burst_resolve(const BurstIo &io, const uint32_t *__restrict__ run_at, const uint32_t *__restrict__ run_end,
+                                              const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                              uint8_t *__restrict__ states, uint32_t nchannels,
+                                              const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
+                                              const uint32_t *__restrict__ nheavy)
 {
     __shared__ __attribute__((aligned(16))) uint8_t ring[kResolveRing];
     __shared__ uint8_t aside[kResolveFast];
@@ -351,9 +391,13 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
     if (hl > kWindow) return;
     const uint32_t npk = end - at;
     // the table of packet k of the run: entry k mod 512
+    bool any_block = false;                                                // (PACKED) of the entries this thread has loaded
     const auto meta_load = [&](uint32_t k0, uint32_t &mp, uint2 &mr) {
         mp = 0u; mr = make_uint2(0u, 0u);
-        if (k0 + t < npk) { mp = sidx[at + k0 + t]; mr = rec[at + k0 + t]; }
+        if (k0 + t < npk) {
+            mp = sidx[at + k0 + t]; mr = rec[at + k0 + t];
+            if constexpr (PACKED) any_block = any_block || mr.x != 0u || mr.y == 0u;
+        }
     };
     const auto meta_store = [&](uint32_t k0, uint32_t mp, uint2 mr) {
         const uint32_t e = (k0 + t) & (2u * kResolveMeta - 1u);
@@ -377,8 +421,8 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
         const uint32_t e = k & (2u * kResolveMeta - 1u);
         const uint32_t len = k < npk ? meta_len[e] : 0u;
         const bool open = meta_open[e] != 0u;
-        const uint8_t *const d = out + (size_t)meta_p[e] * out_stride;
-        const uint16_t *const o = origins + (size_t)(at + k) * out_cap;
+        const uint8_t *const d = burst_packet<PACKED>(io, meta_p[e]).dst;
+        const uint16_t *const o = origins + burst_origin_at<PACKED>(io, PACKED && k >= npk ? at : at + k);   // (room_ends has no entry past the run)
 #pragma unroll
         for (uint32_t s = 0; s < 8u; s++) {
             const uint32_t j = t + 256u * s;
@@ -399,7 +443,7 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
             if (k >= npk) break;
             const uint32_t e = k & (2u * kResolveMeta - 1u);
             const uint32_t len = meta_len[e];
-            uint8_t *const d = out + (size_t)meta_p[e] * out_stride;
+            uint8_t *const d = burst_packet<PACKED>(io, meta_p[e]).dst;
             if (len <= kResolveFast) {
 #pragma unroll
                 for (uint32_t s = 0; s < 8u; s++) {
@@ -415,7 +459,7 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
                 }
             } else {
                 const bool open = meta_open[e] != 0u;
-                const uint16_t *const o = origins + (size_t)(at + k) * out_cap;
+                const uint16_t *const o = origins + burst_origin_at<PACKED>(io, at + k);
                 for (uint32_t j = t; j < len; j += 256u) {
                     uint32_t b = d[j];
                     const uint32_t gg = open ? o[j] : 0u;
@@ -442,6 +486,9 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
         }
     }
     // COMMIT: hist[0, H) = the last H bytes of the run's string, zeros behind them, the length in front
+    if constexpr (PACKED) {
+        if (__syncthreads_or(any_block ? 1 : 0) == 0) return;
+    }
     const uint32_t H = hl + produced < kWindow ? hl + produced : kWindow;
     uint32_t *const hist = reinterpret_cast<uint32_t *>(st + kHistAt);
     for (uint32_t w = t; w < 512u; w += 256u) {
@@ -455,15 +502,41 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
     if (t == 0) *reinterpret_cast<uint32_t *>(st) = H;
 }
 
+__global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
+                                                                const uint32_t *__restrict__ run_at, const uint32_t *__restrict__ run_end,
+                                                                const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                                                uint8_t *__restrict__ states, uint32_t nchannels,
+                                                                const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
+                                                                const uint32_t *__restrict__ nheavy)
+{
+    burst_resolve<false>(burst_strided(nullptr, 0, nullptr, 0u, out, out_stride, out_cap), run_at, run_end, skey, sidx, states, nchannels,
+                         origins, rec, nheavy);
+}
+
+__global__ __launch_bounds__(256) void lzs_burst_resolve_packed_kernel(uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off,
+                                                                       const uint64_t *__restrict__ in_off, const uint32_t *__restrict__ in_len,
+                                                                       const uint64_t *__restrict__ room_ends,
+                                                                       const uint32_t *__restrict__ run_at, const uint32_t *__restrict__ run_end,
+                                                                       const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                                                       uint8_t *__restrict__ states, uint32_t nchannels,
+                                                                       const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
+                                                                       const uint32_t *__restrict__ nheavy)
+{
+    burst_resolve<true>(burst_packed(nullptr, in_off, in_len, out, out_off, room_ends), run_at, run_end, skey, sidx, states, nchannels,
+                        origins, rec, nheavy);
+}
+
 // The work area, in this order, each part 256-byte aligned: npackets channel slots (compression), sort keys and values twice
 // each (the sort's double buffers), the lengths and their scan (64 bit), the runs' weights and positions twice each and their
 // ends (decompression), rocPRIM's temporary storage.
 // A split decode keeps its tables where compression has its slots -- the light runs' weights and positions, {length, open
 // bytes} of every packet by sorted position, the number of heavy runs: 16 bytes a packet -- and npackets * out_cap 16-bit
 // origins, packet by packet in sorted order, behind everything else (`total` is where): the larger work area's extra part.
+// A packed decode has the rooms by sorted position and their scan there as well (16 bytes a packet more), and its origins lie
+// room by room: origin_bytes / 2 of them, as many as the caller's work area holds behind `total`.
 struct BurstLayout {
     size_t slots, key[2], val[2], lens, ends, weight[2], at[2], run_end, temp, temp_bytes, total;
-    size_t light_w, light_at, rec, nheavy, origins;
+    size_t light_w, light_at, rec, nheavy, rooms, room_ends, origins;
 };
 
 size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
@@ -489,34 +562,43 @@ BurstLayout burst_layout(size_t n)
     L.light_w = take(4 * n);
     L.light_at = take(4 * n);
     L.rec = take(8 * n);
-    static_assert(kStateBytes >= 4 * kAlign + 16 + kAlign, "the split decode's tables fit the slots of one packet and more");
+    L.rooms = take(8 * n);
+    L.room_ends = take(8 * n);
+    static_assert(kStateBytes >= 6 * kAlign + 32 + kAlign, "the decoders' tables fit the slots of one packet and more");
     L.origins = L.total;
     return L;
 }
 
-}  // namespace
-
-extern "C" size_t lzs_hip_burst_work_bytes(size_t npackets)
-{
-    return burst_layout(npackets).total;
-}
-
-
 #define BURST_TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
 
-extern "C" int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
-                             const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
-                             const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
-                             void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream_)
+// What a call gives: the packets strided (off: nullptr) or packed.
+struct BurstCall {
+    void *d_out;
+    const void *d_in;
+    size_t out_stride, in_stride;
+    uint32_t out_cap, in_len;
+    const uint32_t *d_in_len;
+    const uint64_t *d_in_off, *d_out_off;
+    bool packed() const { return d_in_off != nullptr; }
+};
+
+// One burst: the grouping, then the kernels of the direction.  split (decompression): the long runs by PARSE and RESOLVE, with
+// origin_cap 16-bit origins behind the burst part of the work area (PACKED; the strided call's host code knows that they fit).
+int burst(int decompress, const BurstCall &c, uint32_t *d_out_len, const uint32_t *d_channel, void *d_states, uint32_t nchannels,
+          uint8_t *d_status, void *d_work, uint32_t npackets, int split, uint64_t origin_cap, uint32_t split_min, void *stream_)
 {
     if (npackets == 0) return 0;
     const hipStream_t stream = (hipStream_t)stream_;
     const BurstLayout L = burst_layout(npackets);
     uint8_t *const W = static_cast<uint8_t *>(d_work);
     const auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t *>(W + at); };
-    uint64_t *const lens = reinterpret_cast<uint64_t *>(W + L.lens), *const ends = reinterpret_cast<uint64_t *>(W + L.ends);
+    const auto u64 = [&](size_t at) { return reinterpret_cast<uint64_t *>(W + at); };
+    uint64_t *const lens = u64(L.lens), *const ends = u64(L.ends);
+    uint64_t *const rooms = u64(L.rooms), *const room_ends = u64(L.room_ends);     // (packed decompression)
     void *const temp = W + L.temp;
     const uint32_t grid = (npackets + 255u) / 256u;
+    const uint8_t *const in = (const uint8_t *)c.d_in;
+    uint8_t *const out = (uint8_t *)c.d_out;
 
     // ---- the runs: a stable sort by channel over the bits a channel id in range (or nchannels) can have
     hipLaunchKernelGGL(lzs_burst_keys_kernel, dim3(grid), dim3(256), 0, stream, d_channel, nchannels, u32(L.key[0]), u32(L.val[0]),
@@ -532,22 +614,39 @@ extern "C" int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uin
     rocprim::double_buffer<uint32_t> keys(u32(L.key[0]), u32(L.key[1])), vals(u32(L.val[0]), u32(L.val[1]));
     BURST_TRY(rocprim::radix_sort_pairs(temp, need, keys, vals, npackets, 0u, bits, stream));
     const uint32_t *const skey = keys.current(), *const sidx = vals.current();
-    // ---- where each packet ends in its channel's string of packets (a scan over all runs: the differences are what counts)
-    hipLaunchKernelGGL(lzs_burst_lens_kernel, dim3(grid), dim3(256), 0, stream, sidx, d_in_len, in_len, lens, npackets);
+    // ---- where each packet ends in its channel's string of packets (a scan over all runs: the differences are what counts);
+    // packed decompression: the same of the rooms
+    if (c.packed())
+        hipLaunchKernelGGL(lzs_burst_lens_packed_kernel, dim3(grid), dim3(256), 0, stream, sidx, c.d_in_off, c.d_in_len, c.d_out_off, lens,
+                           decompress ? rooms : (uint64_t *)nullptr, npackets);
+    else
+        hipLaunchKernelGGL(lzs_burst_lens_kernel, dim3(grid), dim3(256), 0, stream, sidx, c.d_in_len, c.in_len, lens, npackets);
     BURST_TRY(rocprim::inclusive_scan(nullptr, need, lens, ends, (size_t)npackets, rocprim::plus<uint64_t>(), stream));
     if (need > L.temp_bytes) return (int)hipErrorInvalidValue;
     BURST_TRY(rocprim::inclusive_scan(temp, need, lens, ends, (size_t)npackets, rocprim::plus<uint64_t>(), stream));
+    if (c.packed() && decompress)
+        BURST_TRY(rocprim::inclusive_scan(temp, need, rooms, room_ends, (size_t)npackets, rocprim::plus<uint64_t>(), stream));
 
     if (!decompress) {
         uint8_t *const slots = W + L.slots;
-        hipLaunchKernelGGL(lzs_burst_gather_kernel, dim3(npackets), dim3(256), 0, stream, (const uint8_t *)d_in, in_stride, d_in_len,
-                           in_len, skey, sidx, (const uint64_t *)ends, (const uint8_t *)d_states, nchannels, slots);
+        if (c.packed())
+            hipLaunchKernelGGL(lzs_burst_gather_packed_kernel, dim3(npackets), dim3(256), 0, stream, in, c.d_in_off, c.d_in_len, c.d_out_off,
+                               skey, sidx, (const uint64_t *)ends, (const uint8_t *)d_states, nchannels, slots);
+        else
+            hipLaunchKernelGGL(lzs_burst_gather_kernel, dim3(npackets), dim3(256), 0, stream, in, c.in_stride, c.d_in_len,
+                               c.in_len, skey, sidx, (const uint64_t *)ends, (const uint8_t *)d_states, nchannels, slots);
         BURST_TRY(hipGetLastError());
-        const int e = lzs_hip_launch_compress_channels(d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len,
-                                                       nullptr, slots, d_status, npackets, stream_);
+        const int e = c.packed() ? lzs_hip_launch_compress_channels_packed(c.d_out, c.d_out_off, d_out_len, c.d_in, c.d_in_off, c.d_in_len,
+                                                                           nullptr, slots, d_status, npackets, stream_)
+                                 : lzs_hip_launch_compress_channels(c.d_out, c.out_stride, c.out_cap, d_out_len, c.d_in, c.in_stride,
+                                                                    c.d_in_len, c.in_len, nullptr, slots, d_status, npackets, stream_);
         if (e) return e;
-        hipLaunchKernelGGL(lzs_burst_commit_kernel, dim3(npackets), dim3(128), 0, stream, skey, sidx, (const uint8_t *)slots,
-                           nchannels, (uint8_t *)d_states, npackets);
+        if (c.packed())
+            hipLaunchKernelGGL(lzs_burst_commit_packed_kernel, dim3(npackets), dim3(128), 0, stream, c.d_in_off, c.d_in_len, c.d_out_off,
+                               skey, sidx, (const uint8_t *)slots, nchannels, (uint8_t *)d_states, npackets);
+        else
+            hipLaunchKernelGGL(lzs_burst_commit_kernel, dim3(npackets), dim3(128), 0, stream, skey, sidx, (const uint8_t *)slots,
+                               nchannels, (uint8_t *)d_states, npackets);
         return (int)hipGetLastError();
     }
     // ---- decompression: the runs by weight, heaviest first, one decoder stream each
@@ -560,26 +659,71 @@ extern "C" int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uin
     if (need > L.temp_bytes) return (int)hipErrorInvalidValue;
     rocprim::double_buffer<uint32_t> w(u32(L.weight[0]), u32(L.weight[1])), a(u32(L.at[0]), u32(L.at[1]));
     BURST_TRY(rocprim::radix_sort_pairs_desc(temp, need, w, a, npackets, 0u, 32u, stream));
+    const auto runs = [&](const uint32_t *run_key, const uint32_t *run_at) {
+        if (c.packed())
+            return lzs_hip_launch_decompress_runs_packed(c.d_out, c.d_out_off, d_out_len, c.d_in, c.d_in_off, c.d_in_len, room_ends, run_key,
+                                                         run_at, u32(L.run_end), skey, sidx, nchannels, d_states, d_status, npackets, stream_);
+        return lzs_hip_launch_decompress_runs(c.d_out, c.out_stride, c.out_cap, d_out_len, c.d_in, c.in_stride, c.d_in_len, c.in_len,
+                                              run_key, run_at, u32(L.run_end), skey, sidx, nchannels, d_states, d_status, npackets, stream_);
+    };
     if (split) {
         // ---- the heavy runs (a prefix of that order, found on the device) by PARSE and RESOLVE, the others by the run decoder
         // from tables of their own
         uint16_t *const origins = reinterpret_cast<uint16_t *>(W + L.origins);
         uint2 *const rec = reinterpret_cast<uint2 *>(W + L.rec);
-        hipLaunchKernelGGL(lzs_burst_split_plan_kernel, dim3(grid), dim3(256), 0, stream, (const uint32_t *)w.current(),
-                           (const uint32_t *)a.current(), split_min, u32(L.light_w), u32(L.light_at), u32(L.nheavy), npackets);
-        hipLaunchKernelGGL(lzs_burst_parse_kernel, dim3(npackets), dim3(64), 0, stream, (uint8_t *)d_out, out_stride, out_cap, d_out_len,
-                           (const uint8_t *)d_in, in_stride, d_in_len, in_len, skey, sidx, (const uint64_t *)ends,
-                           (const uint32_t *)u32(L.run_end), (const uint8_t *)d_states, nchannels, d_status, origins, rec,
-                           (const uint32_t *)u32(L.nheavy), split_min);
         const uint32_t most_runs = npackets <= nchannels ? npackets : nchannels + 1u;     // (the ids out of range are one more)
-        hipLaunchKernelGGL(lzs_burst_resolve_kernel, dim3(most_runs), dim3(256), 0, stream, (uint8_t *)d_out, out_stride, out_cap,
-                           (const uint32_t *)a.current(), (const uint32_t *)u32(L.run_end), skey, sidx, (uint8_t *)d_states,
-                           nchannels, (const uint16_t *)origins, (const uint2 *)rec, (const uint32_t *)u32(L.nheavy));
+        if (c.packed()) {
+            hipLaunchKernelGGL(lzs_burst_split_plan_packed_kernel, dim3(grid), dim3(256), 0, stream, (const uint32_t *)w.current(),
+                               (const uint32_t *)a.current(), split_min, (const uint64_t *)room_ends, origin_cap, u32(L.light_w),
+                               u32(L.light_at), u32(L.nheavy), npackets);
+            hipLaunchKernelGGL(lzs_burst_parse_packed_kernel, dim3(npackets), dim3(64), 0, stream, out, c.d_out_off, d_out_len, in,
+                               c.d_in_off, c.d_in_len, (const uint64_t *)room_ends, skey, sidx, (const uint64_t *)ends,
+                               (const uint32_t *)u32(L.run_end), (const uint8_t *)d_states, nchannels, d_status, origins, rec,
+                               (const uint32_t *)u32(L.nheavy), split_min);
+            hipLaunchKernelGGL(lzs_burst_resolve_packed_kernel, dim3(most_runs), dim3(256), 0, stream, out, c.d_out_off, c.d_in_off,
+                               c.d_in_len, (const uint64_t *)room_ends, (const uint32_t *)a.current(), (const uint32_t *)u32(L.run_end),
+                               skey, sidx, (uint8_t *)d_states, nchannels, (const uint16_t *)origins, (const uint2 *)rec,
+                               (const uint32_t *)u32(L.nheavy));
+        } else {
+            hipLaunchKernelGGL(lzs_burst_split_plan_kernel, dim3(grid), dim3(256), 0, stream, (const uint32_t *)w.current(),
+                               (const uint32_t *)a.current(), split_min, u32(L.light_w), u32(L.light_at), u32(L.nheavy), npackets);
+            hipLaunchKernelGGL(lzs_burst_parse_kernel, dim3(npackets), dim3(64), 0, stream, out, c.out_stride, c.out_cap, d_out_len,
+                               in, c.in_stride, c.d_in_len, c.in_len, skey, sidx, (const uint64_t *)ends,
+                               (const uint32_t *)u32(L.run_end), (const uint8_t *)d_states, nchannels, d_status, origins, rec,
+                               (const uint32_t *)u32(L.nheavy), split_min);
+            hipLaunchKernelGGL(lzs_burst_resolve_kernel, dim3(most_runs), dim3(256), 0, stream, out, c.out_stride, c.out_cap,
+                               (const uint32_t *)a.current(), (const uint32_t *)u32(L.run_end), skey, sidx, (uint8_t *)d_states,
+                               nchannels, (const uint16_t *)origins, (const uint2 *)rec, (const uint32_t *)u32(L.nheavy));
+        }
         BURST_TRY(hipGetLastError());
-        return lzs_hip_launch_decompress_runs(d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len,
-                                              u32(L.light_w), u32(L.light_at), u32(L.run_end), skey, sidx, nchannels, d_states,
-                                              d_status, npackets, stream_);
+        return runs(u32(L.light_w), u32(L.light_at));
     }
-    return lzs_hip_launch_decompress_runs(d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len, in_len, w.current(),
-                                          a.current(), u32(L.run_end), skey, sidx, nchannels, d_states, d_status, npackets, stream_);
+    return runs(w.current(), a.current());
+}
+
+}  // namespace
+
+extern "C" size_t lzs_hip_burst_work_bytes(size_t npackets)
+{
+    return burst_layout(npackets).total;
+}
+
+extern "C" int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
+                             const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
+                             const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
+                             void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream_)
+{
+    const BurstCall c = {d_out, d_in, out_stride, in_stride, out_cap, in_len, d_in_len, nullptr, nullptr};
+    return burst(decompress, c, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets, split, 0, split_min, stream_);
+}
+
+extern "C" int lzs_hip_burst_packed(int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                    const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, void *d_states,
+                                    uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, size_t origin_bytes,
+                                    uint32_t split_min, void *stream_)
+{
+    const BurstCall c = {d_out, d_in, 0, 0, 0u, 0u, d_in_len, d_in_off, d_out_off};
+    const uint64_t origin_cap = origin_bytes / 2u;
+    return burst(decompress, c, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets,
+                 decompress && origin_cap != 0, origin_cap, split_min, stream_);
 }

@@ -211,6 +211,20 @@ int lzs_hip_launch_compress_channels_packed(void *d_out, const uint64_t *d_out_o
                                             void *d_states, uint8_t *d_status, uint32_t npackets, void *stream);
 int lzs_hip_launch_compact_packed(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off,
                                   const uint32_t *d_len, uint32_t nblocks, void *stream);
+/* Packed bursts (lzs_channels_burst.hip; lzs_packed.c checks the arguments): lzs_hip_burst with the packets and their
+ * rooms addressed as in the packed calls above.  origin_bytes (decompression): what the work area holds behind
+ * lzs_hip_burst_work_bytes(), 0: none; the long runs are split if the sum of the rooms, found on the device, fits it as 16-bit
+ * origins.  lzs_hip_launch_decompress_runs_packed is lzs_hip_launch_decompress_runs on such packets; d_room_ends[i] = the sum of the
+ * rooms of the packets at sorted positions 0 .. i. */
+int lzs_hip_launch_decompress_runs_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                          const uint64_t *d_in_off, const uint32_t *d_in_len, const uint64_t *d_room_ends,
+                                          const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
+                                          const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
+                                          uint8_t *d_status, uint32_t npackets, void *stream);
+int lzs_hip_burst_packed(int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                         const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, void *d_states,
+                         uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, size_t origin_bytes,
+                         uint32_t split_min, void *stream);
 
 #ifdef __cplusplus
 }

@@ -832,6 +832,20 @@ int lzs_hip_launch_decompress_channels_packed(void *d_out, const uint64_t *d_out
     return (int)hipGetLastError();
 }
 
+// The runs of a packed burst (lzs_channels_burst.hip): eight to a wavefront always -- the extents are the kernel's to find.
+int lzs_hip_launch_decompress_runs_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                          const uint64_t *d_in_off, const uint32_t *d_in_len, const uint64_t *d_room_ends,
+                                          const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
+                                          const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
+                                          uint8_t *d_status, uint32_t npackets, void *stream)
+{
+    if (npackets == 0) return 0;
+    hipLaunchKernelGGL(lzs_decompress_runs_packed_grp_kernel, dim3((npackets + kDecGroups - 1) / kDecGroups), dim3(64), 0,
+                       (hipStream_t)stream, (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len,
+                       d_room_ends, d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets);
+    return (int)hipGetLastError();
+}
+
 int lzs_hip_launch_scan_sizes(uint64_t *d_offsets, const uint32_t *d_size, uint32_t align, uint32_t nblocks, void *stream)
 {
     hipLaunchKernelGGL(lzs_scan_sizes_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_offsets, d_size, align - 1u, nblocks);

@@ -2,7 +2,8 @@
  * lzs_packed.c -- the offset-addressed ("packed") calls (include/lzs/lzs_batch.h, lzs_channels.h):
  * lzs_offsets_from_sizes_device, lzs_decompressed_size_packed_device, lzs_decompress_batch_packed_device,
  * lzs_decompress_channels_packed_device; lzs_compressed_bound_packed_device, lzs_compress_batch_packed_device,
- * lzs_compress_channels_packed_device, lzs_compact_packed_device.  The arguments are checked here; lzs_scan_sizes_kernel,
+ * lzs_compress_channels_packed_device, lzs_compact_packed_device; lzs_channels_burst_packed_split_work_bytes,
+ * lzs_compress_channels_burst_packed_device, lzs_decompress_channels_burst_packed_device.  The arguments are checked here; lzs_scan_sizes_kernel,
  * lzs_decoded_size_packed_kernel (lzs_decoded_size.hip), lzs_decompress_packed_grp_kernel (kernels/decompress_packed.inc), the packed
  * entries of kernels/compress_wg.inc and compress_aux.inc and lzs_gather_packed_kernel (kernels/compact_resume.inc) do the rest.
  * Offsets and lengths stay on the device: what they say about a single block is the kernels' to check.
@@ -148,6 +149,62 @@ int lzs_compress_channels_packed_device(void *d_out, const uint64_t *d_out_off, 
     const int e = lzs_hip_launch_compress_channels_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
                                                           d_status, (uint32_t)npackets, hip_stream);
     return e ? hip_fail(e, who) : LZS_OK;
+}
+
+/* Packed bursts (lzs_channels_burst.hip): the checks of the packed calls above and those of device_burst in
+ * lzs_channels.c.  What the work area holds behind the burst size is room for origins: whether the rooms fit it is the device's to
+ * see (lzs_burst_split_plan_packed_kernel). */
+size_t lzs_channels_burst_packed_split_work_bytes(size_t npackets, size_t nchannels, uint64_t out_bytes)
+{
+    const size_t base = lzs_channels_burst_work_bytes(npackets, nchannels);
+    if (out_bytes > (uint64_t)((SIZE_MAX - base) / 2u)) return SIZE_MAX;
+    return base + 2u * (size_t)out_bytes;
+}
+
+static int device_burst_packed(const char *who, int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
+                               const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                               void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets,
+                               void *stream)
+{
+    if (npackets == 0) return LZS_OK;
+    int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
+    if (rc != LZS_OK) return rc;
+    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
+    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
+    if (!d_channel) return fail(LZS_E_ARG, "%s: channel is NULL", who);
+    if (nchannels == 0) return fail(LZS_E_ARG, "%s: no channels for %zu packets", who, npackets);
+    if (nchannels > LZS_CHANNELS_MAX) return fail(LZS_E_ARG, "%s: too many channels (%zu)", who, nchannels);
+    if (!d_work) return fail(LZS_E_ARG, "%s: work is NULL", who);
+    if ((uintptr_t)d_work & 255u) return fail(LZS_E_ARG, "%s: work is not 256-byte aligned", who);
+    const size_t need = lzs_channels_burst_work_bytes(npackets, nchannels);
+    if (work_bytes < need)
+        return fail(LZS_E_ARG, "%s: work_bytes %zu is smaller than lzs_channels_burst_work_bytes() = %zu", who, work_bytes, need);
+    rc = require_device();
+    if (rc != LZS_OK) return rc;
+    const lzs_env_t *env = lzs_env();
+    const uint32_t split_min = env->burst_split_set ? env->burst_split_min : BURST_SPLIT_MIN_DEFAULT;
+    const int e = lzs_hip_burst_packed(decompress, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
+                                       (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, decompress ? work_bytes - need : 0,
+                                       split_min, stream);
+    return e ? hip_fail(e, who) : LZS_OK;
+}
+
+int lzs_compress_channels_burst_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                              const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                              void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes,
+                                              size_t npackets, void *hip_stream)
+{
+    return device_burst_packed("lzs_compress_channels_burst_packed_device", 0, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len,
+                               d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+}
+
+int lzs_decompress_channels_burst_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                                const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                                void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes,
+                                                size_t npackets, void *hip_stream)
+{
+    return device_burst_packed("lzs_decompress_channels_burst_packed_device", 1, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len,
+                               d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_compact_packed_device(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_len,
