@@ -125,11 +125,57 @@ int lzs_decompress_batch_device_sync(void *d_out, size_t out_stride, size_t out_
  * The call is sized for MANY blocks.  On an MI355X 65 536 packets of 1500 bytes of text take 0.51 ms (decoding them into
  * scratch memory: 0.80 ms) and 16 384 blocks of 64 KiB of text 18.6 ms (decoding: 7.5 ms); DESIGN.md 3.13 has every
  * row.  One block is one lane's serial walk however large it is, so a few huge blocks get no help from it: a single block of
- * 1 MiB of text takes 157 ms.
+ * 1 MiB of text takes 157 ms.  Long streams and batches of long blocks are what lzs_decompressed_size_stream_device(),
+ * lzs_decompressed_size_stream() and lzs_decompressed_size_batch_device_sync() below are for: the same answers from a
+ * segmented walk over the whole device.
  */
 int lzs_decompressed_size_batch_device(uint32_t *d_size, uint8_t *d_status,
                                        const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
                                        size_t limit, size_t nblocks, void *hip_stream);
+
+/*
+ * The same question for ONE LONG stream, answered by the whole device: the stream is cut into segments as
+ * lzs_decompress_stream_device() cuts it, every segment is walked without copying a byte and reports how many bytes it
+ * produces, the host sums, and one short walk finds the status where the room runs out or the stream ends.
+ * What the decode calls make their callers guess -- out_cap -- is one call away.
+ *
+ *   flags == 0, the plain rule:
+ *     *size   : what lzs_decompress(out, limit, in, in_len) returns
+ *     *status : (status may be NULL) the LZS_D_STATUS_* byte lzs_decompressed_size_batch_device() writes for the same bytes
+ *               and the same limit, by the rules stated there -- END_MARKER 0x04, NO_OUTPUT_BUFFER_SPACE 0x08, or
+ *               INPUT_STARVED | INPUT_FINISHED 0x03 -- in every corner: an empty stream is 0x03, or 0x08 with limit == 0
+ *   flags == LZS_SIZE_CONCAT, the file rule of lzs_decompress_concat(): the walk goes on behind every end marker
+ *     *size   : what lzs_decompress_concat(out, limit, in, in_len) returns
+ *     *status : NO_OUTPUT_BUFFER_SPACE if *size == limit, otherwise INPUT_STARVED | INPUT_FINISHED; never END_MARKER -- a
+ *               marker ends nothing here
+ *
+ * limit is any uint64_t; UINT64_MAX asks for the true size.  LZS_E_ARG, with the call's name in lzs_last_error() and before
+ * the device is asked: size NULL, an unknown bit in flags, in_len > LZS_BLOCK_MAX, NULL input with in_len > 0.  in_len == 0 is
+ * LZS_OK without a device; a valid call without one is LZS_E_NO_DEVICE.
+ *
+ * *size and *status are in HOST memory.  Synchronous, on the calling thread's own stream with scratch from the thread's
+ * staging, like lzs_decompress_stream_device(): not capturable, no output allocated, d_in must be complete when the call is
+ * made.  Any alignment of d_in; nothing is read outside the aligned 32-bit words that hold the stream's own bytes.
+ * lzs_decompressed_size_stream() is the same from a host buffer, staged through the calling thread's device memory.
+ */
+#define LZS_SIZE_CONCAT 1u    /* the file rule of lzs_decompress_concat(): go on behind every end marker */
+int lzs_decompressed_size_stream_device(uint64_t *size, uint8_t *status, const void *d_in, size_t in_len,
+                                        uint64_t limit, unsigned flags);
+int lzs_decompressed_size_stream(uint64_t *size, uint8_t *status, const uint8_t *in, size_t in_len,
+                                 uint64_t limit, unsigned flags);
+
+/*
+ * The size-query twin of lzs_decompress_batch_device_sync(): a batch of blocks in device memory, the lengths (in_len_each may
+ * be NULL: every block in_len bytes) and the results in HOST memory.  size[b] and status[b] (status may be NULL) are exactly
+ * what lzs_decompressed_size_batch_device() gives block b at the same limit (the plain rule; limit <= 0xFFFFFFFF).  Batches
+ * of long blocks -- 10 167 bytes and more on average (the crossover measured on an MI355X), in an extent that
+ * 32-bit positions reach -- go by segments like one long
+ * stream, all blocks at once; the others by one lane a block.  Synchronous, on the calling thread's own stream and staging.
+ * LZS_E_ARG: size NULL, in_len or a block's length > LZS_BLOCK_MAX, nblocks > 0x7FFFFFFF, limit > 0xFFFFFFFF, NULL input
+ * with a length above 0.  nblocks == 0 is LZS_OK and touches nothing.
+ */
+int lzs_decompressed_size_batch_device_sync(uint32_t *size, uint8_t *status, const void *d_in, size_t in_stride,
+                                            const uint32_t *in_len_each, size_t in_len, size_t limit, size_t nblocks);
 
 /*
  * ONE stream from device memory, on the whole device: the result of

@@ -12,6 +12,7 @@ from .api import (IncrementalCompressor, IncrementalDecompressor, LzsError, back
                   decompress_stream, decompressed_max, incremental_compress, last_error, lib, release_thread_cache)
 from .api import (STATUS_END_MARKER, STATUS_ERROR, STATUS_INPUT_FINISHED, STATUS_INPUT_STARVED, STATUS_NO_OUTPUT_BUFFER_SPACE)
 from .api import decompress_blocks_dense, decompressed_sizes
+from .api import SIZE_CONCAT, decompressed_size, decompressed_size_stream, decompressed_sizes_sync
 from .api import decompress_channels_packed, decompress_dense, decompress_packed, decompressed_sizes_packed, offsets_from_sizes
 from .api import compact_packed, compress_channels_packed, compress_dense, compress_packed, compressed_bounds_packed
 from .api import (channels_burst_packed_split_work_bytes, compress_channels_burst_packed, compress_channels_dense,
@@ -25,6 +26,7 @@ __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_byt
            "decompress_stream", "decompressed_max", "incremental_compress", "last_error", "lib", "release_thread_cache", "workload",
            "STATUS_END_MARKER", "STATUS_ERROR", "STATUS_INPUT_FINISHED", "STATUS_INPUT_STARVED", "STATUS_NO_OUTPUT_BUFFER_SPACE",
            "decompress_blocks_dense", "decompressed_sizes",
+           "SIZE_CONCAT", "decompressed_size", "decompressed_size_stream", "decompressed_sizes_sync",
            "decompress_channels_packed", "decompress_dense", "decompress_packed", "decompressed_sizes_packed", "offsets_from_sizes",
            "compact_packed", "compress_channels_packed", "compress_dense", "compress_packed", "compressed_bounds_packed",
            "channels_burst_packed_split_work_bytes", "compress_channels_burst_packed", "compress_channels_dense",

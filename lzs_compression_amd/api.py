@@ -107,6 +107,13 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "lzs_decompressed_size_batch_device"):      # (an older build named by LZS_LIBRARY, for A/B runs, has none)
             L.lzs_decompressed_size_batch_device.restype = ctypes.c_int
             L.lzs_decompressed_size_batch_device.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp]
+        if hasattr(L, "lzs_decompressed_size_stream_device"):     # (the same: the size query for long streams)
+            _u64p, _u64 = ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64
+            for name in ("lzs_decompressed_size_stream_device", "lzs_decompressed_size_stream"):
+                f = getattr(L, name)
+                f.restype, f.argtypes = ctypes.c_int, [_u64p, _vp, _vp, _sz, _u64, ctypes.c_uint]
+            L.lzs_decompressed_size_batch_device_sync.restype = ctypes.c_int
+            L.lzs_decompressed_size_batch_device_sync.argtypes = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz]
         if hasattr(L, "lzs_decompress_batch_packed_device"):      # (the same: the packed calls)
             L.lzs_offsets_from_sizes_device.restype = ctypes.c_int
             L.lzs_offsets_from_sizes_device.argtypes = [_vp, _vp, _sz, _sz, _vp]
@@ -182,14 +189,20 @@ def compress(data: bytes, out_capacity: Optional[int] = None) -> bytes:
     return _one_shot(lib().lzs_compress, data, cap)
 
 
-def decompress(data: bytes, out_capacity: int) -> bytes:
-    """lzs_decompress() (reference lzs-decompression.c:156-412)."""
+def decompress(data: bytes, out_capacity: Optional[int] = None) -> bytes:
+    """lzs_decompress() (reference lzs-decompression.c:156-412).  ``out_capacity`` None: the size is asked first
+    (decompressed_size) and the output allocated exactly."""
+    if out_capacity is None:
+        out_capacity = decompressed_size(data)[0]
     return _one_shot(lib().lzs_decompress, data, out_capacity)
 
 
-def decompress_concat(data: bytes, out_capacity: int) -> bytes:
+def decompress_concat(data: bytes, out_capacity: Optional[int] = None) -> bytes:
     """A file of streams back to back, decoded as the reference's file tool does
-    (decoder carries on after each end marker: reference lzs-decompression.c:564-576)."""
+    (decoder carries on after each end marker: reference lzs-decompression.c:564-576).  ``out_capacity`` None: the size is
+    asked first (decompressed_size with concat=True) and the output allocated exactly."""
+    if out_capacity is None:
+        out_capacity = decompressed_size(data, concat=True)[0]
     return _one_shot(lib().lzs_decompress_concat, data, out_capacity)
 
 
@@ -297,10 +310,13 @@ def compress_stream(x, out=None):
     return out, int(got.value)
 
 
-def decompress_stream(x, out_capacity, out=None):
+def decompress_stream(x, out_capacity=None, out=None):
     """lzs_decompress_stream_device(): the device tensor ``x`` (one LZS stream, uint8) decompressed
-    by many wavefronts.  Returns (buffer uint8 [out_capacity], nbytes).  Synchronous."""
+    by many wavefronts.  Returns (buffer uint8 [out_capacity], nbytes).  Synchronous.  ``out_capacity`` None:
+    the size is asked first (decompressed_size_stream) and the buffer is exactly that long -- or ``out``, if given, is its room."""
     import torch
+    if out_capacity is None:
+        out_capacity = out.numel() if out is not None else decompressed_size_stream(x)[0]
     if out is None:
         out = torch.empty(out_capacity, dtype=torch.uint8, device=x.device)
     got = _sz(0)
@@ -354,6 +370,55 @@ def decompressed_sizes(x, in_len=None, limit: Optional[int] = None, size=None, s
     _check(lib().lzs_decompressed_size_batch_device(
         size.data_ptr(), status.data_ptr(), x.data_ptr(), x.stride(0) if nb > 1 else x.shape[1],
         None if in_len is None else in_len.data_ptr(), x.shape[1], limit, nb, _stream_handle(stream)))
+    return size, status
+
+
+SIZE_CONCAT = 1                     # LZS_SIZE_CONCAT: the file rule of decompress_concat
+_SIZE_MAX64 = (1 << 64) - 1
+
+
+def _size_stream(fn, ptr, n: int, limit: Optional[int], concat: bool) -> Tuple[int, int]:
+    size, status = ctypes.c_uint64(0), ctypes.c_uint8(0)
+    _check(fn(ctypes.byref(size), ctypes.addressof(status), ptr, n, _SIZE_MAX64 if limit is None else int(limit),
+              SIZE_CONCAT if concat else 0))
+    return int(size.value), int(status.value)
+
+
+def decompressed_size(data: bytes, limit: Optional[int] = None, concat: bool = False) -> Tuple[int, int]:
+    """lzs_decompressed_size_stream(): (size, status) of ONE stream in host memory at an output capacity of ``limit`` (None: no
+    limit, the true size), without decoding it: len(decompress(data, limit)) and the STATUS_* bits the size query of a batch
+    gives -- with ``concat`` len(decompress_concat(data, limit)), and STATUS_NO_OUTPUT_BUFFER_SPACE if that is the limit,
+    otherwise STATUS_INPUT_STARVED | STATUS_INPUT_FINISHED.  A segmented walk over the whole device."""
+    data = bytes(data)
+    src = ctypes.create_string_buffer(data, max(len(data), 1))      # exactly len bytes: no spare byte
+    return _size_stream(lib().lzs_decompressed_size_stream, ctypes.addressof(src), len(data), limit, concat)
+
+
+def decompressed_size_stream(x, limit: Optional[int] = None, concat: bool = False) -> Tuple[int, int]:
+    """lzs_decompressed_size_stream_device(): the same for the device tensor ``x`` (one LZS stream, uint8, contiguous; any
+    alignment).  Synchronous."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+    torch.cuda.current_stream().synchronize()             # the call runs on the library's own stream
+    return _size_stream(lib().lzs_decompressed_size_stream_device, x.data_ptr(), x.numel(), limit, concat)
+
+
+def decompressed_sizes_sync(x, in_len=None, limit: Optional[int] = None):
+    """lzs_decompressed_size_batch_device_sync(): decompressed_sizes() for a batch of LONG blocks in device memory (``x``: uint8
+    [nblocks, stride]) with their lengths on the host (``in_len``: sequence / numpy array, or None for full rows) -- cut into
+    segments for the whole device where the blocks are long enough, one lane a block otherwise.  Synchronous.  Returns
+    (size uint32 [nblocks], status uint8 [nblocks]) as numpy arrays."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.stride(1) == 1
+    nblocks = x.shape[0]
+    lens = None if in_len is None else np.ascontiguousarray(in_len, dtype=np.uint32)
+    assert lens is None or (lens.shape == (nblocks,) and (lens <= x.shape[1]).all())
+    size = np.zeros(nblocks, dtype=np.uint32)
+    status = np.zeros(nblocks, dtype=np.uint8)
+    torch.cuda.current_stream().synchronize()             # the call runs on the library's own stream
+    _check(lib().lzs_decompressed_size_batch_device_sync(
+        size.ctypes.data, status.ctypes.data, x.data_ptr(), x.stride(0) if nblocks > 1 else x.shape[1],
+        None if lens is None else lens.ctypes.data, x.shape[1], SIZE_LIMIT_NONE if limit is None else int(limit), nblocks))
     return size, status
 
 

@@ -71,9 +71,24 @@ int main(int argc, char **argv)
             fwrite(out + b * out_stride, 1, len_out[b], fo);
         }
     } else {
-        /* output size unknown: grow the buffer until the decoder stops short of it */
+        /* output size unknown: ask (the file rule's size query), allocate that and one byte, decode once.  The
+         * spare byte is the check: a decoder that fills it says the answer was too small, and the growth loop takes over. */
+        uint64_t size = 0;
+        int asked = lzs_decompressed_size_stream(&size, NULL, in, n, UINT64_MAX, LZS_SIZE_CONCAT);
+        if (asked == LZS_OK) {
+            uint8_t *out = (uint8_t *)malloc((size_t)size + 1);
+            if (!out) { fprintf(stderr, "lzs-decompress: out of memory\n"); return 1; }
+            const size_t got = lzs_decompress_concat(out, (size_t)size + 1, in, n);
+            if (got == 0 && size && lzs_last_error()[0]) { fprintf(stderr, "lzs-decompress: %s\n", lzs_last_error()); return 1; }
+            if (got <= size) fwrite(out, 1, got, fo); else asked = LZS_E_ARG;
+            free(out);
+        } else if (asked != LZS_E_ARG) {
+            fprintf(stderr, "lzs-decompress: %s\n", lzs_last_error());
+            return 1;
+        }
+        /* a file above LZS_BLOCK_MAX is not the query's: grow the buffer until the decoder stops short of it */
         size_t cap = n * 4 + 4096;
-        for (;;) {
+        while (asked == LZS_E_ARG) {
             uint8_t *out = (uint8_t *)malloc(cap);
             if (!out) { fprintf(stderr, "lzs-decompress: out of memory\n"); return 1; }
             size_t got = lzs_decompress_concat(out, cap, in, n);

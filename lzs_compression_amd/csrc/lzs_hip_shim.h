@@ -186,6 +186,13 @@ int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slo
 int lzs_hip_launch_decoded_size(uint32_t *d_size, uint8_t *d_status, const void *d_in, size_t in_stride,
                                 const uint32_t *d_in_len, uint32_t in_len, uint32_t limit, uint32_t nblocks,
                                 void *stream);
+/* The finishing walk of the size query for long streams (lzs_size_stream.hip; lzs_size_stream.c has the route):
+ * stream i is walked from d_in[d_from[i]], entered in the state word d_entry[i] that SCAN settled for the segment that starts
+ * there (above), to d_in[d_end[i]], its stream's end, with d_room[i] bytes of room: d_counted[i] = the bytes counted,
+ * d_status[i] the LZS_D_STATUS_* bits -- lzs_hip_launch_decoded_size's walk and rules from another start.  One lane a stream. */
+int lzs_hip_launch_size_finish(uint32_t *d_counted, uint8_t *d_status, const void *d_in, const uint32_t *d_from,
+                               const uint32_t *d_end, const uint32_t *d_entry, const uint32_t *d_room, uint32_t nstreams,
+                               void *stream);
 /* The packed calls (lzs_packed.c checks the arguments): stream b lies at d_in + d_in_off[b] -- d_in_len[b] bytes,
  * or up to d_in_off[b + 1] with d_in_len NULL -- and decodes to d_out + d_out_off[b] with d_out_off[b + 1] - d_out_off[b] bytes
  * of room.  lzs_hip_launch_scan_sizes: d_offsets[b + 1] = d_offsets[b] + d_size[b] rounded up to `align` (a power of two),

@@ -196,4 +196,29 @@ LZS_HIDDEN int batch_decompress_segments(staging_t *st, void *stream, const char
                                          uint32_t cap32, uint32_t *out_len, uint32_t *d_len, const void *d_in, size_t d_in_stride,
                                          const uint32_t *in_len_each, uint32_t in_len, size_t nblocks);
 
+/* ---- what the size query for long streams (lzs_size_stream.c) shares with the many-wavefront decompressor */
+/* The segments of one stream, or of all the blocks of a batch, as SCAN, DECODE and RESOLVE see them.  One stream needs no
+ * range tables -- segment k is bytes [k seg, (k + 1) seg) of it -- and only its segment 0 is a first segment: one entered in
+ * a state that is given, not taken over from the segment before.  A batch says for every segment where it starts, where its
+ * block's stream ends, where its block's output begins and must end, and whether it is its block's first. */
+typedef struct {
+    const char *label;              /* "stream decode" or "batch decode": the LZS_STREAM_DEBUG lines */
+    size_t   nblocks;               /* 0: one stream */
+    uint32_t seg, nseg;
+    uint32_t *seen, *entry, *exits, *count, *start;      /* host side; exits and count lie one behind the other */
+    uint32_t *base, *end, *floor_, *limit;               /* the range tables, or NULL */
+    uint8_t  *dirty, *ones, *first;                      /* (first: or NULL) */
+    /* device side, in this order; then two counters, dirty, ones */
+    uint32_t *d_entry, *d_exit, *d_count, *d_start, *d_base, *d_end, *d_floor, *d_limit, *d_counters;
+    uint8_t  *d_dirty, *d_ones;
+} seg_table_t;
+LZS_HIDDEN int stream_call_begins(const char *who, size_t tab_bytes, staging_t **st, void **tables);
+LZS_HIDDEN int stream_copy_in(void *d_in, const uint8_t *prefix, size_t pre, const uint8_t *in, size_t n, void *stream);
+LZS_HIDDEN size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status);
+LZS_HIDDEN uint32_t stream_dec_seg(size_t n);
+LZS_HIDDEN void segtab_lay_out(seg_table_t *t, uint32_t *h, uint32_t *d, int ranges);
+LZS_HIDDEN uint32_t settle_entries(seg_table_t *t, int use_ones, int *host_made);
+LZS_HIDDEN int scan_rounds(seg_table_t *t, void *stream, const char *who, const void *d_in, uint32_t n, uint32_t in_extent,
+                           uint32_t entry0, int concat, uint32_t *d_marks, double *t0);
+
 #endif

@@ -119,4 +119,22 @@ static inline uint32_t lzs_plan_resolve_grid(uint32_t total)
     return grid > 65536u ? 65536u : grid;
 }
 
+/* ---- size query of a batch with its lengths on the host (lzs_size_stream.c): by lanes or by segments -----------
+ * By lanes: lzs_decoded_size_kernel, one lane a block.  By segments: SCAN over every block's segments and one finishing walk a
+ * block -- its tables hold 32-bit positions, so `extent`, nblocks strides plus the longest block, must fit 32 bits, and it pays
+ * only where a block is many segments: from LZS_PLAN_SIZE_SEG_MIN_AVG bytes a block on average (total_in / nblocks) on -- the
+ * smallest average length of the sweep in profiles/r20/size_stream.txt from which every class's rows are faster by segments
+ * (low entropy: 2.35 ms against 2.76 at 10 167 bytes, 1.70 against 0.80 at 2545; text turns between 2460 and 9432, high
+ * entropy between 1721 and 4570).
+ * forced: LZS_SIZE_ROUTE, 0 not set, 1 lanes, 2 segments -- which an extent beyond 32 bits still cannot take. */
+#define LZS_PLAN_SIZE_SEG_MIN_AVG 10167u
+enum { LZS_SIZE_BY_LANES = 0, LZS_SIZE_BY_SEGMENTS = 1 };
+
+static inline int lzs_plan_size_route(uint64_t extent, uint64_t total_in, uint64_t nblocks, int forced)
+{
+    if (extent > 0xFFFFFFFFull || nblocks == 0u || total_in == 0u || forced == 1) return LZS_SIZE_BY_LANES;
+    if (forced == 2) return LZS_SIZE_BY_SEGMENTS;
+    return total_in / nblocks >= LZS_PLAN_SIZE_SEG_MIN_AVG ? LZS_SIZE_BY_SEGMENTS : LZS_SIZE_BY_LANES;
+}
+
 #endif

@@ -17,7 +17,7 @@ LZS_HIDDEN double now_ms(void)
 /* ------------------------------------------------ how a one-stream call begins and ends, compressing or decompressing */
 /* It begins with the device, this thread's staging, `tab_bytes` of its pinned memory for the per-segment tables (they travel every
  * round) and its stream.  LZS_OK or the code reported. */
-static int stream_call_begins(const char *who, size_t tab_bytes, staging_t **st, void **tables)
+LZS_HIDDEN int stream_call_begins(const char *who, size_t tab_bytes, staging_t **st, void **tables)
 {
     tls_error[0] = 0;
     if (require_device() != LZS_OK) return LZS_E_HIP;
@@ -27,7 +27,7 @@ static int stream_call_begins(const char *who, size_t tab_bytes, staging_t **st,
 }
 
 /* in on the host: the prefix of a piece (pre bytes, or none) and the caller's input behind it make the n bytes at d_in */
-static int stream_copy_in(void *d_in, const uint8_t *prefix, size_t pre, const uint8_t *in, size_t n, void *stream)
+LZS_HIDDEN int stream_copy_in(void *d_in, const uint8_t *prefix, size_t pre, const uint8_t *in, size_t n, void *stream)
 {
     if (pre) HIP_TRY_RET(lzs_hip_h2d(d_in, prefix, pre, stream), "hipMemcpy H2D");
     HIP_TRY_RET(lzs_hip_h2d((uint8_t *)d_in + pre, in, n - pre, stream), "hipMemcpy H2D");
@@ -36,7 +36,7 @@ static int stream_copy_in(void *d_in, const uint8_t *prefix, size_t pre, const u
 
 /* It ends: a failed one (rc) gives 0 bytes, says so on stderr (host buffers: the reference's calls have no other way) and leaves
  * nothing of its own in flight; the thread's staging is trimmed to what it may keep. */
-static size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status)
+LZS_HIDDEN size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status)
 {
     staging_t *st = staging_get();
     if (rc != LZS_OK) {
@@ -299,7 +299,7 @@ int lzs_compress_stream_device(void *d_out, size_t out_cap, size_t *out_len, con
  * Measured (text, host buffers, ms; output size): 64 KiB 7.7 with one wavefront, 0.67 in 256-byte
  * segments; 256 KiB 30.8 / 1.0; 1 MiB 122.8 / 2.4 (6.3 in 8 KiB segments); 4 MiB 8.2 in 1 KiB
  * segments, 10.1 in 8 KiB ones. */
-static uint32_t stream_dec_seg(size_t n)
+LZS_HIDDEN uint32_t stream_dec_seg(size_t n)
 {
     const uint32_t v = lzs_env()->dec_seg;
     size_t seg = v ? v : (n / 2048u + 255u) & ~(size_t)255u;
@@ -310,24 +310,10 @@ static uint32_t stream_dec_seg(size_t n)
     return (uint32_t)(seg & ~(size_t)63u);
 }
 
-/* The segments of one stream, or of all the blocks of a batch, as SCAN, DECODE and RESOLVE see them.  One stream needs no
- * range tables -- segment k is bytes [k seg, (k + 1) seg) of it -- and only its segment 0 is a first segment: one entered in
- * a state that is given, not taken over from the segment before.  A batch says for every segment where it starts, where its
- * block's stream ends, where its block's output begins and must end, and whether it is its block's first. */
-typedef struct {
-    const char *label;              /* "stream decode" or "batch decode": the LZS_STREAM_DEBUG lines */
-    size_t   nblocks;               /* 0: one stream */
-    uint32_t seg, nseg;
-    uint32_t *seen, *entry, *exits, *count, *start;      /* host side; exits and count lie one behind the other */
-    uint32_t *base, *end, *floor_, *limit;               /* the range tables, or NULL */
-    uint8_t  *dirty, *ones, *first;                      /* (first: or NULL) */
-    /* device side, in this order; then two counters, dirty, ones */
-    uint32_t *d_entry, *d_exit, *d_count, *d_start, *d_base, *d_end, *d_floor, *d_limit, *d_counters;
-    uint8_t  *d_dirty, *d_ones;
-} seg_table_t;
+/* (seg_table_t, the segments as SCAN, DECODE and RESOLVE see them: lzs_internal.h) */
 
 /* (t->nseg is set; host: 5 words and 2 bytes a segment, with range tables 9 and 3; device: 4 words and 2 bytes, or 8 and 2, and 8 bytes) */
-static void segtab_lay_out(seg_table_t *t, uint32_t *h, uint32_t *d, int ranges)
+LZS_HIDDEN void segtab_lay_out(seg_table_t *t, uint32_t *h, uint32_t *d, int ranges)
 {
     const size_t n = t->nseg;
     t->seen = h; t->entry = h + n; t->exits = h + 2 * n; t->count = h + 3 * n; t->start = h + 4 * n; h += 5 * n;
@@ -343,7 +329,7 @@ static void segtab_lay_out(seg_table_t *t, uint32_t *h, uint32_t *d, int ranges)
 /* After a SCAN round: every segment is to be entered in the state in which the one before it left (a first segment in its
  * own), and those for which that is news are walked again.  Host code only.  Returns how many are dirty now; *host_made:
  * some exits / counts were worked out here, not on the device. */
-static uint32_t settle_entries(seg_table_t *t, int use_ones, int *host_made)
+LZS_HIDDEN uint32_t settle_entries(seg_table_t *t, int use_ones, int *host_made)
 {
     const uint32_t seg = t->seg;
     uint32_t *entry = t->entry, *exits = t->exits, *count = t->count, *seen = t->seen;
@@ -389,7 +375,7 @@ static uint32_t settle_entries(seg_table_t *t, int use_ones, int *host_made)
 /* The SCAN rounds: every segment entered at its first bit in the normal state (segment 0 of one stream: in `entry0`), then
  * those whose predecessor left in another state again, until all agree.  `n`: the stream's length (0 with range tables),
  * `in_extent`: the readable bytes at d_in, `d_marks`: what full walks leave for repeated ones.  LZS_OK or the error reported. */
-static int scan_rounds(seg_table_t *t, void *stream, const char *who, const void *d_in, uint32_t n, uint32_t in_extent,
+LZS_HIDDEN int scan_rounds(seg_table_t *t, void *stream, const char *who, const void *d_in, uint32_t n, uint32_t in_extent,
                        uint32_t entry0, int concat, uint32_t *d_marks, double *t0)
 {
     const lzs_env_t env = *lzs_env();
