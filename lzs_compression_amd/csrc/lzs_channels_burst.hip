@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "lzs_burst_plan.h"                    // the work area's layout and a call's host decisions: plain functions, held to a table on the CPU
 #include "lzs_hip_shim.h"
 
 namespace {
@@ -526,204 +527,202 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_packed_kernel(uint8_t *
                         origins, rec, nheavy);
 }
 
-// The work area, in this order, each part 256-byte aligned: npackets channel slots (compression), sort keys and values twice
-// each (the sort's double buffers), the lengths and their scan (64 bit), the runs' weights and positions twice each and their
-// ends (decompression), rocPRIM's temporary storage.
-// A split decode keeps its tables where compression has its slots -- the light runs' weights and positions, {length, open
-// bytes} of every packet by sorted position, the number of heavy runs: 16 bytes a packet -- and npackets * out_cap 16-bit
-// origins, packet by packet in sorted order, behind everything else (`total` is where): the larger work area's extra part.
-// A packed decode has the rooms by sorted position and their scan there as well (16 bytes a packet more), and its origins lie
-// room by room: origin_bytes / 2 of them, as many as the caller's work area holds behind `total`.
-struct BurstLayout {
-    size_t slots, key[2], val[2], lens, ends, weight[2], at[2], run_end, temp, temp_bytes, total;
-    size_t light_w, light_at, rec, nheavy, rooms, room_ends, origins;
-};
+// ---- The host side: a call's stages, in order.  Where the parts of the work area lie, and what a call decides before it launches,
+// is lzs_burst_plan.h's (tests/cpu_shim/burst_plan_check.c).
+static_assert(kStateBytes == LZS_BURST_SLOT_BYTES && kAlign == LZS_BURST_ALIGN && kSortSpareBytes == LZS_BURST_SORT_SPARE,
+              "lzs_burst_plan.h lays the work area out with these");
 
-size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+#define BURST_TRY(x) do { const int e_ = (int)(x); if (e_ != 0) return e_; } while (0)
 
-BurstLayout burst_layout(size_t n)
-{
-    BurstLayout L;
-    size_t o = 0;
-    const auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-    L.slots = take(n * kStateBytes);
-    for (int k = 0; k < 2; k++) L.key[k] = take(4 * n);
-    for (int k = 0; k < 2; k++) L.val[k] = take(4 * n);
-    L.lens = take(8 * n);
-    L.ends = take(8 * n);
-    for (int k = 0; k < 2; k++) L.weight[k] = take(4 * n);
-    for (int k = 0; k < 2; k++) L.at[k] = take(4 * n);
-    L.run_end = take(4 * n);
-    L.temp_bytes = up(kSortSpareBytes + 8 * n);
-    L.temp = take(L.temp_bytes);
-    L.total = o;
-    o = L.slots;
-    L.nheavy = take(4);
-    L.light_w = take(4 * n);
-    L.light_at = take(4 * n);
-    L.rec = take(8 * n);
-    L.rooms = take(8 * n);
-    L.room_ends = take(8 * n);
-    static_assert(kStateBytes >= 6 * kAlign + 32 + kAlign, "the decoders' tables fit the slots of one packet and more");
-    L.origins = L.total;
-    return L;
-}
-
-#define BURST_TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-// What a call gives: the packets strided (off: nullptr) or packed.
-struct BurstCall {
-    void *d_out;
-    const void *d_in;
+// One burst on its way through the stages: what the call gives -- the packets strided (in_off: nullptr) or packed --, what the host
+// decided for it (lzs_burst_plan.h), the parts of the work area, and what a stage leaves for those behind it.
+struct Burst {
+    uint8_t *out;
+    const uint8_t *in;
     size_t out_stride, in_stride;
-    uint32_t out_cap, in_len;
-    const uint32_t *d_in_len;
-    const uint64_t *d_in_off, *d_out_off;
-    bool packed() const { return d_in_off != nullptr; }
+    uint32_t out_cap, in_len_uniform;
+    const uint32_t *in_len;
+    const uint64_t *in_off, *out_off;
+    bool packed() const { return in_off != nullptr; }
+    int decompress;
+    uint32_t *out_len;
+    const uint32_t *channel;
+    uint8_t *states, *status;
+    uint32_t nchannels, npackets, grid;            // grid: workgroups of 256 threads, a thread a packet
+    uint64_t origin_cap;                           // (split, PACKED) 16-bit origins behind the burst part; the strided call's host code knows that they fit
+    uint32_t split_min;
+    hipStream_t stream;
+    // the work area (rooms, room_ends: packed decompression)
+    uint8_t *slots;
+    uint32_t *key[2], *val[2], *weight[2], *at[2], *run_end, *light_w, *light_at, *nheavy;
+    uint64_t *lens, *ends, *rooms, *room_ends;
+    uint2 *rec;
+    uint16_t *origins;
+    void *temp;                                    // rocPRIM's
+    size_t temp_bytes;
+    const uint32_t *skey, *sidx;                   // group: channel (nchannels if out of range) and packet at each sorted position
+    const uint32_t *run_w, *run_at;                // runs by weight, then split: the runs the run decoder takes, heaviest first
 };
 
-// One burst: the grouping, then the kernels of the direction.  split (decompression): the long runs by PARSE and RESOLVE, with
-// origin_cap 16-bit origins behind the burst part of the work area (PACKED; the strided call's host code knows that they fit).
-int burst(int decompress, const BurstCall &c, uint32_t *d_out_len, const uint32_t *d_channel, void *d_states, uint32_t nchannels,
-          uint8_t *d_status, void *d_work, uint32_t npackets, int split, uint64_t origin_cap, uint32_t split_min, void *stream_)
+void burst_lay_out(Burst &b, void *d_work)
 {
-    if (npackets == 0) return 0;
-    const hipStream_t stream = (hipStream_t)stream_;
-    const BurstLayout L = burst_layout(npackets);
+    const lzs_burst_layout_t L = lzs_burst_layout(b.npackets);
     uint8_t *const W = static_cast<uint8_t *>(d_work);
     const auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t *>(W + at); };
     const auto u64 = [&](size_t at) { return reinterpret_cast<uint64_t *>(W + at); };
-    uint64_t *const lens = u64(L.lens), *const ends = u64(L.ends);
-    uint64_t *const rooms = u64(L.rooms), *const room_ends = u64(L.room_ends);     // (packed decompression)
-    void *const temp = W + L.temp;
-    const uint32_t grid = (npackets + 255u) / 256u;
-    const uint8_t *const in = (const uint8_t *)c.d_in;
-    uint8_t *const out = (uint8_t *)c.d_out;
+    b.slots = W + L.slots;
+    for (int k = 0; k < 2; k++) { b.key[k] = u32(L.key[k]); b.val[k] = u32(L.val[k]); b.weight[k] = u32(L.weight[k]); b.at[k] = u32(L.at[k]); }
+    b.run_end = u32(L.run_end); b.light_w = u32(L.light_w); b.light_at = u32(L.light_at); b.nheavy = u32(L.nheavy);
+    b.lens = u64(L.lens); b.ends = u64(L.ends); b.rooms = u64(L.rooms); b.room_ends = u64(L.room_ends);
+    b.rec = reinterpret_cast<uint2 *>(W + L.rec); b.origins = reinterpret_cast<uint16_t *>(W + L.origins);
+    b.temp = W + L.temp; b.temp_bytes = L.temp_bytes;
+}
 
-    // ---- the runs: a stable sort by channel over the bits a channel id in range (or nchannels) can have
-    hipLaunchKernelGGL(lzs_burst_keys_kernel, dim3(grid), dim3(256), 0, stream, d_channel, nchannels, u32(L.key[0]), u32(L.val[0]),
-                       npackets);
-    unsigned bits = 1;
-    while (bits < 32u && (nchannels >> bits) != 0u) bits++;
+// rocPRIM's way, once: call(nullptr, need) asks for the temporary storage's size, which the layout's has to cover; then it runs.
+template <class Call>
+int burst_prim(const Burst &b, Call call)
+{
     size_t need = 0;
-    {
-        rocprim::double_buffer<uint32_t> keys(u32(L.key[0]), u32(L.key[1])), vals(u32(L.val[0]), u32(L.val[1]));
-        BURST_TRY(rocprim::radix_sort_pairs(nullptr, need, keys, vals, npackets, 0u, bits, stream));
-    }
-    if (need > L.temp_bytes) return (int)hipErrorInvalidValue;
-    rocprim::double_buffer<uint32_t> keys(u32(L.key[0]), u32(L.key[1])), vals(u32(L.val[0]), u32(L.val[1]));
-    BURST_TRY(rocprim::radix_sort_pairs(temp, need, keys, vals, npackets, 0u, bits, stream));
-    const uint32_t *const skey = keys.current(), *const sidx = vals.current();
-    // ---- where each packet ends in its channel's string of packets (a scan over all runs: the differences are what counts);
-    // packed decompression: the same of the rooms
-    if (c.packed())
-        hipLaunchKernelGGL(lzs_burst_lens_packed_kernel, dim3(grid), dim3(256), 0, stream, sidx, c.d_in_off, c.d_in_len, c.d_out_off, lens,
-                           decompress ? rooms : (uint64_t *)nullptr, npackets);
-    else
-        hipLaunchKernelGGL(lzs_burst_lens_kernel, dim3(grid), dim3(256), 0, stream, sidx, c.d_in_len, c.in_len, lens, npackets);
-    BURST_TRY(rocprim::inclusive_scan(nullptr, need, lens, ends, (size_t)npackets, rocprim::plus<uint64_t>(), stream));
-    if (need > L.temp_bytes) return (int)hipErrorInvalidValue;
-    BURST_TRY(rocprim::inclusive_scan(temp, need, lens, ends, (size_t)npackets, rocprim::plus<uint64_t>(), stream));
-    if (c.packed() && decompress)
-        BURST_TRY(rocprim::inclusive_scan(temp, need, rooms, room_ends, (size_t)npackets, rocprim::plus<uint64_t>(), stream));
+    BURST_TRY(call(nullptr, need));
+    if (need > b.temp_bytes) return (int)hipErrorInvalidValue;
+    return (int)call(b.temp, need);
+}
 
-    if (!decompress) {
-        uint8_t *const slots = W + L.slots;
-        if (c.packed())
-            hipLaunchKernelGGL(lzs_burst_gather_packed_kernel, dim3(npackets), dim3(256), 0, stream, in, c.d_in_off, c.d_in_len, c.d_out_off,
-                               skey, sidx, (const uint64_t *)ends, (const uint8_t *)d_states, nchannels, slots);
-        else
-            hipLaunchKernelGGL(lzs_burst_gather_kernel, dim3(npackets), dim3(256), 0, stream, in, c.in_stride, c.d_in_len,
-                               c.in_len, skey, sidx, (const uint64_t *)ends, (const uint8_t *)d_states, nchannels, slots);
+int burst_scan(const Burst &b, uint64_t *from, uint64_t *to)
+{
+    return burst_prim(b, [&](void *temp, size_t &need) {
+        return rocprim::inclusive_scan(temp, need, from, to, (size_t)b.npackets, rocprim::plus<uint64_t>(), b.stream); });
+}
+
+// ---- the runs: a stable sort by channel
+int burst_group(Burst &b)
+{
+    hipLaunchKernelGGL(lzs_burst_keys_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.channel, b.nchannels, b.key[0], b.val[0], b.npackets);
+    const unsigned bits = lzs_burst_plan_sort_bits(b.nchannels);
+    rocprim::double_buffer<uint32_t> keys(b.key[0], b.key[1]), vals(b.val[0], b.val[1]);
+    const int e = burst_prim(b, [&](void *temp, size_t &need) {
+        return rocprim::radix_sort_pairs(temp, need, keys, vals, b.npackets, 0u, bits, b.stream); });
+    b.skey = keys.current(); b.sidx = vals.current();
+    return e;
+}
+
+// ---- where each packet ends in its channel's string of packets (a scan over all runs: the differences are what counts); packed
+// decompression: the same of the rooms
+int burst_lengths(const Burst &b)
+{
+    const bool rooms = b.packed() && b.decompress;
+    if (b.packed())
+        hipLaunchKernelGGL(lzs_burst_lens_packed_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.sidx, b.in_off, b.in_len, b.out_off, b.lens,
+                           rooms ? b.rooms : nullptr, b.npackets);
+    else
+        hipLaunchKernelGGL(lzs_burst_lens_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.sidx, b.in_len, b.in_len_uniform, b.lens, b.npackets);
+    BURST_TRY(burst_scan(b, b.lens, b.ends));
+    return rooms ? burst_scan(b, b.rooms, b.room_ends) : 0;
+}
+
+// ---- compression: every packet's history into its work slot, the channel kernel on all packets, each run's last slot to its channel
+int burst_compress(const Burst &b)
+{
+    const dim3 grid(b.npackets);
+    if (b.packed()) {
+        hipLaunchKernelGGL(lzs_burst_gather_packed_kernel, grid, dim3(256), 0, b.stream, b.in, b.in_off, b.in_len, b.out_off, b.skey, b.sidx,
+                           b.ends, b.states, b.nchannels, b.slots);
         BURST_TRY(hipGetLastError());
-        const int e = c.packed() ? lzs_hip_launch_compress_channels_packed(c.d_out, c.d_out_off, d_out_len, c.d_in, c.d_in_off, c.d_in_len,
-                                                                           nullptr, slots, d_status, npackets, stream_)
-                                 : lzs_hip_launch_compress_channels(c.d_out, c.out_stride, c.out_cap, d_out_len, c.d_in, c.in_stride,
-                                                                    c.d_in_len, c.in_len, nullptr, slots, d_status, npackets, stream_);
-        if (e) return e;
-        if (c.packed())
-            hipLaunchKernelGGL(lzs_burst_commit_packed_kernel, dim3(npackets), dim3(128), 0, stream, c.d_in_off, c.d_in_len, c.d_out_off,
-                               skey, sidx, (const uint8_t *)slots, nchannels, (uint8_t *)d_states, npackets);
-        else
-            hipLaunchKernelGGL(lzs_burst_commit_kernel, dim3(npackets), dim3(128), 0, stream, skey, sidx, (const uint8_t *)slots,
-                               nchannels, (uint8_t *)d_states, npackets);
-        return (int)hipGetLastError();
-    }
-    // ---- decompression: the runs by weight, heaviest first, one decoder stream each
-    hipLaunchKernelGGL(lzs_burst_runs_kernel, dim3(grid), dim3(256), 0, stream, skey, (const uint64_t *)ends, u32(L.weight[0]),
-                       u32(L.at[0]), u32(L.run_end), npackets);
-    {
-        rocprim::double_buffer<uint32_t> w(u32(L.weight[0]), u32(L.weight[1])), a(u32(L.at[0]), u32(L.at[1]));
-        BURST_TRY(rocprim::radix_sort_pairs_desc(nullptr, need, w, a, npackets, 0u, 32u, stream));
-    }
-    if (need > L.temp_bytes) return (int)hipErrorInvalidValue;
-    rocprim::double_buffer<uint32_t> w(u32(L.weight[0]), u32(L.weight[1])), a(u32(L.at[0]), u32(L.at[1]));
-    BURST_TRY(rocprim::radix_sort_pairs_desc(temp, need, w, a, npackets, 0u, 32u, stream));
-    const auto runs = [&](const uint32_t *run_key, const uint32_t *run_at) {
-        if (c.packed())
-            return lzs_hip_launch_decompress_runs_packed(c.d_out, c.d_out_off, d_out_len, c.d_in, c.d_in_off, c.d_in_len, room_ends, run_key,
-                                                         run_at, u32(L.run_end), skey, sidx, nchannels, d_states, d_status, npackets, stream_);
-        return lzs_hip_launch_decompress_runs(c.d_out, c.out_stride, c.out_cap, d_out_len, c.d_in, c.in_stride, c.d_in_len, c.in_len,
-                                              run_key, run_at, u32(L.run_end), skey, sidx, nchannels, d_states, d_status, npackets, stream_);
-    };
-    if (split) {
-        // ---- the heavy runs (a prefix of that order, found on the device) by PARSE and RESOLVE, the others by the run decoder
-        // from tables of their own
-        uint16_t *const origins = reinterpret_cast<uint16_t *>(W + L.origins);
-        uint2 *const rec = reinterpret_cast<uint2 *>(W + L.rec);
-        const uint32_t most_runs = npackets <= nchannels ? npackets : nchannels + 1u;     // (the ids out of range are one more)
-        if (c.packed()) {
-            hipLaunchKernelGGL(lzs_burst_split_plan_packed_kernel, dim3(grid), dim3(256), 0, stream, (const uint32_t *)w.current(),
-                               (const uint32_t *)a.current(), split_min, (const uint64_t *)room_ends, origin_cap, u32(L.light_w),
-                               u32(L.light_at), u32(L.nheavy), npackets);
-            hipLaunchKernelGGL(lzs_burst_parse_packed_kernel, dim3(npackets), dim3(64), 0, stream, out, c.d_out_off, d_out_len, in,
-                               c.d_in_off, c.d_in_len, (const uint64_t *)room_ends, skey, sidx, (const uint64_t *)ends,
-                               (const uint32_t *)u32(L.run_end), (const uint8_t *)d_states, nchannels, d_status, origins, rec,
-                               (const uint32_t *)u32(L.nheavy), split_min);
-            hipLaunchKernelGGL(lzs_burst_resolve_packed_kernel, dim3(most_runs), dim3(256), 0, stream, out, c.d_out_off, c.d_in_off,
-                               c.d_in_len, (const uint64_t *)room_ends, (const uint32_t *)a.current(), (const uint32_t *)u32(L.run_end),
-                               skey, sidx, (uint8_t *)d_states, nchannels, (const uint16_t *)origins, (const uint2 *)rec,
-                               (const uint32_t *)u32(L.nheavy));
-        } else {
-            hipLaunchKernelGGL(lzs_burst_split_plan_kernel, dim3(grid), dim3(256), 0, stream, (const uint32_t *)w.current(),
-                               (const uint32_t *)a.current(), split_min, u32(L.light_w), u32(L.light_at), u32(L.nheavy), npackets);
-            hipLaunchKernelGGL(lzs_burst_parse_kernel, dim3(npackets), dim3(64), 0, stream, out, c.out_stride, c.out_cap, d_out_len,
-                               in, c.in_stride, c.d_in_len, c.in_len, skey, sidx, (const uint64_t *)ends,
-                               (const uint32_t *)u32(L.run_end), (const uint8_t *)d_states, nchannels, d_status, origins, rec,
-                               (const uint32_t *)u32(L.nheavy), split_min);
-            hipLaunchKernelGGL(lzs_burst_resolve_kernel, dim3(most_runs), dim3(256), 0, stream, out, c.out_stride, c.out_cap,
-                               (const uint32_t *)a.current(), (const uint32_t *)u32(L.run_end), skey, sidx, (uint8_t *)d_states,
-                               nchannels, (const uint16_t *)origins, (const uint2 *)rec, (const uint32_t *)u32(L.nheavy));
-        }
+        BURST_TRY(lzs_hip_launch_compress_channels_packed(b.out, b.out_off, b.out_len, b.in, b.in_off, b.in_len, nullptr, b.slots, b.status,
+                                                          b.npackets, b.stream));
+        hipLaunchKernelGGL(lzs_burst_commit_packed_kernel, grid, dim3(128), 0, b.stream, b.in_off, b.in_len, b.out_off, b.skey, b.sidx, b.slots,
+                           b.nchannels, b.states, b.npackets);
+    } else {
+        hipLaunchKernelGGL(lzs_burst_gather_kernel, grid, dim3(256), 0, b.stream, b.in, b.in_stride, b.in_len, b.in_len_uniform, b.skey, b.sidx,
+                           b.ends, b.states, b.nchannels, b.slots);
         BURST_TRY(hipGetLastError());
-        return runs(u32(L.light_w), u32(L.light_at));
+        BURST_TRY(lzs_hip_launch_compress_channels(b.out, b.out_stride, b.out_cap, b.out_len, b.in, b.in_stride, b.in_len, b.in_len_uniform,
+                                                   nullptr, b.slots, b.status, b.npackets, b.stream));
+        hipLaunchKernelGGL(lzs_burst_commit_kernel, grid, dim3(128), 0, b.stream, b.skey, b.sidx, b.slots, b.nchannels, b.states, b.npackets);
     }
-    return runs(w.current(), a.current());
+    return (int)hipGetLastError();
+}
+
+// ---- decompression: the runs by weight, heaviest first
+int burst_runs_by_weight(Burst &b)
+{
+    hipLaunchKernelGGL(lzs_burst_runs_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.skey, b.ends, b.weight[0], b.at[0], b.run_end, b.npackets);
+    rocprim::double_buffer<uint32_t> w(b.weight[0], b.weight[1]), a(b.at[0], b.at[1]);
+    const int e = burst_prim(b, [&](void *temp, size_t &need) {
+        return rocprim::radix_sort_pairs_desc(temp, need, w, a, b.npackets, 0u, 32u, b.stream); });
+    b.run_w = w.current(); b.run_at = a.current();
+    return e;
+}
+
+// ---- the heavy runs (a prefix of that order, found on the device) by PARSE and RESOLVE; the others are left in tables of their own
+int burst_split(Burst &b)
+{
+    const dim3 grid(b.grid), packets(b.npackets), runs(lzs_burst_plan_resolve_grid(b.npackets, b.nchannels));
+    if (b.packed()) {
+        hipLaunchKernelGGL(lzs_burst_split_plan_packed_kernel, grid, dim3(256), 0, b.stream, b.run_w, b.run_at, b.split_min, b.room_ends,
+                           b.origin_cap, b.light_w, b.light_at, b.nheavy, b.npackets);
+        hipLaunchKernelGGL(lzs_burst_parse_packed_kernel, packets, dim3(64), 0, b.stream, b.out, b.out_off, b.out_len, b.in, b.in_off, b.in_len,
+                           b.room_ends, b.skey, b.sidx, b.ends, b.run_end, b.states, b.nchannels, b.status, b.origins, b.rec, b.nheavy,
+                           b.split_min);
+        hipLaunchKernelGGL(lzs_burst_resolve_packed_kernel, runs, dim3(256), 0, b.stream, b.out, b.out_off, b.in_off, b.in_len, b.room_ends,
+                           b.run_at, b.run_end, b.skey, b.sidx, b.states, b.nchannels, b.origins, b.rec, b.nheavy);
+    } else {
+        hipLaunchKernelGGL(lzs_burst_split_plan_kernel, grid, dim3(256), 0, b.stream, b.run_w, b.run_at, b.split_min, b.light_w, b.light_at,
+                           b.nheavy, b.npackets);
+        hipLaunchKernelGGL(lzs_burst_parse_kernel, packets, dim3(64), 0, b.stream, b.out, b.out_stride, b.out_cap, b.out_len, b.in, b.in_stride,
+                           b.in_len, b.in_len_uniform, b.skey, b.sidx, b.ends, b.run_end, b.states, b.nchannels, b.status, b.origins, b.rec,
+                           b.nheavy, b.split_min);
+        hipLaunchKernelGGL(lzs_burst_resolve_kernel, runs, dim3(256), 0, b.stream, b.out, b.out_stride, b.out_cap, b.run_at, b.run_end, b.skey,
+                           b.sidx, b.states, b.nchannels, b.origins, b.rec, b.nheavy);
+    }
+    BURST_TRY(hipGetLastError());
+    b.run_w = b.light_w; b.run_at = b.light_at;
+    return 0;
+}
+
+// ---- one decoder stream a run
+int burst_decode_runs(const Burst &b)
+{
+    if (b.packed())
+        return lzs_hip_launch_decompress_runs_packed(b.out, b.out_off, b.out_len, b.in, b.in_off, b.in_len, b.room_ends, b.run_w, b.run_at,
+                                                     b.run_end, b.skey, b.sidx, b.nchannels, b.states, b.status, b.npackets, b.stream);
+    return lzs_hip_launch_decompress_runs(b.out, b.out_stride, b.out_cap, b.out_len, b.in, b.in_stride, b.in_len, b.in_len_uniform, b.run_w,
+                                          b.run_at, b.run_end, b.skey, b.sidx, b.nchannels, b.states, b.status, b.npackets, b.stream);
+}
+
+// One burst: the grouping, then the kernels of the direction.  b: where the packets lie.  split (decompression): the long runs by PARSE and RESOLVE.
+int burst(Burst &b, int decompress, uint32_t *d_out_len, const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
+          void *d_work, uint32_t npackets, int split, uint64_t origin_cap, uint32_t split_min, void *stream)
+{
+    if (npackets == 0) return 0;
+    b.decompress = decompress; b.out_len = d_out_len; b.channel = d_channel; b.states = static_cast<uint8_t *>(d_states); b.status = d_status;
+    b.nchannels = nchannels; b.npackets = npackets; b.grid = (npackets + 255u) / 256u;
+    b.origin_cap = origin_cap; b.split_min = split_min; b.stream = static_cast<hipStream_t>(stream);
+    burst_lay_out(b, d_work);
+    BURST_TRY(burst_group(b));
+    BURST_TRY(burst_lengths(b));
+    if (!decompress) return burst_compress(b);
+    BURST_TRY(burst_runs_by_weight(b));
+    if (split) BURST_TRY(burst_split(b));
+    return burst_decode_runs(b);
 }
 
 }  // namespace
 
-extern "C" size_t lzs_hip_burst_work_bytes(size_t npackets)
-{
-    return burst_layout(npackets).total;
-}
-
 extern "C" int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                              const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                              const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
-                             void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream_)
+                             void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream)
 {
-    const BurstCall c = {d_out, d_in, out_stride, in_stride, out_cap, in_len, d_in_len, nullptr, nullptr};
-    return burst(decompress, c, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets, split, 0, split_min, stream_);
+    Burst b = {(uint8_t *)d_out, (const uint8_t *)d_in, out_stride, in_stride, out_cap, in_len, d_in_len, nullptr, nullptr};
+    return burst(b, decompress, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets, split, 0, split_min, stream);
 }
 
 extern "C" int lzs_hip_burst_packed(int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                                     const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, void *d_states,
-                                    uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, size_t origin_bytes,
-                                    uint32_t split_min, void *stream_)
+                                    uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, int split,
+                                    uint64_t origin_cap, uint32_t split_min, void *stream)
 {
-    const BurstCall c = {d_out, d_in, 0, 0, 0u, 0u, d_in_len, d_in_off, d_out_off};
-    const uint64_t origin_cap = origin_bytes / 2u;
-    return burst(decompress, c, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets,
-                 decompress && origin_cap != 0, origin_cap, split_min, stream_);
+    Burst b = {(uint8_t *)d_out, (const uint8_t *)d_in, 0, 0, 0u, 0u, d_in_len, d_in_off, d_out_off};
+    return burst(b, decompress, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets, split, origin_cap, split_min, stream);
 }

@@ -168,12 +168,11 @@ int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_
                                    const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
                                    const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
                                    uint8_t *d_status, uint32_t npackets, void *stream);
-/* Many packets per channel (lzs_channels_burst.hip; lzs_channels.c checks the arguments): the work area's size, and one burst
- * through compression (decompress 0) or decompression (1) -- the grouping, then the kernels above.  `split` (decompression;
- * the work area then holds lzs_hip_burst_work_bytes() + 2 * npackets * out_cap bytes): the
+/* Many packets per channel (lzs_channels_burst.hip; lzs_channels.c checks the arguments; the work area's layout and size, and
+ * `split` and `split_min`, are lzs_burst_plan.h's): one burst through compression (decompress 0) or decompression (1) -- the
+ * grouping, then the kernels above.  `split` (decompression; the work area then holds the split size): the
  * runs of at least `split_min` compressed bytes are decoded by all their packets at once with per-byte origins and resolved
  * afterwards (lzs_burst_parse_kernel, lzs_burst_resolve_kernel), the others by lzs_hip_launch_decompress_runs. */
-size_t lzs_hip_burst_work_bytes(size_t npackets);
 int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                   const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
@@ -219,9 +218,9 @@ int lzs_hip_launch_compress_channels_packed(void *d_out, const uint64_t *d_out_o
 int lzs_hip_launch_compact_packed(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off,
                                   const uint32_t *d_len, uint32_t nblocks, void *stream);
 /* Packed bursts (lzs_channels_burst.hip; lzs_packed.c checks the arguments): lzs_hip_burst with the packets and their
- * rooms addressed as in the packed calls above.  origin_bytes (decompression): what the work area holds behind
- * lzs_hip_burst_work_bytes(), 0: none; the long runs are split if the sum of the rooms, found on the device, fits it as 16-bit
- * origins.  lzs_hip_launch_decompress_runs_packed is lzs_hip_launch_decompress_runs on such packets; d_room_ends[i] = the sum of the
+ * rooms addressed as in the packed calls above.  split, origin_cap (lzs_burst_plan_split_packed): the work area holds origin_cap
+ * 16-bit origins behind the burst size; the long runs are split if the sum of the rooms, found on the device, fits them.
+ * lzs_hip_launch_decompress_runs_packed is lzs_hip_launch_decompress_runs on such packets; d_room_ends[i] = the sum of the
  * rooms of the packets at sorted positions 0 .. i. */
 int lzs_hip_launch_decompress_runs_packed(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                                           const uint64_t *d_in_off, const uint32_t *d_in_len, const uint64_t *d_room_ends,
@@ -230,8 +229,8 @@ int lzs_hip_launch_decompress_runs_packed(void *d_out, const uint64_t *d_out_off
                                           uint8_t *d_status, uint32_t npackets, void *stream);
 int lzs_hip_burst_packed(int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
                          const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, void *d_states,
-                         uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, size_t origin_bytes,
-                         uint32_t split_min, void *stream);
+                         uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, int split,
+                         uint64_t origin_cap, uint32_t split_min, void *stream);
 
 #ifdef __cplusplus
 }

@@ -54,12 +54,17 @@ typedef struct {
     int      route;                 /* LZS_ROUTE: 0 by size (the default), 1 "device": every call on the device, 2 "host": the small
                                      * calls' host route for every size it can take, and no device needed (lzs_hostcodec.c) */
     int      burst_split_set;       /* LZS_BURST_SPLIT_MIN is given: the burst decoder splits the runs of at least ... */
-    uint32_t burst_split_min;       /* ... this many compressed bytes over the device (0: every run; unset: BURST_SPLIT_MIN_DEFAULT) */
+    uint32_t burst_split_min;       /* ... this many compressed bytes over the device (0: every run; unset: the default of lzs_burst_plan.h) */
 } lzs_env_t;
 LZS_HIDDEN const lzs_env_t *lzs_env(void);
-/* Runs of at least this many compressed bytes are split over the device where the work area allows it (DESIGN.md 3.12 has the
- * sweep: the crossover of both routes on queues with one long run); LZS_BURST_SPLIT_MIN overrides it.  (lzs_channels.c, lzs_packed.c) */
-#define BURST_SPLIT_MIN_DEFAULT 8192u
+/* Checks that the channel calls of lzs_channels.c and lzs_packed.c share: the states; a burst's ids and work area (lzs_channels.c). */
+static inline int check_states(const char *who, const void *d_states)
+{
+    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
+    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
+    return LZS_OK;
+}
+LZS_HIDDEN int check_burst(const char *who, const uint32_t *d_channel, size_t nchannels, const void *d_work, size_t work_bytes, size_t npackets);
 
 #define PIPE_STREAMS 4               /* copy in, copy out, two run streams (lzs_pipeline.c) */
 #define PIPE_EVENTS  14              /* lzs_pipeline.c: EV_COUNT */

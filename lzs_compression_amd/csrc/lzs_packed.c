@@ -9,6 +9,7 @@
  * Offsets and lengths stay on the device: what they say about a single block is the kernels' to check.
  */
 #include "lzs_internal.h"
+#include "lzs_burst_plan.h"
 #include "lzs/lzs_channels.h"
 
 static int offsets_aligned(const char *who, const char *name, const uint64_t *p)
@@ -93,10 +94,8 @@ int lzs_decompress_channels_packed_device(void *d_out, const uint64_t *d_out_off
     const char *who = "lzs_decompress_channels_packed_device";
     if (npackets == 0) return LZS_OK;
     int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
-    if (rc != LZS_OK) return rc;
-    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
-    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
-    rc = require_device();
+    if (rc == LZS_OK) rc = check_states(who, d_states);
+    if (rc == LZS_OK) rc = require_device();
     if (rc != LZS_OK) return rc;
     const int e = lzs_hip_launch_decompress_channels_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
                                                             d_status, (uint32_t)npackets, hip_stream);
@@ -141,24 +140,20 @@ int lzs_compress_channels_packed_device(void *d_out, const uint64_t *d_out_off, 
     const char *who = "lzs_compress_channels_packed_device";
     if (npackets == 0) return LZS_OK;
     int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
-    if (rc != LZS_OK) return rc;
-    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
-    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
-    rc = require_device();
+    if (rc == LZS_OK) rc = check_states(who, d_states);
+    if (rc == LZS_OK) rc = require_device();
     if (rc != LZS_OK) return rc;
     const int e = lzs_hip_launch_compress_channels_packed(d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
                                                           d_status, (uint32_t)npackets, hip_stream);
     return e ? hip_fail(e, who) : LZS_OK;
 }
 
-/* Packed bursts (lzs_channels_burst.hip): the checks of the packed calls above and those of device_burst in
- * lzs_channels.c.  What the work area holds behind the burst size is room for origins: whether the rooms fit it is the device's to
- * see (lzs_burst_split_plan_packed_kernel). */
+/* Packed bursts (lzs_channels_burst.hip): the checks of the packed calls above and a burst's (check_burst).  What the
+ * work area holds behind the burst size is room for origins (lzs_burst_plan.h): whether the rooms fit it is the device's to see
+ * (lzs_burst_split_plan_packed_kernel). */
 size_t lzs_channels_burst_packed_split_work_bytes(size_t npackets, size_t nchannels, uint64_t out_bytes)
 {
-    const size_t base = lzs_channels_burst_work_bytes(npackets, nchannels);
-    if (out_bytes > (uint64_t)((SIZE_MAX - base) / 2u)) return SIZE_MAX;
-    return base + 2u * (size_t)out_bytes;
+    return lzs_burst_plan_packed_split_work_bytes(npackets, nchannels, out_bytes);
 }
 
 static int device_burst_packed(const char *who, int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
@@ -168,24 +163,15 @@ static int device_burst_packed(const char *who, int decompress, void *d_out, con
 {
     if (npackets == 0) return LZS_OK;
     int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
+    if (rc == LZS_OK) rc = check_states(who, d_states);
+    if (rc == LZS_OK) rc = check_burst(who, d_channel, nchannels, d_work, work_bytes, npackets);
+    if (rc == LZS_OK) rc = require_device();
     if (rc != LZS_OK) return rc;
-    if (!d_states) return fail(LZS_E_ARG, "%s: states is NULL", who);
-    if ((uintptr_t)d_states & 3u) return fail(LZS_E_ARG, "%s: states is not 4-byte aligned", who);
-    if (!d_channel) return fail(LZS_E_ARG, "%s: channel is NULL", who);
-    if (nchannels == 0) return fail(LZS_E_ARG, "%s: no channels for %zu packets", who, npackets);
-    if (nchannels > LZS_CHANNELS_MAX) return fail(LZS_E_ARG, "%s: too many channels (%zu)", who, nchannels);
-    if (!d_work) return fail(LZS_E_ARG, "%s: work is NULL", who);
-    if ((uintptr_t)d_work & 255u) return fail(LZS_E_ARG, "%s: work is not 256-byte aligned", who);
-    const size_t need = lzs_channels_burst_work_bytes(npackets, nchannels);
-    if (work_bytes < need)
-        return fail(LZS_E_ARG, "%s: work_bytes %zu is smaller than lzs_channels_burst_work_bytes() = %zu", who, work_bytes, need);
-    rc = require_device();
-    if (rc != LZS_OK) return rc;
+    const lzs_burst_split_t split = lzs_burst_plan_split_packed(decompress, work_bytes - lzs_burst_plan_work_bytes(npackets, nchannels));
     const lzs_env_t *env = lzs_env();
-    const uint32_t split_min = env->burst_split_set ? env->burst_split_min : BURST_SPLIT_MIN_DEFAULT;
     const int e = lzs_hip_burst_packed(decompress, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
-                                       (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, decompress ? work_bytes - need : 0,
-                                       split_min, stream);
+                                       (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, split.split, split.origin_cap,
+                                       lzs_burst_plan_split_min(env->burst_split_set, env->burst_split_min), stream);
     return e ? hip_fail(e, who) : LZS_OK;
 }
 
