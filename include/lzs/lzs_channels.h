@@ -217,6 +217,65 @@ int lzs_decompress_channels_burst_packed_device(void *d_out, const uint64_t *d_o
                                                 const uint32_t *d_channel, void *d_states, size_t nchannels, uint8_t *d_status,
                                                 void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
 
+/*
+ * HISTORY RESETS INSIDE A QUEUE.  RFC 1974 resets a link's history after a Reset-Request / Reset-Ack exchange or a
+ * lost packet, and IPComp-style traffic (RFC 2395) does so in front of every packet.  Setting hist_len to 0 does that between calls;
+ * the four entries below do it inside a burst.  Each takes the arguments of the burst entry it is named after and, directly behind
+ * d_channel, d_flags: a device array of npackets bytes, or NULL.  Only bit 0, LZS_PACKET_RESET, is read; d_flags needs no alignment.
+ *
+ * With d_flags == NULL an entry is the burst entry it extends, byte for byte (the four burst entries above are these with NULL).
+ *
+ * THE RULE is the rank rule of the bursts, extended.  Split the call into ranks, rank k being the k-th packet of every channel in
+ * ascending b, and make one call of lzs_*_channels_device (packed: lzs_*_channels_packed_device) per rank, in order.  Before the
+ * call of rank k, for every packet of that rank that has LZS_PACKET_RESET set, whose channel id is below nchannels and (packed)
+ * whose entry is a block, store 0 to its channel's hist_len.  Every packet's bytes, d_out_len[b], d_status[b] and every channel's
+ * final slot are byte for byte what that sequence gives.  So:
+ *   - a flagged packet is compressed, or decoded, from an empty history, whatever the slot or the packets before it held; in the
+ *     decoder an offset that reaches in front of the flagged packet's own output reads zeros;
+ *   - a flag on the first packet of a channel discards the slot's history;
+ *   - a slot with hist_len > 2047 gives ERROR to the channel's packets before its first flagged block; from that block on the
+ *     channel is a valid, empty one, and it ends the call with a canonical slot (hist_len, the history, zeros behind it);
+ *   - a flag on an id >= nchannels is ignored: that packet gets ERROR as without it;
+ *   - a flag on a packed entry that is not a block is ignored: the entry does nothing at all, and the run goes on behind it with the
+ *     history it had;
+ *   - a flagged packet of no bytes leaves its channel with hist_len 0 and hist[] all zero (until the next packet), and so does a
+ *     flagged decoder packet that produces nothing;
+ *   - a compressed packet cut at its room, or a decoder copy cut at its room, behaves as without flags: a flag changes only the
+ *     history the packet starts from.
+ *
+ * A flagged packet depends on nothing in front of it, so the decoder treats it as the start of a new run: a queue of one channel
+ * in which every packet is flagged decodes like a batch of independent blocks, not like one long run.
+ *
+ * The work areas are those of the burst entries, unchanged in size: lzs_channels_burst_work_bytes(), and for the decoder's split
+ * lzs_channels_burst_split_work_bytes() / lzs_channels_burst_packed_split_work_bytes().  The argument checks are those of the burst
+ * entries, with the entry's own name in lzs_last_error(); npackets == 0 is LZS_OK and touches nothing; without a device a valid call
+ * returns LZS_E_NO_DEVICE.  Asynchronous on hip_stream, no allocation, no synchronisation: safe to capture into a hipGraph, with the
+ * caveat of the calls above.
+ */
+#define LZS_PACKET_RESET 0x01u   /* d_flags[b]: reset the channel's history in front of packet b */
+
+int lzs_compress_channels_burst_flags_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                             const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                             const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, size_t nchannels,
+                                             uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
+
+int lzs_decompress_channels_burst_flags_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                               const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                               const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, size_t nchannels,
+                                               uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets, void *hip_stream);
+
+int lzs_compress_channels_burst_packed_flags_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
+                                                    const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                                    const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, size_t nchannels,
+                                                    uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets,
+                                                    void *hip_stream);
+
+int lzs_decompress_channels_burst_packed_flags_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
+                                                      const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                                      const uint32_t *d_channel, const uint8_t *d_flags, void *d_states,
+                                                      size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes,
+                                                      size_t npackets, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from .api import decompress_channels_packed, decompress_dense, decompress_packed
 from .api import compact_packed, compress_channels_packed, compress_dense, compress_packed, compressed_bounds_packed
 from .api import (channels_burst_packed_split_work_bytes, compress_channels_burst_packed, compress_channels_dense,
                   decompress_channels_burst_packed, decompress_channels_dense)
+from .api import PACKET_RESET
 from . import workload
 
 __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_bytes", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
@@ -30,4 +31,5 @@ __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_byt
            "decompress_channels_packed", "decompress_dense", "decompress_packed", "decompressed_sizes_packed", "offsets_from_sizes",
            "compact_packed", "compress_channels_packed", "compress_dense", "compress_packed", "compressed_bounds_packed",
            "channels_burst_packed_split_work_bytes", "compress_channels_burst_packed", "compress_channels_dense",
-           "decompress_channels_burst_packed", "decompress_channels_dense"]
+           "decompress_channels_burst_packed", "decompress_channels_dense",
+           "PACKET_RESET"]

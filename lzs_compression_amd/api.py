@@ -138,6 +138,13 @@ def lib() -> ctypes.CDLL:
             for name in ("lzs_compress_channels_burst_packed_device", "lzs_decompress_channels_burst_packed_device"):
                 f = getattr(L, name)
                 f.restype, f.argtypes = ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp]
+        if hasattr(L, "lzs_compress_channels_burst_flags_device"):       # (the same: history resets inside a burst)
+            for name in ("lzs_compress_channels_burst_flags_device", "lzs_decompress_channels_burst_flags_device"):
+                f = getattr(L, name)
+                f.restype, f.argtypes = ctypes.c_int, _BURST_DEV[:9] + [_vp] + _BURST_DEV[9:]
+            for name in ("lzs_compress_channels_burst_packed_flags_device", "lzs_decompress_channels_burst_packed_flags_device"):
+                f = getattr(L, name)
+                f.restype, f.argtypes = ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp]
         _lib = L
     return _lib
 
@@ -867,7 +874,19 @@ def channels_burst_split_work_bytes(npackets: int, nchannels: int, out_capacity:
     return int(lib().lzs_channels_burst_split_work_bytes(npackets, nchannels, out_capacity))
 
 
-def _device_burst(fn, x, in_len, channels, states, out_cap, out, out_len, status, work, stream, split=False):
+PACKET_RESET = 1                    # LZS_PACKET_RESET: flags[b] & 1 resets the channel's history in front of packet b
+
+
+def _burst_flags(flags, nb, device):
+    """``flags`` of a burst call, checked: a contiguous CUDA uint8 tensor [npackets], or None."""
+    import torch
+    if flags is not None:
+        assert flags.is_cuda and flags.dtype == torch.uint8 and flags.is_contiguous() and flags.numel() == nb \
+            and flags.device == device, "flags must be a contiguous CUDA uint8 tensor [npackets]"
+    return flags
+
+
+def _device_burst(fn, x, in_len, channels, states, out_cap, out, out_len, status, work, stream, split=False, flags=None):
     import torch
     assert channels is not None and channels.is_cuda and channels.dtype == torch.int32 and channels.is_contiguous() \
         and channels.numel() == x.shape[0], "channels must be a contiguous CUDA int32 tensor [npackets]"
@@ -879,30 +898,37 @@ def _device_burst(fn, x, in_len, channels, states, out_cap, out, out_len, status
             work = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
             _BURST_WORK[str(x.device)] = work
     assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous(), "work must be a contiguous CUDA uint8 tensor"
-    return _device_channels(lambda *a: fn(*a[:10], nch, a[10], work.data_ptr(), work.numel(), *a[11:]), x, in_len, channels,
-                            states, out_cap, out, out_len, status, stream)
+    if _burst_flags(flags, nb, x.device) is None:
+        return _device_channels(lambda *a: fn(*a[:10], nch, a[10], work.data_ptr(), work.numel(), *a[11:]), x, in_len, channels,
+                                states, out_cap, out, out_len, status, stream)
+    fn = getattr(lib(), fn.__name__.replace("_burst_device", "_burst_flags_device"))
+    return _device_channels(lambda *a: fn(*a[:9], flags.data_ptr(), a[9], nch, a[10], work.data_ptr(), work.numel(), *a[11:]), x, in_len,
+                            channels, states, out_cap, out, out_len, status, stream)
 
 
 def compress_channels_burst(x, in_len, channels, states, out_capacity: Optional[int] = None, out=None, out_len=None, status=None,
-                            work=None, stream=None):
+                            work=None, stream=None, flags=None):
     """lzs_compress_channels_burst_device(): as compress_channels, but ``channels`` (CUDA int32, required) may repeat: the packets
     of a channel are taken in row order, each with the history of the ones before it -- what ChannelCodec.compress gives, in one
     call, with no host synchronisation.  An id >= len(states) gives that packet STATUS_ERROR and length 0.  ``work``: a CUDA
     uint8 tensor of channels_burst_work_bytes() bytes or more (default: one per device, kept and reused -- give each stream
-    that runs burst calls at the same time its own).  Returns (slots, lengths int32, status uint8)."""
+    that runs burst calls at the same time its own).  ``flags`` (CUDA uint8 [npackets], or None): a packet with PACKET_RESET set is
+    compressed from an empty history, as if its channel's hist_len had been zeroed in front of it -- a reset inside the queue
+    (lzs_compress_channels_burst_flags_device).  Returns (slots, lengths int32, status uint8)."""
     cap = compressed_max(x.shape[1]) if out_capacity is None else out_capacity
     return _device_burst(lib().lzs_compress_channels_burst_device, x, in_len, channels, states, cap, out, out_len, status, work,
-                         stream)
+                         stream, flags=flags)
 
 
 def decompress_channels_burst(x, in_len, channels, states, out_capacity: int, out=None, out_len=None, status=None, work=None,
-                              stream=None):
+                              stream=None, flags=None):
     """lzs_decompress_channels_burst_device(): the reverse, on the decompressor's states -- what ChannelCodec.decompress gives,
     in one call.  Arguments as compress_channels_burst.  The default work area has channels_burst_split_work_bytes() bytes, with
     which long runs are split over the device; a caller's ``work`` decides by its size (the results are the same).
+    ``flags``: as for compress_channels_burst -- a flagged packet is decoded from an empty history and starts a run of its own.
     Returns (out, lengths int32, status uint8: LZS_D_STATUS_* bits)."""
     return _device_burst(lib().lzs_decompress_channels_burst_device, x, in_len, channels, states, out_capacity, out, out_len,
-                         status, work, stream, split=True)
+                         status, work, stream, split=True, flags=flags)
 
 
 # ------------------------------- packed bursts: many packets per channel, addressed by offsets (lzs_channels.h; DESIGN.md 3.16)
@@ -912,7 +938,7 @@ def channels_burst_packed_split_work_bytes(npackets: int, nchannels: int, out_by
     return int(lib().lzs_channels_burst_packed_split_work_bytes(npackets, nchannels, out_bytes))
 
 
-def _device_burst_packed(fn, data, in_off, channels, states, out, out_off, in_len, out_len, status, work, stream, split):
+def _device_burst_packed(fn, data, in_off, channels, states, out, out_off, in_len, out_len, status, work, stream, split, flags=None):
     import torch
     nb = _packed_output(out, out_off)
     _packed_input(data, in_off, in_len, nb)
@@ -935,41 +961,46 @@ def _device_burst_packed(fn, data, in_off, channels, states, out, out_off, in_le
             work = torch.empty(max(need, 256), dtype=torch.uint8, device=data.device)
             _BURST_WORK[str(data.device)] = work
     assert work.is_cuda and work.dtype == torch.uint8 and work.is_contiguous(), "work must be a contiguous CUDA uint8 tensor"
+    extra = ()
+    if _burst_flags(flags, nb, data.device) is not None:
+        fn = getattr(lib(), fn.__name__.replace("_packed_device", "_packed_flags_device"))
+        extra = (flags.data_ptr(),)
     _check(fn(_ptr(out, out_off), out_off.data_ptr(), out_len.data_ptr(), _ptr(data, in_off), in_off.data_ptr(),
-              None if in_len is None else in_len.data_ptr(), channels.data_ptr(), states.data_ptr(), nch, status.data_ptr(),
+              None if in_len is None else in_len.data_ptr(), channels.data_ptr(), *extra, states.data_ptr(), nch, status.data_ptr(),
               work.data_ptr(), work.numel(), nb, _stream_handle(stream)))
     return out, out_len, status
 
 
 def compress_channels_burst_packed(data, in_off, channels, states, out, out_off, in_len=None, out_len=None, status=None, work=None,
-                                   stream=None):
+                                   stream=None, flags=None):
     """lzs_compress_channels_burst_packed_device(): compress_channels_burst() from packed packets to packed rooms -- a drained
     queue compressed where it lies.  Packet b is data[in_off[b]:in_off[b + 1]] (or ``in_len[b]`` bytes at in_off[b]) on channel
     ``channels[b]`` (CUDA int32, required; ids may repeat, the packets of a channel are taken in order of b) and goes to
     out[out_off[b]:out_off[b + 1]], its room.  ``work``: as for compress_channels_burst.  Returns (out, out_len int32, status uint8:
     0x07, 0x0B where the room cut the packet, STATUS_ERROR for an entry that is not a block, an id >= len(states) or a slot that is
-    no state).  Asynchronous."""
+    no state).  ``flags``: as for compress_channels_burst; a flag on an entry that is not a block is ignored.  Asynchronous."""
     return _device_burst_packed(lib().lzs_compress_channels_burst_packed_device, data, in_off, channels, states, out, out_off, in_len,
-                                out_len, status, work, stream, False)
+                                out_len, status, work, stream, False, flags)
 
 
 def decompress_channels_burst_packed(data, in_off, channels, states, out, out_off, in_len=None, out_len=None, status=None, work=None,
-                                     stream=None):
+                                     stream=None, flags=None):
     """lzs_decompress_channels_burst_packed_device(): the reverse, on the decompressor's states.  Arguments as
     compress_channels_burst_packed.  The default work area has channels_burst_packed_split_work_bytes() bytes for rooms of
     len(out) bytes, with which long runs are split over the device; a caller's ``work`` decides by its size (the results are the
-    same).  Returns (out, out_len int32, status uint8: LZS_D_STATUS_* bits)."""
+    same).  ``flags``: as for compress_channels_burst_packed.  Returns (out, out_len int32, status uint8: LZS_D_STATUS_* bits)."""
     return _device_burst_packed(lib().lzs_decompress_channels_burst_packed_device, data, in_off, channels, states, out, out_off, in_len,
-                                out_len, status, work, stream, True)
+                                out_len, status, work, stream, True, flags)
 
 
-def compress_channels_dense(data, in_off, channels, states, in_len=None, align: int = 16, stream=None):
+def compress_channels_dense(data, in_off, channels, states, in_len=None, align: int = 16, stream=None, flags=None):
     """A drained packet queue compressed into ONE dense byte string of channel packets: compressed_bounds_packed(),
     offsets_from_sizes() at ``align`` for the rooms, one host read of their total, one allocation of the rooms,
     compress_channels_burst_packed() on ``states``, the scan of the lengths, one host read of the dense total, one allocation of
     exactly that, compact_packed().  Returns (dense uint8 [total], offsets int64 [npackets + 1], status uint8 [npackets]); packet b's
     stream is dense[offsets[b]:offsets[b + 1]] -- empty for a packet that got STATUS_ERROR --, and decompress_channels_dense(dense,
-    offsets, channels, peer_states) gives the packets back.  Peak device memory: as compress_dense(), and the burst work area."""
+    offsets, channels, peer_states) gives the packets back -- with the same ``flags`` (as for compress_channels_burst_packed), if any
+    were given.  Peak device memory: as compress_dense(), and the burst work area."""
     import torch
     nb = _packed_input(data, in_off, in_len)
     if nb == 0:
@@ -980,20 +1011,20 @@ def compress_channels_dense(data, in_off, channels, states, in_len=None, align: 
     with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
         rooms = torch.empty(int(room_off[nb].cpu()), dtype=torch.uint8, device=data.device)          # the first host read
         _, _, status = compress_channels_burst_packed(data, in_off, channels, states, rooms, room_off, in_len=in_len, out_len=size,
-                                                      stream=stream)                                 # (the lengths take the bounds' place)
+                                                      stream=stream, flags=flags)                              # (the lengths take the bounds' place)
         offsets = offsets_from_sizes(size, 1, stream=stream)
         dense = torch.empty(int(offsets[nb].cpu()), dtype=torch.uint8, device=data.device)           # the second host read
     compact_packed(rooms, room_off, size, stream=stream, dense=dense, offsets=offsets)
     return dense, offsets, status
 
 
-def decompress_channels_dense(data, in_off, channels, states, in_len=None, align: int = 1, stream=None):
+def decompress_channels_dense(data, in_off, channels, states, in_len=None, align: int = 1, stream=None, flags=None):
     """Packed channel packets decoded into ONE dense byte string by a caller who does not know their sizes:
     decompressed_sizes_packed() -- a packet's size does not depend on its channel's history --, offsets_from_sizes(), one host read
     -- the total, and the first packet that does not end in its end marker --, one allocation of exactly the total,
     decompress_channels_burst_packed() on ``states``.  Returns (dense uint8 [total], offsets int64 [npackets + 1], status uint8
     [npackets]); packet b is dense[offsets[b] : offsets[b] + size[b]].  Raises ValueError naming the first packet that does not end
-    in an end marker, before any state is touched."""
+    in an end marker, before any state is touched.  ``flags``: as for decompress_channels_burst_packed."""
     import torch
     nb = _packed_input(data, in_off, in_len)
     if nb == 0:
@@ -1012,7 +1043,7 @@ def decompress_channels_dense(data, in_off, channels, states, in_len=None, align
         raise ValueError(f"decompress_channels_dense: packet {first_bad} does not end in an end marker (status 0x{its_status:02x})")
     dense = torch.empty(total, dtype=torch.uint8, device=data.device)
     decompress_channels_burst_packed(data, in_off, channels, states, dense, offsets, in_len=in_len, out_len=size, status=status,
-                                     stream=stream)
+                                     stream=stream, flags=flags)
     return dense, offsets, status
 
 
@@ -1039,10 +1070,13 @@ class ChannelCodec:
         self.enc_states = new_channel_states(nchannels, device)
         self.dec_states = new_channel_states(nchannels, device)
 
-    def _run(self, call, states, x, in_len, channels, out_cap, stream):
+    def _run(self, call, states, x, in_len, channels, out_cap, stream, resets=None):
         import torch
         ids = np.asarray(channels, dtype=np.int64).reshape(-1)
         nb = x.shape[0]
+        rs = np.zeros(nb, dtype=bool) if resets is None else (np.asarray(resets, dtype=np.int64).reshape(-1) & PACKET_RESET) != 0
+        assert rs.size == nb, "resets: one entry a packet"
+
         assert ids.size == nb and (nb == 0 or (ids.min() >= 0 and ids.max() < states.shape[0])), "channel ids out of range"
         out = torch.empty((nb, (max(out_cap, 1) + 15) // 16 * 16), dtype=torch.uint8, device=x.device)
         out_len = torch.empty(nb, dtype=torch.int32, device=x.device)
@@ -1050,6 +1084,10 @@ class ChannelCodec:
         rank = _occurrence_rank(ids)
         for r in range(int(rank.max()) + 1 if nb else 0):
             sel = np.nonzero(rank == r)[0]
+            hit = ids[sel][rs[sel]]
+            if hit.size:             # the reset: hist_len = 0 in front of this launch, in stream order
+                with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+                    states[:, :4].index_fill_(0, torch.from_numpy(hit).to(x.device), 0)
             if sel.size == nb:       # every id once: one launch over the caller's own tensors
                 call(x, in_len, torch.from_numpy(ids.astype(np.int32)).to(x.device), states, out_cap, out, out_len, status, stream)
                 break
@@ -1061,14 +1099,16 @@ class ChannelCodec:
             status[idx] = st
         return out, out_len, status
 
-    def compress(self, x, in_len, channels, out_capacity: Optional[int] = None, stream=None):
-        """Row b of ``x`` on channel ``channels[b]`` (a host sequence; ids may repeat).  Returns (slots, lengths, status)."""
+    def compress(self, x, in_len, channels, out_capacity: Optional[int] = None, stream=None, resets=None):
+        """Row b of ``x`` on channel ``channels[b]`` (a host sequence; ids may repeat).  ``resets`` (a host sequence, one entry a
+        packet, or None): where PACKET_RESET is set the channel's hist_len is zeroed in front of the launch that takes the packet --
+        the rule of the burst calls' ``flags``, written out.  Returns (slots, lengths, status)."""
         cap = compressed_max(x.shape[1]) if out_capacity is None else out_capacity
         return self._run(lambda *a: compress_channels(*a[:4], out_capacity=a[4], out=a[5], out_len=a[6], status=a[7], stream=a[8]),
-                         self.enc_states, x, in_len, channels, cap, stream)
+                         self.enc_states, x, in_len, channels, cap, stream, resets)
 
-    def decompress(self, x, in_len, channels, out_capacity: int, stream=None):
-        """The reverse on the decompressor states.  Returns (out, lengths, status)."""
+    def decompress(self, x, in_len, channels, out_capacity: int, stream=None, resets=None):
+        """The reverse on the decompressor states; ``resets`` as for compress.  Returns (out, lengths, status)."""
         return self._run(lambda *a: decompress_channels(*a[:4], out_capacity=a[4], out=a[5], out_len=a[6], status=a[7], stream=a[8]),
-                         self.dec_states, x, in_len, channels, out_capacity, stream)
+                         self.dec_states, x, in_len, channels, out_capacity, stream, resets)
 

@@ -1,17 +1,17 @@
 // kernels/burst_gather.inc -- the body of lzs_burst_gather_kernel and lzs_burst_gather_packed_kernel (lzs_channels_burst.hip), included
 // inside each (as text, as kernels/size_walk.inc is: the strided kernel keeps its code as it was).  It expects, in scope: skey, sidx,
-// ends, states, nchannels, work_slots, and the macros BURST_LEN(p) -- packet p's length, 0 for an entry that is not a block -- and
+// ends, states, nchannels, work_slots, rt, and the macros BURST_LEN(p) -- packet p's length, 0 for an entry that is not a block -- and
 // BURST_SRC(p) -- where its bytes lie.
     const uint32_t i = blockIdx.x, t = threadIdx.x;
     const uint32_t key = skey[i], p = sidx[i];
     uint32_t *const slot = reinterpret_cast<uint32_t *>(work_slots + (size_t)p * kStateBytes);
     const uint8_t *const st = states + (size_t)(key < nchannels ? key : 0u) * kStateBytes;
-    const uint32_t hl = key < nchannels ? *reinterpret_cast<const uint32_t *>(st) : ~0u;
+    const uint32_t start = run_first(rt.rkey, i, rt.rkey[i]);
+    const uint32_t hl = key < nchannels ? (run_is_fresh(rt, start) ? 0u : *reinterpret_cast<const uint32_t *>(st)) : ~0u;
     if (hl > kWindow) {
         if (t == 0) slot[0] = ~0u;
         return;
     }
-    const uint32_t start = run_first(skey, i, key);
     const uint64_t e = i ? ends[i - 1u] : 0u, s = start ? ends[start - 1u] : 0u;
     const uint32_t hp = (uint32_t)(e - s < kWindow ? e - s : kWindow);     // from the run's earlier packets ...
     const uint32_t hs = hl < kWindow - hp ? hl : kWindow - hp;              // ... and from the slot, in front of them

@@ -1,6 +1,6 @@
 // kernels/burst_parse.inc -- the body of lzs_burst_parse_kernel and lzs_burst_parse_packed_kernel (lzs_channels_burst.hip), included
 // inside each (as text, as kernels/size_walk.inc is: the strided kernel keeps its code as it was).  It expects, in scope: out_len,
-// skey, sidx, ends, run_end, states, nchannels, status, origins, rec, nheavy, split_min, out_cap after BURST_PACKET(p) -- the
+// skey, sidx, ends, run_end, states, nchannels, status, origins, rec, nheavy, split_min, rt (the runs: kernels/common.inc), out_cap after BURST_PACKET(p) -- the
 // packet's room --, and the macros BURST_PACKET(p) -- statements that look packet p up and answer an entry that is not a block --,
 // BURST_LEN(p), BURST_SRC(p), BURST_DST(p) -- its length and where it lies and goes -- and BURST_ORIGIN_AT(i) -- where the origins of
 // the packet at sorted position i begin.
@@ -9,12 +9,12 @@
     if (*nheavy == 0u) return;
     const uint32_t i = blockIdx.x, lane = threadIdx.x;
     const uint32_t key = skey[i];
-    const uint32_t start = run_first(skey, i, key);
+    const uint32_t start = run_first(rt.rkey, i, rt.rkey[i]);
     const uint32_t end = run_end[start];
     const uint64_t bytes = ends[end - 1u] - (start ? ends[start - 1u] : 0u);
     if (!run_is_heavy((uint32_t)(bytes < 0xFFFFFFFEull ? bytes : 0xFFFFFFFEull) + 1u, split_min)) return;
     const uint32_t p = sidx[i];
-    const uint32_t hl = key < nchannels ? *reinterpret_cast<const uint32_t *>(states + (size_t)key * kStateBytes) : ~0u;
+    const uint32_t hl = key < nchannels ? (run_is_fresh(rt, start) ? 0u : *reinterpret_cast<const uint32_t *>(states + (size_t)key * kStateBytes)) : ~0u;
     if (hl > kWindow) {                                                    // not a channel, not a state
         if (lane == 0) {
             out_len[p] = 0;

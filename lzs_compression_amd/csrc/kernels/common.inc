@@ -50,6 +50,32 @@ __device__ __forceinline__ bool packed_entry(const uint64_t *in_off, const uint3
     return ok;
 }
 
+// Bursts with packet flags (include/lzs/lzs_channels.h LZS_PACKET_RESET; DESIGN.md 3.18): a reset starts a new run, so a channel may
+// have several.  The decoders' tables by sorted position: rkey[i] = the run's id (1-based, ascending), rmark[i] = kRunStart at a run's
+// first position, | kRunFresh where the run starts from an empty history and reads no slot; skey[i] = the channel.  Without flags
+// rmark is null: a run per channel, from its slot, back to its slot.
+constexpr uint32_t kRunStart = 1u, kRunFresh = 2u;
+
+struct RunTables {
+    const uint32_t *rkey = nullptr, *rmark = nullptr;
+    uint8_t *stage = nullptr;                                      // staging slots, lzs_burst_plan_stage_slot() of the run
+};
+
+__device__ __forceinline__ bool run_is_fresh(const RunTables &rt, uint32_t at) { return rt.rmark != nullptr && (rt.rmark[at] & kRunFresh) != 0u; }
+
+// Where the run at sorted positions [at, end) of n, of channel `key` in range whose slot is `st`, leaves its final history: nowhere
+// (null) unless it is its channel's last; in the slot if it is also the first -- the workgroup that read the slot is the one that
+// writes it --; otherwise in a staging slot, which lzs_burst_stage_commit_kernel copies to the channel after every decode kernel
+// of the call has ended: no workgroup writes a slot that another may still read.
+__device__ __forceinline__ uint8_t *run_commit_to(const RunTables &rt, const uint32_t *skey, uint32_t at, uint32_t end, uint32_t n,
+                                                  uint32_t key, uint8_t *st)
+{
+    if (rt.rmark == nullptr) return st;
+    if (end < n && skey[end] == key) return nullptr;
+    if (at == 0u || skey[at - 1u] != key) return st;
+    return rt.stage + (size_t)((rt.rkey[at] - 2u) / 2u) * kChanStateBytes;
+}
+
 // A value the optimiser may not look through (keeps a select a select, a compare a compare).
 template <class T> __device__ __forceinline__ T opaque(T x) { asm volatile("" : "+v"(x)); return x; }
 

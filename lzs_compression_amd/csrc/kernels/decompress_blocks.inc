@@ -93,9 +93,11 @@ struct DecChan {
     // RUN (lzs_decompress_runs_grp_kernel, CHAN as well): stream b is a RUN of one channel's packets, decoded one after the
     // other in the same window.  The packets sorted by channel (skey / sidx: channel id -- nchannels for one out of range --
     // and packet at each sorted position); run b starts at sorted position run_at[b] and ends before run_end[run_at[b]];
-    // run_key[b] == 0: there is no run b.
+    // run_key[b] == 0: there is no run b.  rt (calls with packet flags): a channel may have several runs -- one that starts
+    // from a reset has an empty history whatever the slot holds, and only the channel's last run leaves a history (run_commit_to).
     const uint32_t *run_key = nullptr, *run_at = nullptr, *run_end = nullptr, *skey = nullptr, *sidx = nullptr;
     uint32_t nchannels = 0;
+    RunTables rt;
 };
 
 // (CHAN) hist[0, H) of the state slot = the H window bytes before position cpos, hist[H, 2048) = 0 -- the bytes the compressor
@@ -228,6 +230,7 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
     uint8_t *cst = nullptr;                                        // CHAN: the stream's state slot ...
     uint32_t hlen = 0;                                             // ... and its history's length (> 2047: not a state)
     uint32_t r_at = 0, r_end = 0;                                  // RUN: the run's sorted positions
+    uint8_t *r_commit = nullptr;                                   // RUN: where its final history goes (null: nowhere)
     uint64_t pk_from = 0, pk_to = 0;                               // PACKED: the entry's offsets, its length and its room
     uint32_t pk_n = 0, pk_room = 0;
     bool pk_block = false;
@@ -241,7 +244,8 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
             const uint32_t c = ch.skey[r_at];
             if (c < ch.nchannels) {
                 cst = ch.states + (size_t)c * kChanStateBytes;
-                hlen = *reinterpret_cast<const uint32_t *>(cst);
+                hlen = run_is_fresh(ch.rt, r_at) ? 0u : *reinterpret_cast<const uint32_t *>(cst);
+                r_commit = run_commit_to(ch.rt, ch.skey, r_at, r_end, nblocks, c, cst);
             }
         }
     } else if constexpr (CHAN) {
@@ -756,10 +760,10 @@ __device__ __forceinline__ void lzs_decompress_blocks_grp(DecGroupLds &L, uint8_
     // (RUN) the run's history goes back once, at its end (PACKED: not if no packet of the run was a block -- the slot stays as it is,
     // byte for byte, as after the packed calls rank by rank, which look at no slot for such entries)
     if constexpr (RUN) {
-        if (live_run && (!PACKED || any_block)) {
+        if (live_run && r_commit != nullptr && (!PACKED || any_block)) {
             const uint32_t H = min(hlen + produced, kWindow);
-            dec_put_history(cst, ring8, run_pos, H, j);
-            if (j == 0u) *reinterpret_cast<uint32_t *>(cst) = H;
+            dec_put_history(r_commit, ring8, run_pos, H, j);
+            if (j == 0u) *reinterpret_cast<uint32_t *>(r_commit) = H;
         }
     }
 }
@@ -836,7 +840,7 @@ void lzs_decompress_runs_grp_kernel(uint8_t *__restrict__ out, size_t out_stride
                                     const uint32_t *__restrict__ run_key, const uint32_t *__restrict__ run_at,
                                     const uint32_t *__restrict__ run_end, const uint32_t *__restrict__ skey,
                                     const uint32_t *__restrict__ sidx, uint32_t nchannels, uint8_t *__restrict__ states,
-                                    uint8_t *__restrict__ status, uint32_t nruns, uint32_t per_wave)
+                                    uint8_t *__restrict__ status, uint32_t nruns, uint32_t per_wave, RunTables rt)
 {
     __shared__ DecGroupLds L;
     uint64_t total = 0, blocks = 0;
@@ -855,6 +859,7 @@ void lzs_decompress_runs_grp_kernel(uint8_t *__restrict__ out, size_t out_stride
     DecChan ch;
     ch.states = states; ch.status = status;
     ch.run_key = run_key; ch.run_at = run_at; ch.run_end = run_end; ch.skey = skey; ch.sidx = sidx; ch.nchannels = nchannels;
+    ch.rt = rt;
     if (two)       lzs_decompress_blocks_grp<true, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
     else if (wide) lzs_decompress_blocks_grp<false, true, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);
     else           lzs_decompress_blocks_grp<false, false, false, true, true>(L, out, out_stride, out_cap, out_len, in, in_stride, in_len, in_len_uniform, nruns, 0u, per_wave, ch);

@@ -52,7 +52,7 @@ void lzs_decompress_runs_packed_grp_kernel(uint8_t *__restrict__ out, const uint
                                            const uint32_t *__restrict__ run_key, const uint32_t *__restrict__ run_at,
                                            const uint32_t *__restrict__ run_end, const uint32_t *__restrict__ skey,
                                            const uint32_t *__restrict__ sidx, uint32_t nchannels, uint8_t *__restrict__ states,
-                                           uint8_t *__restrict__ status, uint32_t nruns)
+                                           uint8_t *__restrict__ status, uint32_t nruns, RunTables rt)
 {
     __shared__ DecGroupLds L;
     uint64_t total = 0, full = 0;
@@ -72,6 +72,7 @@ void lzs_decompress_runs_packed_grp_kernel(uint8_t *__restrict__ out, const uint
     DecChan ch;
     ch.states = states; ch.status = status;
     ch.run_key = run_key; ch.run_at = run_at; ch.run_end = run_end; ch.skey = skey; ch.sidx = sidx; ch.nchannels = nchannels;
+    ch.rt = rt;
     if (two)       lzs_decompress_blocks_grp<true, false, false, true, true, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nruns, 0u, kDecGroups, ch, pk);
     else if (wide) lzs_decompress_blocks_grp<false, true, false, true, true, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nruns, 0u, kDecGroups, ch, pk);
     else           lzs_decompress_blocks_grp<false, false, false, true, true, true>(L, out, 0, 0u, out_len, in, 0, in_len, 0u, nruns, 0u, kDecGroups, ch, pk);

@@ -27,10 +27,16 @@
  * A packed decode has the rooms by sorted position and their scan there as well (16 bytes a packet more), and its origins lie
  * room by room: as many as the caller's work area holds behind `total`.
  * The six tables end before the slots do -- 256 + 32 n bytes and five roundings against 2112 n -- which the table's rows hold
- * at every n they have. */
+ * at every n they have.
+ * A call with packet flags (history resets) has more runs than channels.  Its start marks lie in weight[0] until
+ * they are scanned -- no direction has written it by then --, the run ids and the runs' records in the halves of key[] and val[]
+ * the channel sort left unused (which halves is the sort's to say: burst_group).  Decompression stages the final slot
+ * of every channel that has a second run behind its tables, `stage_slots` slots at `stage`: a second run needs a second packet,
+ * so n / 2 slots do, and they end before the slots' region does (tests/cpu_shim/burst_flags_plan_check.c). */
 typedef struct {
     size_t slots, key[2], val[2], lens, ends, weight[2], at[2], run_end, temp, temp_bytes, total;
     size_t light_w, light_at, rec, nheavy, rooms, room_ends, origins;
+    size_t stage, stage_slots, stage_end, marks;
 } lzs_burst_layout_t;
 
 static inline size_t lzs_burst_up(size_t x) { return (x + LZS_BURST_ALIGN - 1u) / LZS_BURST_ALIGN * LZS_BURST_ALIGN; }
@@ -60,6 +66,10 @@ static inline lzs_burst_layout_t lzs_burst_layout(size_t n)
     L.rooms = lzs_burst_take(&o, 8u * n);
     L.room_ends = lzs_burst_take(&o, 8u * n);
     L.origins = L.total;
+    L.stage_slots = n / 2u;
+    L.stage = lzs_burst_take(&o, L.stage_slots * LZS_BURST_SLOT_BYTES);
+    L.stage_end = o;
+    L.marks = L.weight[0];
     return L;
 }
 
@@ -104,6 +114,16 @@ static inline uint32_t lzs_burst_plan_resolve_grid(uint32_t npackets, uint32_t n
 {
     return npackets <= nchannels ? npackets : nchannels + 1u;
 }
+
+/* With packet flags a reset starts a run: as many runs as packets there can be.  Without them the grid above. */
+static inline uint32_t lzs_burst_plan_resolve_grid_flags(uint32_t npackets, uint32_t nchannels, int flags)
+{
+    return flags ? npackets : lzs_burst_plan_resolve_grid(npackets, nchannels);
+}
+
+/* The staging slot of a channel whose last run is run `run` of the call (0-based, in sorted order) and not its first: two such
+ * channels' last runs lie at least two runs apart and none is run 0, so (run - 1) / 2 is one slot each, below npackets / 2. */
+static inline uint32_t lzs_burst_plan_stage_slot(uint32_t run) { return (run - 1u) / 2u; }
 
 /* Whether the decoder splits its long runs (PARSE and RESOLVE), and over how many 16-bit origins behind the burst part of the
  * work area (packed: whether the rooms fit them is the device's to see, lzs_burst_split_plan_packed_kernel).  The compressor

@@ -73,7 +73,7 @@ size_t lzs_channels_burst_split_work_bytes(size_t npackets, size_t nchannels, si
 /* Many packets per channel (lzs_channels_burst.hip). */
 static int device_burst(const char *who, int decompress, void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
                         const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len, const uint32_t *d_channel,
-                        void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets,
+                        const uint8_t *d_flags, void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets,
                         void *stream)
 {
     if (npackets == 0) return LZS_OK;
@@ -84,9 +84,28 @@ static int device_burst(const char *who, int decompress, void *d_out, size_t out
     const lzs_burst_split_t split = lzs_burst_plan_split_strided(decompress, work_bytes, npackets, nchannels, cap32);
     const lzs_env_t *env = lzs_env();
     const int e = lzs_hip_burst(decompress, d_out, out_stride, cap32, d_out_len, d_in, in_stride, d_in_len, (uint32_t)in_len,
-                                d_channel, d_states, (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, split.split,
+                                d_channel, d_flags, d_states, (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, split.split,
                                 lzs_burst_plan_split_min(env->burst_split_set, env->burst_split_min), stream);
     return e ? hip_fail(e, who) : LZS_OK;
+}
+
+/* The burst entries are the flags entries without flags (lzs_channels.h, LZS_PACKET_RESET): one path, one set of checks. */
+int lzs_compress_channels_burst_flags_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                             const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                             const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, size_t nchannels,
+                                             uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
+{
+    return device_burst("lzs_compress_channels_burst_flags_device", 0, d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len,
+                        in_len, d_channel, d_flags, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+}
+
+int lzs_decompress_channels_burst_flags_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
+                                               const void *d_in, size_t in_stride, const uint32_t *d_in_len, size_t in_len,
+                                               const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, size_t nchannels,
+                                               uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
+{
+    return device_burst("lzs_decompress_channels_burst_flags_device", 1, d_out, out_stride, out_cap, d_out_len, d_in, in_stride,
+                        d_in_len, in_len, d_channel, d_flags, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_compress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
@@ -95,7 +114,7 @@ int lzs_compress_channels_burst_device(void *d_out, size_t out_stride, size_t ou
                                        void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
 {
     return device_burst("lzs_compress_channels_burst_device", 0, d_out, out_stride, out_cap, d_out_len, d_in, in_stride, d_in_len,
-                        in_len, d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+                        in_len, d_channel, NULL, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_decompress_channels_burst_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,
@@ -104,7 +123,7 @@ int lzs_decompress_channels_burst_device(void *d_out, size_t out_stride, size_t 
                                          void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
 {
     return device_burst("lzs_decompress_channels_burst_device", 1, d_out, out_stride, out_cap, d_out_len, d_in, in_stride,
-                        d_in_len, in_len, d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+                        d_in_len, in_len, d_channel, NULL, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_decompress_channels_device(void *d_out, size_t out_stride, size_t out_cap, uint32_t *d_out_len,

@@ -16,6 +16,13 @@
 // arrays on the device.  The kernels that look at a packet's bytes exist in both forms from one body each (BurstIo, PACKED); the
 // compressor is lzs_hip_launch_compress_channels_packed, the run decoder lzs_hip_launch_decompress_runs_packed.
 //
+// Packet flags (lzs_*_channels_burst*_flags_device): a packet flagged LZS_PACKET_RESET starts from an empty history,
+// so it depends on nothing before it and STARTS A NEW RUN.  The start marks -- a channel's first position, or a flagged block of a
+// channel in range -- are scanned into run ids (rkey[], ascending by sorted position like skey[]), and every place that looks for a
+// run's borders searches rkey[] where it searched skey[]; without flags rkey is skey and rmark null, and every kernel does what it
+// did.  A run that a reset started reads no slot; only a channel's last run leaves a history, and where that is not also its first
+// run it goes to a staging slot that a kernel behind all the others copies to the channel (run_commit_to, kernels/common.inc).
+//
 // (<cstring> and the HIP runtime before rocPRIM: its texture cache iterator uses memset in host code.)
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -149,17 +156,68 @@ __global__ __launch_bounds__(256) void lzs_burst_lens_packed_kernel(const uint32
     if (rooms) rooms[i] = k.cap;
 }
 
+// (packet flags) start[i] = 1 where a run starts at sorted position i -- the first of its channel, or a flagged packet of a channel
+// in range that is a block --, 0 elsewhere: their inclusive scan is the run id of every position.  rmark[i]: kRunStart, kRunFresh.
+template <bool PACKED>
+__device__ __forceinline__ void burst_marks(const BurstIo &io, const uint8_t *__restrict__ flags, const uint32_t *__restrict__ skey,
+                                            const uint32_t *__restrict__ sidx, uint32_t nchannels, uint32_t *__restrict__ start,
+                                            uint32_t *__restrict__ rmark, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t key = skey[i], p = sidx[i];
+    const bool first = i == 0u || skey[i - 1u] != key;
+    const bool reset = (flags[p] & 1u) != 0u && key < nchannels && burst_packet<PACKED>(io, p).block;
+    start[i] = first || reset ? 1u : 0u;
+    rmark[i] = (first || reset ? kRunStart : 0u) | (reset ? kRunFresh : 0u);
+}
+
+__global__ __launch_bounds__(256) void lzs_burst_marks_kernel(const uint8_t *__restrict__ flags, const uint32_t *__restrict__ skey,
+                                                              const uint32_t *__restrict__ sidx, uint32_t nchannels,
+                                                              uint32_t *__restrict__ start, uint32_t *__restrict__ rmark, uint32_t n)
+{
+    burst_marks<false>(BurstIo{}, flags, skey, sidx, nchannels, start, rmark, n);
+}
+
+__global__ __launch_bounds__(256) void lzs_burst_marks_packed_kernel(const uint64_t *__restrict__ in_off, const uint32_t *__restrict__ in_len,
+                                                                     const uint64_t *__restrict__ out_off, const uint8_t *__restrict__ flags,
+                                                                     const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
+                                                                     uint32_t nchannels, uint32_t *__restrict__ start,
+                                                                     uint32_t *__restrict__ rmark, uint32_t n)
+{
+    burst_marks<true>(burst_packed(nullptr, in_off, in_len, nullptr, out_off), flags, skey, sidx, nchannels, start, rmark, n);
+}
+
+// (packet flags, decompression) One workgroup per sorted position: where the last run of a channel that has several starts, its
+// staging slot goes to the channel -- after every kernel that may read that channel's slot has ended (run_commit_to).  Such a run
+// was started by a reset, so it is of a channel in range, holds a block and was decoded: its staging slot was written.
+__global__ __launch_bounds__(128) void lzs_burst_stage_commit_kernel(const uint32_t *__restrict__ skey, RunTables rt,
+                                                                     uint8_t *__restrict__ states, uint32_t n)
+{
+    const uint32_t i = blockIdx.x;
+    if ((rt.rmark[i] & kRunStart) == 0u) return;
+    const uint32_t key = skey[i];
+    if (i == 0u || skey[i - 1u] != key) return;                            // the channel's first run: it wrote the slot itself, if it is the last
+    const uint32_t end = run_last_end(rt.rkey, i, n, rt.rkey[i]);
+    if (end < n && skey[end] == key) return;
+    const uint32_t *const from = reinterpret_cast<const uint32_t *>(run_commit_to(rt, skey, i, end, n, key, nullptr));
+    uint32_t *const to = reinterpret_cast<uint32_t *>(states + (size_t)key * kStateBytes);
+    for (uint32_t w = threadIdx.x; w < 512u; w += 128u) to[kHistAt / 4u + w] = from[kHistAt / 4u + w];
+    if (threadIdx.x == 0) to[0] = from[0];
+}
+
 // One workgroup per sorted position i: the history packet p = sidx[i] is compressed with, into work slot p -- the last
 // H <= 2047 bytes of (the channel's slot | the packets at sorted positions [start, i)), where `start` begins the run.  With
 // ends[] the inclusive scan of the lengths, the run's earlier packets are the bytes [ends[start - 1], ends[i - 1]) of one
 // string; a history byte there is found by binary search over ends[start, i) (a run of 40-byte packets needs 50 of them, a
 // packet of 0 bytes none).  A channel id out of range or a slot that is not a state: hist_len = ~0, which the channel kernel
-// answers with ERROR, and the slot is not committed.
+// answers with ERROR, and the slot is not committed.  rt (packet flags): the run is the one of rkey[], and one that a reset
+// started has no slot in front of it -- the slot is not read, whatever it holds.
 __global__ __launch_bounds__(256) void lzs_burst_gather_kernel(const uint8_t *__restrict__ in, size_t in_stride,
                                                                const uint32_t *__restrict__ in_len, uint32_t in_len_uniform,
                                                                const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                                                                const uint64_t *__restrict__ ends, const uint8_t *__restrict__ states,
-                                                               uint32_t nchannels, uint8_t *__restrict__ work_slots)
+                                                               uint32_t nchannels, uint8_t *__restrict__ work_slots, RunTables rt)
 {
 #define BURST_LEN(p) burst_len(in_len, in_len_uniform, (p))
 #define BURST_SRC(p) (in + (size_t)(p) * in_stride)
@@ -172,7 +230,7 @@ __global__ __launch_bounds__(256) void lzs_burst_gather_packed_kernel(const uint
                                                                       const uint32_t *__restrict__ in_len, const uint64_t *__restrict__ out_off,
                                                                       const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                                                                       const uint64_t *__restrict__ ends, const uint8_t *__restrict__ states,
-                                                                      uint32_t nchannels, uint8_t *__restrict__ work_slots)
+                                                                      uint32_t nchannels, uint8_t *__restrict__ work_slots, RunTables rt)
 {
     const BurstIo io = burst_packed(in, in_off, in_len, nullptr, out_off);
 #define BURST_LEN(p) burst_packet<true>(io, (p)).n
@@ -187,6 +245,8 @@ __global__ __launch_bounds__(256) void lzs_burst_gather_packed_kernel(const uint
 // PACKED: an entry that is not a block leaves its work slot as the gather wrote it -- the history behind the blocks before it --,
 // so the last slot is the run's whatever its last entry is; but a run with no block at all is not committed: its channel's slot
 // stays as it is byte for byte (the packed call looks at no slot for such an entry), not rewritten in canonical form.
+// Packet flags change nothing here: the last position of a channel is the last of its last run, whose work slot holds that run's
+// history alone; and a run that a reset started begins with a block, so the walk back finds one inside it.
 template <bool PACKED>
 __device__ __forceinline__ void burst_commit(const BurstIo &io, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                                              const uint8_t *__restrict__ work_slots, uint32_t nchannels,
@@ -312,7 +372,7 @@ __global__ __launch_bounds__(64) void lzs_burst_parse_kernel(uint8_t *__restrict
                                                              const uint32_t *__restrict__ run_end, const uint8_t *__restrict__ states,
                                                              uint32_t nchannels, uint8_t *__restrict__ status,
                                                              uint16_t *__restrict__ origins, uint2 *__restrict__ rec,
-                                                             const uint32_t *__restrict__ nheavy, uint32_t split_min)
+                                                             const uint32_t *__restrict__ nheavy, uint32_t split_min, RunTables rt)
 {
 #define BURST_PACKET(p)
 #define BURST_LEN(p) burst_len(in_len, in_len_uniform, (p))
@@ -335,7 +395,7 @@ __global__ __launch_bounds__(64) void lzs_burst_parse_packed_kernel(uint8_t *__r
                                                                     const uint32_t *__restrict__ run_end, const uint8_t *__restrict__ states,
                                                                     uint32_t nchannels, uint8_t *__restrict__ status,
                                                                     uint16_t *__restrict__ origins, uint2 *__restrict__ rec,
-                                                                    const uint32_t *__restrict__ nheavy, uint32_t split_min)
+                                                                    const uint32_t *__restrict__ nheavy, uint32_t split_min, RunTables rt)
 {
     const BurstIo io = burst_packed(in, in_off, in_len, out, out_off, room_ends);
     // (one that is not a block: nothing of it is read or written)
@@ -373,12 +433,14 @@ __global__ __launch_bounds__(64) void lzs_burst_parse_packed_kernel(uint8_t *__r
 // produced) bytes are the channel's new history (COMMIT).  Runs that are not a state's were answered by PARSE: not touched.
 // PACKED: a packet's output and its origins are found through the entries, and a run none of whose entries is a block (rec = {0, 1}
 // throughout) is not committed: its slot stays as it is byte for byte.
+// rt (packet flags): a run that a reset started begins with the ring all zero and reads no slot, and the run's history goes where
+// run_commit_to says -- nowhere, the slot, or a staging slot.
 template <bool PACKED>
 __device__ __forceinline__ void burst_resolve(const BurstIo &io, const uint32_t *__restrict__ run_at, const uint32_t *__restrict__ run_end,
                                               const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                                               uint8_t *__restrict__ states, uint32_t nchannels,
                                               const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
-                                              const uint32_t *__restrict__ nheavy)
+                                              const uint32_t *__restrict__ nheavy, const RunTables &rt, uint32_t n)
 {
     __shared__ __attribute__((aligned(16))) uint8_t ring[kResolveRing];
     __shared__ uint8_t aside[kResolveFast];
@@ -388,7 +450,7 @@ __device__ __forceinline__ void burst_resolve(const BurstIo &io, const uint32_t 
     const uint32_t at = run_at[r], end = run_end[at], key = skey[at];
     if (key >= nchannels) return;
     uint8_t *const st = states + (size_t)key * kStateBytes;
-    const uint32_t hl = *reinterpret_cast<const uint32_t *>(st);
+    const uint32_t hl = run_is_fresh(rt, at) ? 0u : *reinterpret_cast<const uint32_t *>(st);
     if (hl > kWindow) return;
     const uint32_t npk = end - at;
     // the table of packet k of the run: entry k mod 512
@@ -490,8 +552,10 @@ __device__ __forceinline__ void burst_resolve(const BurstIo &io, const uint32_t 
     if constexpr (PACKED) {
         if (__syncthreads_or(any_block ? 1 : 0) == 0) return;
     }
+    uint8_t *const to = run_commit_to(rt, skey, at, end, n, key, st);
+    if (to == nullptr) return;
     const uint32_t H = hl + produced < kWindow ? hl + produced : kWindow;
-    uint32_t *const hist = reinterpret_cast<uint32_t *>(st + kHistAt);
+    uint32_t *const hist = reinterpret_cast<uint32_t *>(to + kHistAt);
     for (uint32_t w = t; w < 512u; w += 256u) {
         uint32_t word = 0;
         for (uint32_t b = 0; b < 4u; b++) {
@@ -500,7 +564,7 @@ __device__ __forceinline__ void burst_resolve(const BurstIo &io, const uint32_t 
         }
         hist[w] = word;
     }
-    if (t == 0) *reinterpret_cast<uint32_t *>(st) = H;
+    if (t == 0) *reinterpret_cast<uint32_t *>(to) = H;
 }
 
 __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t out_cap,
@@ -508,10 +572,10 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_kernel(uint8_t *__restr
                                                                 const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                                                                 uint8_t *__restrict__ states, uint32_t nchannels,
                                                                 const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
-                                                                const uint32_t *__restrict__ nheavy)
+                                                                const uint32_t *__restrict__ nheavy, RunTables rt, uint32_t n)
 {
     burst_resolve<false>(burst_strided(nullptr, 0, nullptr, 0u, out, out_stride, out_cap), run_at, run_end, skey, sidx, states, nchannels,
-                         origins, rec, nheavy);
+                         origins, rec, nheavy, rt, n);
 }
 
 __global__ __launch_bounds__(256) void lzs_burst_resolve_packed_kernel(uint8_t *__restrict__ out, const uint64_t *__restrict__ out_off,
@@ -521,10 +585,10 @@ __global__ __launch_bounds__(256) void lzs_burst_resolve_packed_kernel(uint8_t *
                                                                        const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sidx,
                                                                        uint8_t *__restrict__ states, uint32_t nchannels,
                                                                        const uint16_t *__restrict__ origins, const uint2 *__restrict__ rec,
-                                                                       const uint32_t *__restrict__ nheavy)
+                                                                       const uint32_t *__restrict__ nheavy, RunTables rt, uint32_t n)
 {
     burst_resolve<true>(burst_packed(nullptr, in_off, in_len, out, out_off, room_ends), run_at, run_end, skey, sidx, states, nchannels,
-                        origins, rec, nheavy);
+                        origins, rec, nheavy, rt, n);
 }
 
 // ---- The host side: a call's stages, in order.  Where the parts of the work area lie, and what a call decides before it launches,
@@ -547,6 +611,7 @@ struct Burst {
     int decompress;
     uint32_t *out_len;
     const uint32_t *channel;
+    const uint8_t *flags;                          // a byte a packet, bit 0: a reset in front of it; or nullptr
     uint8_t *states, *status;
     uint32_t nchannels, npackets, grid;            // grid: workgroups of 256 threads, a thread a packet
     uint64_t origin_cap;                           // (split, PACKED) 16-bit origins behind the burst part; the strided call's host code knows that they fit
@@ -561,6 +626,9 @@ struct Burst {
     void *temp;                                    // rocPRIM's
     size_t temp_bytes;
     const uint32_t *skey, *sidx;                   // group: channel (nchannels if out of range) and packet at each sorted position
+    uint32_t *key_free, *val_free;                 // group: the halves of key[] and val[] the sort left unused
+    uint8_t *stage;                                // (flags, decompression) staging slots of the channels with several runs
+    RunTables rt;                                  // runs: without flags a run a channel (rkey = skey, no marks), else the scanned marks
     const uint32_t *run_w, *run_at;                // runs by weight, then split: the runs the run decoder takes, heaviest first
 };
 
@@ -576,6 +644,7 @@ void burst_lay_out(Burst &b, void *d_work)
     b.lens = u64(L.lens); b.ends = u64(L.ends); b.rooms = u64(L.rooms); b.room_ends = u64(L.room_ends);
     b.rec = reinterpret_cast<uint2 *>(W + L.rec); b.origins = reinterpret_cast<uint16_t *>(W + L.origins);
     b.temp = W + L.temp; b.temp_bytes = L.temp_bytes;
+    b.stage = W + L.stage;
 }
 
 // rocPRIM's way, once: call(nullptr, need) asks for the temporary storage's size, which the layout's has to cover; then it runs.
@@ -603,7 +672,29 @@ int burst_group(Burst &b)
     const int e = burst_prim(b, [&](void *temp, size_t &need) {
         return rocprim::radix_sort_pairs(temp, need, keys, vals, b.npackets, 0u, bits, b.stream); });
     b.skey = keys.current(); b.sidx = vals.current();
+    b.key_free = keys.alternate(); b.val_free = vals.alternate();
     return e;
+}
+
+// ---- the runs inside the channels: without flags one each; with flags a reset starts another (marks in weight[0], which no direction
+// has written yet, scanned into ids)
+int burst_runs(Burst &b)
+{
+    b.rt = RunTables{b.skey, nullptr, nullptr};
+    if (!b.flags) return 0;
+    uint32_t *const start = b.weight[0];
+    if (b.packed())
+        hipLaunchKernelGGL(lzs_burst_marks_packed_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.in_off, b.in_len, b.out_off, b.flags, b.skey,
+                           b.sidx, b.nchannels, start, b.val_free, b.npackets);
+    else
+        hipLaunchKernelGGL(lzs_burst_marks_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.flags, b.skey, b.sidx, b.nchannels, start, b.val_free,
+                           b.npackets);
+    BURST_TRY(hipGetLastError());
+    uint32_t *const rkey = b.key_free;
+    BURST_TRY(burst_prim(b, [&](void *temp, size_t &need) {
+        return rocprim::inclusive_scan(temp, need, start, rkey, (size_t)b.npackets, rocprim::plus<uint32_t>(), b.stream); }));
+    b.rt = RunTables{rkey, b.val_free, b.decompress ? b.stage : nullptr};
+    return 0;
 }
 
 // ---- where each packet ends in its channel's string of packets (a scan over all runs: the differences are what counts); packed
@@ -626,7 +717,7 @@ int burst_compress(const Burst &b)
     const dim3 grid(b.npackets);
     if (b.packed()) {
         hipLaunchKernelGGL(lzs_burst_gather_packed_kernel, grid, dim3(256), 0, b.stream, b.in, b.in_off, b.in_len, b.out_off, b.skey, b.sidx,
-                           b.ends, b.states, b.nchannels, b.slots);
+                           b.ends, b.states, b.nchannels, b.slots, b.rt);
         BURST_TRY(hipGetLastError());
         BURST_TRY(lzs_hip_launch_compress_channels_packed(b.out, b.out_off, b.out_len, b.in, b.in_off, b.in_len, nullptr, b.slots, b.status,
                                                           b.npackets, b.stream));
@@ -634,7 +725,7 @@ int burst_compress(const Burst &b)
                            b.nchannels, b.states, b.npackets);
     } else {
         hipLaunchKernelGGL(lzs_burst_gather_kernel, grid, dim3(256), 0, b.stream, b.in, b.in_stride, b.in_len, b.in_len_uniform, b.skey, b.sidx,
-                           b.ends, b.states, b.nchannels, b.slots);
+                           b.ends, b.states, b.nchannels, b.slots, b.rt);
         BURST_TRY(hipGetLastError());
         BURST_TRY(lzs_hip_launch_compress_channels(b.out, b.out_stride, b.out_cap, b.out_len, b.in, b.in_stride, b.in_len, b.in_len_uniform,
                                                    nullptr, b.slots, b.status, b.npackets, b.stream));
@@ -646,7 +737,7 @@ int burst_compress(const Burst &b)
 // ---- decompression: the runs by weight, heaviest first
 int burst_runs_by_weight(Burst &b)
 {
-    hipLaunchKernelGGL(lzs_burst_runs_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.skey, b.ends, b.weight[0], b.at[0], b.run_end, b.npackets);
+    hipLaunchKernelGGL(lzs_burst_runs_kernel, dim3(b.grid), dim3(256), 0, b.stream, b.rt.rkey, b.ends, b.weight[0], b.at[0], b.run_end, b.npackets);
     rocprim::double_buffer<uint32_t> w(b.weight[0], b.weight[1]), a(b.at[0], b.at[1]);
     const int e = burst_prim(b, [&](void *temp, size_t &need) {
         return rocprim::radix_sort_pairs_desc(temp, need, w, a, b.npackets, 0u, 32u, b.stream); });
@@ -657,23 +748,23 @@ int burst_runs_by_weight(Burst &b)
 // ---- the heavy runs (a prefix of that order, found on the device) by PARSE and RESOLVE; the others are left in tables of their own
 int burst_split(Burst &b)
 {
-    const dim3 grid(b.grid), packets(b.npackets), runs(lzs_burst_plan_resolve_grid(b.npackets, b.nchannels));
+    const dim3 grid(b.grid), packets(b.npackets), runs(lzs_burst_plan_resolve_grid_flags(b.npackets, b.nchannels, b.flags != nullptr));
     if (b.packed()) {
         hipLaunchKernelGGL(lzs_burst_split_plan_packed_kernel, grid, dim3(256), 0, b.stream, b.run_w, b.run_at, b.split_min, b.room_ends,
                            b.origin_cap, b.light_w, b.light_at, b.nheavy, b.npackets);
         hipLaunchKernelGGL(lzs_burst_parse_packed_kernel, packets, dim3(64), 0, b.stream, b.out, b.out_off, b.out_len, b.in, b.in_off, b.in_len,
                            b.room_ends, b.skey, b.sidx, b.ends, b.run_end, b.states, b.nchannels, b.status, b.origins, b.rec, b.nheavy,
-                           b.split_min);
+                           b.split_min, b.rt);
         hipLaunchKernelGGL(lzs_burst_resolve_packed_kernel, runs, dim3(256), 0, b.stream, b.out, b.out_off, b.in_off, b.in_len, b.room_ends,
-                           b.run_at, b.run_end, b.skey, b.sidx, b.states, b.nchannels, b.origins, b.rec, b.nheavy);
+                           b.run_at, b.run_end, b.skey, b.sidx, b.states, b.nchannels, b.origins, b.rec, b.nheavy, b.rt, b.npackets);
     } else {
         hipLaunchKernelGGL(lzs_burst_split_plan_kernel, grid, dim3(256), 0, b.stream, b.run_w, b.run_at, b.split_min, b.light_w, b.light_at,
                            b.nheavy, b.npackets);
         hipLaunchKernelGGL(lzs_burst_parse_kernel, packets, dim3(64), 0, b.stream, b.out, b.out_stride, b.out_cap, b.out_len, b.in, b.in_stride,
                            b.in_len, b.in_len_uniform, b.skey, b.sidx, b.ends, b.run_end, b.states, b.nchannels, b.status, b.origins, b.rec,
-                           b.nheavy, b.split_min);
+                           b.nheavy, b.split_min, b.rt);
         hipLaunchKernelGGL(lzs_burst_resolve_kernel, runs, dim3(256), 0, b.stream, b.out, b.out_stride, b.out_cap, b.run_at, b.run_end, b.skey,
-                           b.sidx, b.states, b.nchannels, b.origins, b.rec, b.nheavy);
+                           b.sidx, b.states, b.nchannels, b.origins, b.rec, b.nheavy, b.rt, b.npackets);
     }
     BURST_TRY(hipGetLastError());
     b.run_w = b.light_w; b.run_at = b.light_at;
@@ -685,44 +776,55 @@ int burst_decode_runs(const Burst &b)
 {
     if (b.packed())
         return lzs_hip_launch_decompress_runs_packed(b.out, b.out_off, b.out_len, b.in, b.in_off, b.in_len, b.room_ends, b.run_w, b.run_at,
-                                                     b.run_end, b.skey, b.sidx, b.nchannels, b.states, b.status, b.npackets, b.stream);
+                                                     b.run_end, b.skey, b.sidx, b.nchannels, b.states, b.status, b.npackets, b.rt.rkey, b.rt.rmark,
+                                                     b.rt.stage, b.stream);
     return lzs_hip_launch_decompress_runs(b.out, b.out_stride, b.out_cap, b.out_len, b.in, b.in_stride, b.in_len, b.in_len_uniform, b.run_w,
-                                          b.run_at, b.run_end, b.skey, b.sidx, b.nchannels, b.states, b.status, b.npackets, b.stream);
+                                          b.run_at, b.run_end, b.skey, b.sidx, b.nchannels, b.states, b.status, b.npackets, b.rt.rkey, b.rt.rmark, b.rt.stage,
+                                          b.stream);
+}
+
+// ---- (flags) the staged final slots to their channels, behind every kernel that read a slot
+int burst_commit_staged(const Burst &b)
+{
+    hipLaunchKernelGGL(lzs_burst_stage_commit_kernel, dim3(b.npackets), dim3(128), 0, b.stream, b.skey, b.rt, b.states, b.npackets);
+    return (int)hipGetLastError();
 }
 
 // One burst: the grouping, then the kernels of the direction.  b: where the packets lie.  split (decompression): the long runs by PARSE and RESOLVE.
-int burst(Burst &b, int decompress, uint32_t *d_out_len, const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
+int burst(Burst &b, int decompress, uint32_t *d_out_len, const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, uint32_t nchannels, uint8_t *d_status,
           void *d_work, uint32_t npackets, int split, uint64_t origin_cap, uint32_t split_min, void *stream)
 {
     if (npackets == 0) return 0;
-    b.decompress = decompress; b.out_len = d_out_len; b.channel = d_channel; b.states = static_cast<uint8_t *>(d_states); b.status = d_status;
+    b.decompress = decompress; b.out_len = d_out_len; b.channel = d_channel; b.flags = d_flags; b.states = static_cast<uint8_t *>(d_states); b.status = d_status;
     b.nchannels = nchannels; b.npackets = npackets; b.grid = (npackets + 255u) / 256u;
     b.origin_cap = origin_cap; b.split_min = split_min; b.stream = static_cast<hipStream_t>(stream);
     burst_lay_out(b, d_work);
     BURST_TRY(burst_group(b));
+    BURST_TRY(burst_runs(b));
     BURST_TRY(burst_lengths(b));
     if (!decompress) return burst_compress(b);
     BURST_TRY(burst_runs_by_weight(b));
     if (split) BURST_TRY(burst_split(b));
-    return burst_decode_runs(b);
+    BURST_TRY(burst_decode_runs(b));
+    return b.flags ? burst_commit_staged(b) : 0;
 }
 
 }  // namespace
 
 extern "C" int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                              const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
-                             const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
+                             const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, uint32_t nchannels, uint8_t *d_status,
                              void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream)
 {
     Burst b = {(uint8_t *)d_out, (const uint8_t *)d_in, out_stride, in_stride, out_cap, in_len, d_in_len, nullptr, nullptr};
-    return burst(b, decompress, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets, split, 0, split_min, stream);
+    return burst(b, decompress, d_out_len, d_channel, d_flags, d_states, nchannels, d_status, d_work, npackets, split, 0, split_min, stream);
 }
 
 extern "C" int lzs_hip_burst_packed(int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
-                                    const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, void *d_states,
-                                    uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, int split,
+                                    const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                    const uint8_t *d_flags, void *d_states, uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, int split,
                                     uint64_t origin_cap, uint32_t split_min, void *stream)
 {
     Burst b = {(uint8_t *)d_out, (const uint8_t *)d_in, 0, 0, 0u, 0u, d_in_len, d_in_off, d_out_off};
-    return burst(b, decompress, d_out_len, d_channel, d_states, nchannels, d_status, d_work, npackets, split, origin_cap, split_min, stream);
+    return burst(b, decompress, d_out_len, d_channel, d_flags, d_states, nchannels, d_status, d_work, npackets, split, origin_cap, split_min, stream);
 }

@@ -162,20 +162,24 @@ int lzs_hip_launch_decompress_channels(void *d_out, size_t out_stride, uint32_t 
 /* Many packets per channel (lzs_channels_burst.hip): the runs of a burst, one per group of a wavefront, longest first --
  * d_run_key[r] (1 + compressed bytes, 0: no run r; descending) and d_run_at[r] (its first position in the order by channel),
  * d_run_end[position of a run's first packet] (one past its last), d_skey / d_sidx (channel, nchannels if out of range, and
- * packet at each position). */
+ * packet at each position).  A call with packet flags has a run per reset as well: d_rmark[position] says where
+ * runs start and which start from an empty history, d_rkey[position] is the run's id, d_stage the staging slots of the channels with
+ * several runs (kernels/common.inc, RunTables); all three NULL without flags. */
 int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                                    const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                                    const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
                                    const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
-                                   uint8_t *d_status, uint32_t npackets, void *stream);
+                                   uint8_t *d_status, uint32_t npackets, const uint32_t *d_rkey, const uint32_t *d_rmark, void *d_stage,
+                                   void *stream);
 /* Many packets per channel (lzs_channels_burst.hip; lzs_channels.c checks the arguments; the work area's layout and size, and
  * `split` and `split_min`, are lzs_burst_plan.h's): one burst through compression (decompress 0) or decompression (1) -- the
  * grouping, then the kernels above.  `split` (decompression; the work area then holds the split size): the
  * runs of at least `split_min` compressed bytes are decoded by all their packets at once with per-byte origins and resolved
- * afterwards (lzs_burst_parse_kernel, lzs_burst_resolve_kernel), the others by lzs_hip_launch_decompress_runs. */
+ * afterwards (lzs_burst_parse_kernel, lzs_burst_resolve_kernel), the others by lzs_hip_launch_decompress_runs.  d_flags: a byte a
+ * packet, bit 0 a history reset in front of it (lzs_channels.h, LZS_PACKET_RESET), or NULL. */
 int lzs_hip_burst(int decompress, void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                   const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
-                  const uint32_t *d_channel, void *d_states, uint32_t nchannels, uint8_t *d_status,
+                  const uint32_t *d_channel, const uint8_t *d_flags, void *d_states, uint32_t nchannels, uint8_t *d_status,
                   void *d_work, uint32_t npackets, int split, uint32_t split_min, void *stream);
 int lzs_hip_launch_compact(void *d_dense, uint64_t *d_offsets, const void *d_slots,
                            size_t slot_stride, const uint32_t *d_len, uint32_t nblocks,
@@ -226,10 +230,11 @@ int lzs_hip_launch_decompress_runs_packed(void *d_out, const uint64_t *d_out_off
                                           const uint64_t *d_in_off, const uint32_t *d_in_len, const uint64_t *d_room_ends,
                                           const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
                                           const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
-                                          uint8_t *d_status, uint32_t npackets, void *stream);
+                                          uint8_t *d_status, uint32_t npackets, const uint32_t *d_rkey, const uint32_t *d_rmark,
+                                          void *d_stage, void *stream);
 int lzs_hip_burst_packed(int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
-                         const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, void *d_states,
-                         uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, int split,
+                         const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel, const uint8_t *d_flags,
+                         void *d_states, uint32_t nchannels, uint8_t *d_status, void *d_work, uint32_t npackets, int split,
                          uint64_t origin_cap, uint32_t split_min, void *stream);
 
 #ifdef __cplusplus

@@ -632,14 +632,16 @@ int lzs_hip_launch_decompress_runs(void *d_out, size_t out_stride, uint32_t out_
                                    const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
                                    const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
                                    const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
-                                   uint8_t *d_status, uint32_t npackets, void *stream)
+                                   uint8_t *d_status, uint32_t npackets, const uint32_t *d_rkey, const uint32_t *d_rmark, void *d_stage,
+                                   void *stream)
 {
     if (npackets == 0) return 0;
     // (a wavefront's runs take packets from anywhere in the input: eight runs to a wavefront if all of it is one 32-bit extent)
     const uint32_t per_wave = lzs_plan_dec_per_wave_runs(in_stride, npackets, d_in_len != nullptr, in_len);
     hipLaunchKernelGGL(lzs_decompress_runs_grp_kernel, dim3((npackets + per_wave - 1) / per_wave), dim3(64), 0, (hipStream_t)stream,
                        (uint8_t *)d_out, out_stride, out_cap, d_out_len, (const uint8_t *)d_in, in_stride, d_in_len, in_len,
-                       d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets, per_wave);
+                       d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets, per_wave,
+                       RunTables{d_rkey, d_rmark, (uint8_t *)d_stage});
     return (int)hipGetLastError();
 }
 
@@ -837,12 +839,14 @@ int lzs_hip_launch_decompress_runs_packed(void *d_out, const uint64_t *d_out_off
                                           const uint64_t *d_in_off, const uint32_t *d_in_len, const uint64_t *d_room_ends,
                                           const uint32_t *d_run_key, const uint32_t *d_run_at, const uint32_t *d_run_end,
                                           const uint32_t *d_skey, const uint32_t *d_sidx, uint32_t nchannels, void *d_states,
-                                          uint8_t *d_status, uint32_t npackets, void *stream)
+                                          uint8_t *d_status, uint32_t npackets, const uint32_t *d_rkey, const uint32_t *d_rmark,
+                                          void *d_stage, void *stream)
 {
     if (npackets == 0) return 0;
     hipLaunchKernelGGL(lzs_decompress_runs_packed_grp_kernel, dim3((npackets + kDecGroups - 1) / kDecGroups), dim3(64), 0,
                        (hipStream_t)stream, (uint8_t *)d_out, d_out_off, d_out_len, (const uint8_t *)d_in, d_in_off, d_in_len,
-                       d_room_ends, d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets);
+                       d_room_ends, d_run_key, d_run_at, d_run_end, d_skey, d_sidx, nchannels, (uint8_t *)d_states, d_status, npackets,
+                       RunTables{d_rkey, d_rmark, (uint8_t *)d_stage});
     return (int)hipGetLastError();
 }
 

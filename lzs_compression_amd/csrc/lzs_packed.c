@@ -158,8 +158,8 @@ size_t lzs_channels_burst_packed_split_work_bytes(size_t npackets, size_t nchann
 
 static int device_burst_packed(const char *who, int decompress, void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len,
                                const void *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
-                               void *d_states, size_t nchannels, uint8_t *d_status, void *d_work, size_t work_bytes, size_t npackets,
-                               void *stream)
+                               const uint8_t *d_flags, void *d_states, size_t nchannels, uint8_t *d_status, void *d_work,
+                               size_t work_bytes, size_t npackets, void *stream)
 {
     if (npackets == 0) return LZS_OK;
     int rc = check_decode(who, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, npackets);
@@ -169,10 +169,29 @@ static int device_burst_packed(const char *who, int decompress, void *d_out, con
     if (rc != LZS_OK) return rc;
     const lzs_burst_split_t split = lzs_burst_plan_split_packed(decompress, work_bytes - lzs_burst_plan_work_bytes(npackets, nchannels));
     const lzs_env_t *env = lzs_env();
-    const int e = lzs_hip_burst_packed(decompress, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_states,
+    const int e = lzs_hip_burst_packed(decompress, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len, d_channel, d_flags, d_states,
                                        (uint32_t)nchannels, d_status, d_work, (uint32_t)npackets, split.split, split.origin_cap,
                                        lzs_burst_plan_split_min(env->burst_split_set, env->burst_split_min), stream);
     return e ? hip_fail(e, who) : LZS_OK;
+}
+
+/* The packed burst entries are the flags entries without flags (lzs_channels.h, LZS_PACKET_RESET). */
+int lzs_compress_channels_burst_packed_flags_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                                    const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                                    const uint8_t *d_flags, void *d_states, size_t nchannels, uint8_t *d_status,
+                                                    void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
+{
+    return device_burst_packed("lzs_compress_channels_burst_packed_flags_device", 0, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len,
+                               d_channel, d_flags, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+}
+
+int lzs_decompress_channels_burst_packed_flags_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
+                                                      const uint64_t *d_in_off, const uint32_t *d_in_len, const uint32_t *d_channel,
+                                                      const uint8_t *d_flags, void *d_states, size_t nchannels, uint8_t *d_status,
+                                                      void *d_work, size_t work_bytes, size_t npackets, void *hip_stream)
+{
+    return device_burst_packed("lzs_decompress_channels_burst_packed_flags_device", 1, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len,
+                               d_channel, d_flags, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_compress_channels_burst_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
@@ -181,7 +200,7 @@ int lzs_compress_channels_burst_packed_device(void *d_out, const uint64_t *d_out
                                               size_t npackets, void *hip_stream)
 {
     return device_burst_packed("lzs_compress_channels_burst_packed_device", 0, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len,
-                               d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+                               d_channel, NULL, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_decompress_channels_burst_packed_device(void *d_out, const uint64_t *d_out_off, uint32_t *d_out_len, const void *d_in,
@@ -190,7 +209,7 @@ int lzs_decompress_channels_burst_packed_device(void *d_out, const uint64_t *d_o
                                                 size_t npackets, void *hip_stream)
 {
     return device_burst_packed("lzs_decompress_channels_burst_packed_device", 1, d_out, d_out_off, d_out_len, d_in, d_in_off, d_in_len,
-                               d_channel, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
+                               d_channel, NULL, d_states, nchannels, d_status, d_work, work_bytes, npackets, hip_stream);
 }
 
 int lzs_compact_packed_device(void *d_dense, uint64_t *d_offsets, const void *d_src, const uint64_t *d_src_off, const uint32_t *d_len,
