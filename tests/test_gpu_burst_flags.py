@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 import packed_burst_helpers as H  # noqa: E402
 import test_channel_model as M  # noqa: E402
+from burst_flags_cases import _apply_rule, _check_slots, _reach_back, _want_slots  # noqa: E402
 from packed_burst_helpers import FILL, GUARD  # noqa: E402
 from test_channel_model import O  # noqa: E402
 
@@ -45,50 +46,6 @@ def _start_slots(rng):
             rows[c, :4] = np.frombuffer(len(h).to_bytes(4, "little"), dtype=np.uint8)
             rows[c, HIST_AT:HIST_AT + len(h)] = np.frombuffer(h, dtype=np.uint8)
     return hists, rows
-
-
-def _apply_rule(step, ids, flags, hists, skip=()):
-    """The rule of the header over a queue: packet b on channel ids[b]; a flag on a block of a channel in range empties the
-    history first.  step(b, hist) -> (bytes, status, new history).  Returns (outs, status, final histories, touched channels)."""
-    hists = list(hists)
-    outs, status, touched = [], [], set()
-    for b, c in enumerate(ids):
-        if not 0 <= c < len(hists) or b in skip:
-            outs.append(b"")
-            status.append(A.STATUS_ERROR)
-            continue
-        if flags[b] & 1:
-            hists[c] = b""
-        if hists[c] is None:
-            outs.append(b"")
-            status.append(A.STATUS_ERROR)
-            continue
-        out, st, hists[c] = step(b, hists[c])
-        touched.add(c)
-        outs.append(out)
-        status.append(st)
-    return outs, np.array(status, dtype=np.uint8), hists, touched
-
-
-def _want_slots(before, hists, touched):
-    """A committed channel has its hist_len and all of hist[] rewritten, the reserved bytes as they were; the others are untouched."""
-    want = before.copy()
-    for c in touched:
-        h = hists[c]
-        want[c, :4] = np.frombuffer(len(h).to_bytes(4, "little"), dtype=np.uint8)
-        want[c, HIST_AT:] = 0
-        want[c, HIST_AT:HIST_AT + len(h)] = np.frombuffer(h, dtype=np.uint8)
-    return want
-
-
-def _check_slots(tag, states, want):
-    s = states.cpu().numpy()
-    rows = np.nonzero((s != want).any(axis=1))[0]
-    if rows.size:
-        c = int(rows[0])
-        i = int(np.nonzero(s[c] != want[c])[0][0])
-        raise AssertionError(f"{tag}: {rows.size} slots differ, first channel {c} at slot byte {i}: hist_len {int(s[c, :4].view('<u4')[0])} "
-                             f"(model {int(want[c, :4].view('<u4')[0])}), bytes {s[c, i:i + 8].tobytes().hex()} (model {want[c, i:i + 8].tobytes().hex()})")
 
 
 def _rows(packets):
@@ -135,20 +92,6 @@ def _check_strided(tag, got, outs, status):
 
 
 # ------------------------------------------------------------------ 1. the decoder against the model
-def _reach_back(rng, size):
-    """A whole packet of exactly `size` >= 24 bytes that BEGINS with a copy reaching in front of its own output: what it gives
-    depends on the history it starts from."""
-    head = int(rng.integers(8, 24))
-    bits = M.copy_bits(int(rng.integers(head + 1, 41)), head)      # (every history here that is one has 40 bytes and more)
-    return _join(bits, M.synth_exact(rng, size - head))
-
-
-def _join(bits, tail_packet):
-    """`bits`, then the tokens of a whole packet made by the synthesiser (its bits are its bytes: it ends with the marker and padding)."""
-    tail = "".join(f"{v:08b}" for v in tail_packet)
-    return M.to_bytes(bits + tail)
-
-
 def _decoder_queue():
     rng = np.random.default_rng(1974)
     packets = []
