@@ -99,6 +99,27 @@ int lzs_decompress_batch_device_sync(void *d_out, size_t out_stride, size_t out_
                                      size_t in_len, size_t nblocks);
 
 /*
+ * The compressing twin: lzs_compress_batch_device() for a batch of FEW LONG blocks, which does not fill the device with one
+ * workgroup per block (a workgroup alone takes 15 ms for 1 MiB of text, whatever the batch).  Every block is cut into segments,
+ * one workgroup each, as lzs_compress_stream_device() cuts one stream, with the entry rounds and the stitch over all blocks at
+ * once (profiles/r24/batch_compress.txt has the rows).  Buffers in device memory, the lengths in HOST memory
+ * (in_len_each may be NULL: every block in_len bytes; out_len receives the results).
+ *   out_len[b], bytes [0, out_len[b]) of slot b : byte for byte what lzs_compress_batch_device() gives at the same out_cap
+ *   the rest of slot b                          : unspecified, as that call leaves it; nothing outside slot b's out_stride bytes
+ *                                                 is stored to on b's behalf
+ * The segments are taken when out_cap <= out_stride and d_out, out_stride are multiples of 4, and the batch is of the shape for
+ * which they are faster; every other batch is one launch of the workgroup-per-block kernel, with the same results.
+ * Synchronous, on the calling thread's own stream: it returns when d_out is complete, and it is NOT capturable into a hipGraph
+ * (the entry rounds are decided on the host).  Scratch from the calling thread's staging, as the one-stream call takes it:
+ * LZS_COMPRESSED_MAX(segment) a segment, about 1.14 times the input, for at most LZS_BLOCK_MAX bytes of input at a time (longer
+ * batches go group by group), and 37 bytes a segment of tables.  LZS_E_ARG as lzs_compress_batch_device(), and for a block above
+ * LZS_BLOCK_MAX; nblocks == 0 is LZS_OK and touches nothing.
+ */
+int lzs_compress_batch_device_sync(void *d_out, size_t out_stride, size_t out_cap, uint32_t *out_len,
+                                   const void *d_in, size_t in_stride, const uint32_t *in_len_each,
+                                   size_t in_len, size_t nblocks);
+
+/*
  * How long every block of a batch decodes to, and how its decoding ends, WITHOUT decoding it: what a caller needs to choose
  * out_cap or to allocate the output before any of the decode calls (LZS_DECOMPRESSED_MAX() is no bound: see lzs.h).
  *

@@ -8,7 +8,7 @@ fallback: without the built library or without a GPU, calls raise.
 from .api import (CHANNEL_STATE_BYTES, ChannelCodec, channels_burst_split_work_bytes, channels_burst_work_bytes, compress_channels, compress_channels_burst,
                   decompress_channels, decompress_channels_burst, new_channel_states)
 from .api import (IncrementalCompressor, IncrementalDecompressor, LzsError, backend_info, compact, compress, compress_batch, compress_blocks,
-                  compress_stream, compressed_max, decompress, decompress_batch, decompress_blocks, decompress_blocks_sync, decompress_concat,
+                  compress_blocks_sync, compress_stream, compressed_max, decompress, decompress_batch, decompress_blocks, decompress_blocks_sync, decompress_concat,
                   decompress_stream, decompressed_max, incremental_compress, last_error, lib, release_thread_cache)
 from .api import (STATUS_END_MARKER, STATUS_ERROR, STATUS_INPUT_FINISHED, STATUS_INPUT_STARVED, STATUS_NO_OUTPUT_BUFFER_SPACE)
 from .api import decompress_blocks_dense, decompressed_sizes
@@ -23,7 +23,7 @@ from . import workload
 __all__ = ["CHANNEL_STATE_BYTES", "ChannelCodec", "channels_burst_split_work_bytes", "channels_burst_work_bytes", "compress_channels", "compress_channels_burst",
            "decompress_channels", "decompress_channels_burst", "new_channel_states",
            "IncrementalCompressor", "IncrementalDecompressor", "LzsError", "backend_info", "compact", "compress", "compress_batch", "compress_blocks",
-           "compress_stream", "compressed_max", "decompress", "decompress_batch", "decompress_blocks", "decompress_blocks_sync", "decompress_concat",
+           "compress_blocks_sync", "compress_stream", "compressed_max", "decompress", "decompress_batch", "decompress_blocks", "decompress_blocks_sync", "decompress_concat",
            "decompress_stream", "decompressed_max", "incremental_compress", "last_error", "lib", "release_thread_cache", "workload",
            "STATUS_END_MARKER", "STATUS_ERROR", "STATUS_INPUT_FINISHED", "STATUS_INPUT_STARVED", "STATUS_NO_OUTPUT_BUFFER_SPACE",
            "decompress_blocks_dense", "decompressed_sizes",

@@ -77,6 +77,8 @@ def lib() -> ctypes.CDLL:
         for name in ("lzs_compress_batch", "lzs_decompress_batch", "lzs_decompress_batch_device_sync"):
             f = getattr(L, name)
             f.restype, f.argtypes = ctypes.c_int, _BATCH_HOST
+        if hasattr(L, "lzs_compress_batch_device_sync"):          # (an older build named by LZS_LIBRARY, for A/B runs, has none)
+            L.lzs_compress_batch_device_sync.restype, L.lzs_compress_batch_device_sync.argtypes = ctypes.c_int, _BATCH_HOST
         L.lzs_compress_stream_device.restype = ctypes.c_int
         L.lzs_compress_stream_device.argtypes = [_vp, _sz, ctypes.POINTER(_sz), _vp, _sz]
         L.lzs_decompress_stream_device.restype = ctypes.c_int
@@ -299,6 +301,28 @@ def decompress_blocks_sync(x, in_len, out_capacity: int, out=None):
     _check(lib().lzs_decompress_batch_device_sync(
         out.data_ptr(), out.stride(0), out_capacity, out_len.ctypes.data,
         x.data_ptr(), x.stride(0), None if lens is None else lens.ctypes.data, x.shape[1], nblocks))
+    return out, out_len
+
+
+def compress_blocks_sync(x, in_len=None, out_capacity: Optional[int] = None, out=None):
+    """lzs_compress_batch_device_sync(): a batch of FEW LONG blocks in device memory (``x``: uint8 [nblocks, stride]) with their
+    lengths on the host (``in_len``: sequence / numpy array, or None for full rows), every block cut into segments for the whole
+    device where that is faster.  Same streams as compress_blocks().  Synchronous.  Returns
+    (out [nblocks, slot_stride] on the device -- the capacity rounded up to 4 --, lengths as a numpy array)."""
+    import torch
+    assert x.is_cuda and x.dtype == torch.uint8 and x.dim() == 2 and x.stride(1) == 1
+    nblocks = x.shape[0]
+    cap = compressed_max(x.shape[1]) if out_capacity is None else out_capacity
+    if out is None:
+        out = torch.empty((nblocks, (max(cap, 1) + 3) // 4 * 4), dtype=torch.uint8, device=x.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.shape[0] == nblocks and out.stride(1) == 1
+    lens = None if in_len is None else np.ascontiguousarray(in_len, dtype=np.uint32)
+    assert lens is None or (lens.shape == (nblocks,) and (lens <= x.shape[1]).all())
+    out_len = np.zeros(nblocks, dtype=np.uint32)
+    torch.cuda.current_stream().synchronize()             # the call runs on the library's own stream
+    _check(lib().lzs_compress_batch_device_sync(
+        out.data_ptr(), out.stride(0) if nblocks > 1 else out.shape[1], cap, out_len.ctypes.data,
+        x.data_ptr(), x.stride(0) if nblocks > 1 else x.shape[1], None if lens is None else lens.ctypes.data, x.shape[1], nblocks))
     return out, out_len
 
 

@@ -179,6 +179,50 @@ void lzs_stitch_segments_kernel(uint8_t *__restrict__ out, const uint8_t *__rest
     }
 }
 
+// The same for the segments of the blocks of a batch (lzs_compress_segments_batch_kernel's tables; DESIGN.md 3.19): segment k's
+// bits go to bit bit_at[k] of ITS BLOCK's output, out + b out_stride (4-aligned, zeroed as far as it is written), and the end
+// marker follows the last segment of every block -- the one that reaches blk_len[b]; a block without a byte has one segment
+// without a bit and is nothing but the marker.  No store, plain or ORed, leaves the block's capw words (its capacity rounded up
+// to a word, within its out_stride bytes by the caller's check): a destination word at or past them is dropped.
+__global__ __launch_bounds__(256)
+void lzs_stitch_segments_batch_kernel(uint8_t *__restrict__ out, size_t out_stride, uint32_t capw,
+                                      const uint8_t *__restrict__ slots, size_t slot_stride,
+                                      const unsigned long long *__restrict__ bit_at, const unsigned long long *__restrict__ nbits,
+                                      const uint32_t *__restrict__ seg_block, const uint32_t *__restrict__ seg_start,
+                                      const uint32_t *__restrict__ blk_len, uint32_t seg, uint32_t nseg)
+{
+    const uint32_t k = blockIdx.x;
+    if (k >= nseg) return;
+    const uint32_t b = uniform(seg_block[k]), s = uniform(seg_start[k]), n = uniform(blk_len[b]);
+    const unsigned long long at = bit_at[k], mine = nbits[k];
+    const bool fits = mine <= 8ull * slot_stride;                  // else its bits are ORed in directly
+    const uint32_t nb = fits ? (uint32_t)mine : 0u;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(slots + (size_t)k * slot_stride);
+    unsigned int *blk = reinterpret_cast<unsigned int *>(out + (size_t)b * out_stride);
+    const unsigned long long w0 = at >> 5;                         // destination word of the segment's first bit
+    const uint32_t sh = (uint32_t)(at & 31ull);
+    const uint32_t words = (nb + 31u) >> 5;
+    const uint32_t tail = (nb & 31u) ? ~0u << (32u - (nb & 31u)) : ~0u;
+    const uint32_t shared = (sh + nb) >> 5;
+    for (uint32_t j = threadIdx.x; j <= words; j += blockDim.x) {
+        if (w0 + j >= capw) break;                                 // (ascending in j: the rest lies behind the capacity too)
+        uint32_t cur = 0, prev = 0;
+        if (j < words) cur = __builtin_bswap32(src[j]) & (j == words - 1u ? tail : ~0u);
+        if (j > 0u && sh) prev = __builtin_bswap32(src[j - 1u]) & (j == words ? tail : ~0u);
+        const uint32_t v = (cur >> sh) | (sh ? prev << (32u - sh) : 0u);
+        if (j > 0u && j < shared) blk[w0 + j] = __builtin_bswap32(v);
+        else if (v) atomicOr(blk + w0 + j, __builtin_bswap32(v));
+    }
+    if (n - s <= seg && threadIdx.x == 0) {                        // the block's last segment: the end marker after its last bit
+        const unsigned long long end = at + mine;
+        const uint32_t s2 = (uint32_t)(end & 31ull);
+        const unsigned long long m = (unsigned long long)0x180u << (64u - 9u - s2);
+        const unsigned long long w2 = end >> 5;
+        if (w2 < capw) atomicOr(blk + w2, __builtin_bswap32((uint32_t)(m >> 32)));
+        if ((uint32_t)m && w2 + 1u < capw) atomicOr(blk + w2 + 1u, __builtin_bswap32((uint32_t)m));
+    }
+}
+
 // A piece of a stream that begins inside a long match (lzs_compress_incremental: the call before
 // ended with the match still running, state COMPRESS_EXTENDED of lzs-compression.c:750-776).  One
 // wavefront measures how far in[c0..n) goes on repeating what lies `off` before it and writes the

@@ -275,6 +275,9 @@ struct WgOut {
 __device__ __forceinline__ uint32_t wg_bit_at(const WgOut &o) { return ((o.flushed << 3) + o.head) & kBitMask; }
 
 // Store one complete quarter (2048 bits) of the ring from the calling wave and clear it.
+// (BOUNDED_OR: the ORed stores stop at `limit` too -- the segments of a batch, whose neighbour in memory is another block's output;
+// a parameter of the instance, so that the entries that had an instance keep their instructions)
+template <bool BOUNDED_OR = false>
 __device__ __forceinline__ void wg_store_quarter(const WgOut &o, BlkLds &L, uint32_t lane)
 {
     const uint32_t slot = ((o.flushed >> 8) & (kWgBitWords / 64u - 1u)) * 64u + lane;
@@ -282,7 +285,7 @@ __device__ __forceinline__ void wg_store_quarter(const WgOut &o, BlkLds &L, uint
     L.bits[slot] = 0;
     const uint32_t at = o.flushed + 4 * lane;
     if (o.ored) {                                             // o.dst is 4-aligned in this mode
-        if (v) atomicOr(reinterpret_cast<unsigned int *>(o.dst + at), v);
+        if (v && (!BOUNDED_OR || at + 4u <= o.limit)) atomicOr(reinterpret_cast<unsigned int *>(o.dst + at), v);
         return;
     }
     if (o.aligned4 && at + 4 <= o.limit) {
@@ -853,7 +856,8 @@ __device__ __forceinline__ u32x4 wg_view_read16(const WgJob &job, uint32_t q)
 #endif
 
 // (ENTRY changes nothing in the code: the packed entries below take instance 1, so that every strided entry stays the only caller
-// of the instance it had -- as a second caller of that one they moved the strided kernels' instructions; DESIGN.md 3.15)
+// of the instance it had -- as a second caller of that one they moved the strided kernels' instructions; DESIGN.md 3.15.  Instance 2,
+// the segments of a batch, differs in one compare: its ORed stores are bounded, wg_store_quarter<true>; DESIGN.md 3.19)
 // (HE: SEARCH with LZS_WGV_HOP_END's rule -- the block and packed entries of a variant that asks for it; the segments entry does not)
 template <int ENTRY = 0, bool HE = false>
 __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgOut o)
@@ -1071,7 +1075,7 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
             // are all in (barrier above), and nothing is added before the next barrier
             while (o.head >= 2048u) {
                 PROF_COUNT(29, 1);
-                if (wave == ((o.flushed >> 8) & (kW - 1u))) wg_store_quarter(o, L, lane);
+                if (wave == ((o.flushed >> 8) & (kW - 1u))) wg_store_quarter<ENTRY == 2>(o, L, lane);
                 o.flushed += 256u;
                 o.head -= 2048u;
             }
@@ -1310,7 +1314,7 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
                     if (lane == 0 && wave < 4u) L.bcast[4u * par + wave] = mw;   // (a step is 255 threads' worth whatever the workgroup's size)
                     PROF_SYNC(40);                           // the counts are there; the bits of the step before are in
                     while (o.head >= 2048u) {
-                        if (wave == ((o.flushed >> 8) & (kW - 1u))) wg_store_quarter(o, L, lane);
+                        if (wave == ((o.flushed >> 8) & (kW - 1u))) wg_store_quarter<ENTRY == 2>(o, L, lane);
                         o.flushed += 256u;
                         o.head -= 2048u;
                     }
@@ -1397,11 +1401,11 @@ __device__ __forceinline__ void wg_compress_job(BlkLds &L, const WgJob &job, WgO
             if (lane == 0) bits_or(L.bits, kWgBitWords, wg_bit_at(o), 0x180u, 9);
             o.head = (o.head + 9u + 7u) & ~7u;
         }
-        while (o.head >= 2048u) { wg_store_quarter(o, L, lane); o.flushed += 256u; o.head -= 2048u; }
+        while (o.head >= 2048u) { wg_store_quarter<ENTRY == 2>(o, L, lane); o.flushed += 256u; o.head -= 2048u; }
         __builtin_amdgcn_wave_barrier();
         const uint32_t nbytes = (o.head + 7u) >> 3;                // a segment may end inside a byte
         if (o.ored) {
-            if (32u * lane < o.head) wg_store_quarter(o, L, lane);     // the words the last bits reach into
+            if (32u * lane < o.head) wg_store_quarter<ENTRY == 2>(o, L, lane);     // the words the last bits reach into
         } else {
             for (uint32_t i = lane; i < nbytes; i += 64) {
                 const uint32_t bit = ((o.flushed << 3) + 8 * i) & kBitMask;
@@ -1562,6 +1566,65 @@ void lzs_compress_segments_kernel(uint8_t *__restrict__ slots, size_t slot_strid
         o.head = (uint32_t)(g & 2047ull); o.limit = ~0u; o.ored = true;
     }
     wg_compress_job(L, job, o);
+}
+
+// The same for the segments of MANY streams, the blocks of a batch (lzs_batch_compress.c; DESIGN.md 3.19): segment k belongs to
+// block seg_block[k], which is the blk_len[b] bytes at in + blk_at[b] (64-bit: a batch may be longer than 4 GiB), and starts
+// seg_start[k] bytes into it.  The job is the BLOCK's -- src its first byte, n its length, every position relative to it -- so the
+// chains never reach before the block and no load goes past its end, whatever lies beside it in memory; the slot index stays
+// global.  Every block is whole (no `lim`, no open match).  The second pass ORs into the block's own output, out + b out_stride
+// (4-aligned), and stops where its capacity, rounded up to a word (cap4), ends: the next block's output may begin right there.
+// (Instance 2 of wg_compress_job: the bounded form of the ORed stores is its alone.)
+#ifdef LZS_WGV_WAVES
+__global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(LZS_WGV_WAVES, LZS_WGV_WAVES)))
+#else
+__global__ __launch_bounds__(kWgThreads)
+#endif
+void lzs_compress_segments_batch_kernel(uint8_t *__restrict__ slots, size_t slot_stride,
+                                        const uint8_t *__restrict__ in, const unsigned long long *__restrict__ blk_at,
+                                        const uint32_t *__restrict__ blk_len, const uint32_t *__restrict__ seg_block,
+                                        const uint32_t *__restrict__ seg_start, uint32_t seg, uint32_t nseg,
+                                        const uint32_t *__restrict__ entry, const uint8_t *__restrict__ dirty,
+                                        uint32_t *__restrict__ exit_pos, unsigned long long *__restrict__ nbits,
+                                        uint8_t *__restrict__ out, size_t out_stride, uint32_t cap4,
+                                        const unsigned long long *__restrict__ bit_at)
+{
+    __shared__ BlkLds L;
+    const uint32_t k = blockIdx.x;
+    if (k >= nseg) return;
+    if (dirty && !dirty[k]) return;
+    // (one load per table and workgroup, then scalars)
+    const uint32_t b = uniform(seg_block[k]), s = uniform(seg_start[k]);
+    const uint32_t n = uniform(blk_len[b]);
+    const unsigned long long at0 = blk_at[b];
+    const unsigned long long at = ((unsigned long long)uniform((uint32_t)(at0 >> 32)) << 32) | uniform((uint32_t)at0);
+    const uint32_t e = n - s > seg ? s + seg : n;              // (s <= n by the table's construction)
+    WgJob job;
+    job.src = in + at; job.n = n; job.cend = e;
+    job.c0 = uniform(entry[k]);
+    const uint32_t c64 = job.c0 & ~63u;
+    job.w0 = c64 > 2176u ? c64 - 2176u : 0u;                   // block coordinates: never from before the block
+    job.last = false;
+    job.out_len = nullptr; job.exit_pos = exit_pos + k; job.nbits = nbits + k;
+    job.open_info = nullptr;
+    if (job.c0 >= e) {                                         // the segment before ran over all of this one (or the block is empty)
+        if (threadIdx.x == 0) { exit_pos[k] = job.c0; nbits[k] = 0; }
+        return;
+    }
+    WgOut o;
+    o.flushed = 0; o.cap = ~0u; o.aligned4 = true;
+    if (!out) {
+        o.dst = slots + (size_t)k * slot_stride;               // 16-aligned by the host
+        o.head = 0; o.limit = (uint32_t)slot_stride; o.ored = false;
+    } else {
+        const unsigned long long g0 = bit_at[k];
+        const unsigned long long g = ((unsigned long long)uniform((uint32_t)(g0 >> 32)) << 32) | uniform((uint32_t)g0);
+        const unsigned long long first = 256ull * (g >> 11);   // the 256-byte granule its first bit falls in
+        if (first >= cap4) return;                             // all of it lies behind the capacity: nothing to store
+        o.dst = out + (size_t)b * out_stride + first;
+        o.head = (uint32_t)(g & 2047ull); o.limit = cap4 - (uint32_t)first; o.ored = true;
+    }
+    wg_compress_job<2>(L, job, o);
 }
 
 #endif  // LZS_WGV_SEGMENTS

@@ -98,6 +98,27 @@ int lzs_hip_launch_stitch_segments(void *d_out, const void *d_slots, size_t slot
                                    int end_marker, void *stream);
 int lzs_hip_launch_extend_resume(void *d_out, uint32_t bit0, const void *d_in, uint32_t n, uint32_t c0,
                                  uint32_t off, int last, uint32_t *d_result, void *stream);
+/* The same two for the segments of MANY streams, the blocks of a batch (lzs_batch_compress.c).  Block b is the
+ * d_blk_len[b] bytes at d_in + d_blk_at[b] (a 64-bit byte offset) and is compressed as a whole stream of its own: nothing in
+ * front of it or behind it is read, whatever its address.  Segment k belongs to block d_seg_block[k] and starts d_seg_start[k]
+ * bytes into it (a multiple of `seg`; a block of length 0 has one segment, at 0, without a bit); d_entry, d_exit are positions in
+ * the block; slots, d_dirty, d_nbits as above, indexed by k.
+ * lzs_hip_launch_stitch_segments_batch() ORs segment k's slot into bit d_bit_at[k] of ITS BLOCK's output, d_out + b out_stride --
+ * 4-aligned and zeroed as far as the block's stream reaches -- and puts the end marker behind the last segment of every block.
+ * With d_out / d_bit_at set, lzs_hip_launch_compress_segments_batch() is the second pass of the segments with d_dirty[k] != 0
+ * (those that did not fit their slot), ORed into the same place.
+ * Neither stores outside [d_out + b out_stride, + out_cap rounded up to 4) for any block b; the caller sees to it that this lies
+ * within the block's out_stride bytes (out_cap <= out_stride, out_stride a multiple of 4).  What would lie behind is dropped. */
+int lzs_hip_launch_compress_segments_batch(void *d_slots, size_t slot_stride, const void *d_in, const uint64_t *d_blk_at,
+                                           const uint32_t *d_blk_len, const uint32_t *d_seg_block, const uint32_t *d_seg_start,
+                                           uint32_t seg, uint32_t nseg, const uint32_t *d_entry, const uint8_t *d_dirty,
+                                           uint32_t *d_exit, uint64_t *d_nbits, void *d_out, size_t out_stride, uint32_t out_cap,
+                                           const uint64_t *d_bit_at, void *stream);
+int lzs_hip_launch_stitch_segments_batch(void *d_out, size_t out_stride, uint32_t out_cap, const void *d_slots, size_t slot_stride,
+                                         const uint64_t *d_bit_at, const uint64_t *d_nbits, const uint32_t *d_seg_block,
+                                         const uint32_t *d_seg_start, const uint32_t *d_blk_len, uint32_t seg, uint32_t nseg, void *stream);
+/* `rows` rows of `width` bytes, `pitch` bytes apart, set to `value`; what lies between the rows is not touched */
+int lzs_hip_memset_rows(void *d, size_t pitch, int value, size_t width, size_t rows, void *stream);
 /* One long stream decompressed by many wavefronts (lzs_scan_stream_kernel, lzs_decode_stream_kernel,
  * lzs_resolve_stream_kernel; state words and the scheme are described at the kernels).  With the
  * tables (all NULL for one stream) the segments belong to many streams in one buffer -- a batch of

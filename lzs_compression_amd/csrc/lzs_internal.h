@@ -7,6 +7,7 @@
  *                      scan / decode / resolve
  *   lzs_incremental.c  the reference's incremental interface on top of both: one loop over a call's stages per direction
  *   lzs_hostcodec.c    the small calls' host route: the calling thread's own codec
+ *   lzs_batch_compress.c  a batch in device memory compressed by segments over all blocks at once, or by workgroups
  */
 #ifndef LZS_INTERNAL_H
 #define LZS_INTERNAL_H
@@ -221,6 +222,13 @@ LZS_HIDDEN int stream_call_begins(const char *who, size_t tab_bytes, staging_t *
 LZS_HIDDEN int stream_copy_in(void *d_in, const uint8_t *prefix, size_t pre, const uint8_t *in, size_t n, void *stream);
 LZS_HIDDEN size_t stream_call_ends(size_t result, int rc, int dev, const char *who, int *status);
 LZS_HIDDEN uint32_t stream_dec_seg(size_t n);
+LZS_HIDDEN uint32_t stream_seg(size_t n);              /* the segment compressor's segment size for n bytes of input (LZS_STREAM_SEG forces it) */
+
+/* ---- a batch in device memory compressed by segments (lzs_batch_compress.c) */
+/* After a round over the segments of many blocks: settle_compress_entries() with a first segment (seg_start[k] == 0) wherever a
+ * block begins -- entered at 0, never dirty again.  Host code only.  Returns how many are dirty now. */
+LZS_HIDDEN uint32_t settle_compress_entries_batch(uint32_t *entry, uint8_t *dirty, const uint32_t *exits, const uint32_t *seg_start,
+                                                  uint32_t nseg);
 LZS_HIDDEN void segtab_lay_out(seg_table_t *t, uint32_t *h, uint32_t *d, int ranges);
 LZS_HIDDEN uint32_t settle_entries(seg_table_t *t, int use_ones, int *host_made);
 LZS_HIDDEN int scan_rounds(seg_table_t *t, void *stream, const char *who, const void *d_in, uint32_t n, uint32_t in_extent,

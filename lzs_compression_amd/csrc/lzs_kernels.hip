@@ -675,6 +675,21 @@ int lzs_hip_launch_compress_segments(void *d_slots, size_t slot_stride, const vo
                                (uint8_t *)d_out, (const unsigned long long *)d_bit_at, lim, d_open);
 }
 
+// The segments of the blocks of a batch (lzs_batch_compress.c).
+int lzs_hip_launch_compress_segments_batch(void *d_slots, size_t slot_stride, const void *d_in, const uint64_t *d_blk_at,
+                                           const uint32_t *d_blk_len, const uint32_t *d_seg_block, const uint32_t *d_seg_start,
+                                           uint32_t seg, uint32_t nseg, const uint32_t *d_entry, const uint8_t *d_dirty,
+                                           uint32_t *d_exit, uint64_t *d_nbits, void *d_out, size_t out_stride, uint32_t out_cap,
+                                           const uint64_t *d_bit_at, void *stream)
+{
+    if (nseg == 0) return 0;
+    const uint32_t cap4 = out_cap > 0xFFFFFFFCu ? 0xFFFFFFFCu : (out_cap + 3u) & ~3u;
+    return launch_safe_or_text(LZS_SAFE_OR_TEXT(, lzs_compress_segments_batch_kernel), nseg, stream,
+                               (uint8_t *)d_slots, slot_stride, (const uint8_t *)d_in, (const unsigned long long *)d_blk_at, d_blk_len,
+                               d_seg_block, d_seg_start, seg, nseg, d_entry, d_dirty, d_exit, (unsigned long long *)d_nbits,
+                               (uint8_t *)d_out, out_stride, cap4, (const unsigned long long *)d_bit_at);
+}
+
 // Many channels, one packet each.
 int lzs_hip_launch_compress_channels(void *d_out, size_t out_stride, uint32_t out_cap, uint32_t *d_out_len,
                                      const void *d_in, size_t in_stride, const uint32_t *d_in_len, uint32_t in_len,
@@ -716,6 +731,27 @@ int lzs_hip_launch_stitch_segments(void *d_out, const void *d_slots, size_t slot
                        (const unsigned long long *)d_bit_at, (const unsigned long long *)d_nbits, nseg,
                        end_marker ? 1u : 0u);
     return (int)hipGetLastError();
+}
+
+int lzs_hip_launch_stitch_segments_batch(void *d_out, size_t out_stride, uint32_t out_cap, const void *d_slots, size_t slot_stride,
+                                         const uint64_t *d_bit_at, const uint64_t *d_nbits, const uint32_t *d_seg_block,
+                                         const uint32_t *d_seg_start, const uint32_t *d_blk_len, uint32_t seg, uint32_t nseg, void *stream)
+{
+    if (nseg == 0) return 0;
+    const uint32_t capw = out_cap / 4u + (out_cap % 4u != 0u);
+    hipLaunchKernelGGL(lzs_stitch_segments_batch_kernel, dim3(nseg), dim3(256), 0, (hipStream_t)stream,
+                       (uint8_t *)d_out, out_stride, capw, (const uint8_t *)d_slots, slot_stride,
+                       (const unsigned long long *)d_bit_at, (const unsigned long long *)d_nbits, d_seg_block, d_seg_start, d_blk_len,
+                       seg, nseg);
+    return (int)hipGetLastError();
+}
+
+// `rows` rows of `width` bytes, `pitch` apart, set to `value` (the outputs of a batch cleared as far as they are written)
+int lzs_hip_memset_rows(void *d, size_t pitch, int value, size_t width, size_t rows, void *stream)
+{
+    if (width == 0 || rows == 0) return 0;
+    if (rows == 1 || width == pitch) return (int)hipMemsetAsync(d, value, (rows - 1) * pitch + width, (hipStream_t)stream);
+    return (int)hipMemset2DAsync(d, pitch, value, width, rows, (hipStream_t)stream);
 }
 
 #endif  // !LZS_TU_DECOMPRESS

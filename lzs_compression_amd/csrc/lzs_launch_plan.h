@@ -137,4 +137,70 @@ static inline int lzs_plan_size_route(uint64_t extent, uint64_t total_in, uint64
     return total_in / nblocks >= LZS_PLAN_SIZE_SEG_MIN_AVG ? LZS_SIZE_BY_SEGMENTS : LZS_SIZE_BY_LANES;
 }
 
+/* ---- compressing a batch in device memory with its lengths on the host (lzs_batch_compress.c) ------------------
+ * By workgroups: lzs_hip_launch_compress, one workgroup a block.  By segments: every block cut into segments, one workgroup each,
+ * entry rounds over all blocks at once, one stitch.  The segments write through 32-bit words into the caller's slots, so
+ * d_out (out_align: its address, or its low bits) and out_stride must be multiples of 4, and out_cap must not exceed out_stride:
+ * then a block's capacity rounded up to a word lies within its own slot.  Everything else goes by workgroups.
+ * Where it pays (profiles/r24/batch_compress.txt: MI355X, medians, ms, by workgroups / by segments; text, low entropy, high
+ * entropy; run-to-run spread of the medians 3.8 % at the most).  By workgroups a batch takes as long as its longest block --
+ * 1, 8 and 64 blocks of 16 MiB of text all take 210 ms -- and by segments as long as its bytes in all:
+ *     64 x 16 MiB   210.4 / 16.1    44.7 / 4.60    163.0 / 15.6        64 x 1 MiB   13.21 / 2.19    2.88 / 0.66    10.22 / 1.98
+ *    256 x 1 MiB    13.23 / 5.09    3.01 / 1.44    10.25 / 4.90      1024 x 1 MiB   16.72 / 16.03   3.69 / 4.66    12.48 / 15.58
+ *    256 x 64 KiB   0.885 / 0.616   0.258 / 0.399  0.675 / 0.466
+ * Blocks of 1 MiB win by segments in every class up to 256 of them and lose in two classes at 1024; blocks of 64 KiB lose in one
+ * class at 256 already, the smallest batch measured.  So: by segments when the longest block has LZS_PLAN_BC_SEG_MIN_LONGEST
+ * bytes and the batch holds at most LZS_PLAN_BC_SEG_MAX_BLOCKS times that in all -- for uniform blocks, at most that many blocks;
+ * a ragged batch is measured by what it would be in blocks of its longest.  Nothing between the measured rows is claimed.
+ * forced: LZS_BATCH_COMPRESS_ROUTE, 0 not set, 1 workgroups, 2 segments -- which the preconditions still bind. */
+#define LZS_PLAN_BC_SEG_MIN_LONGEST 1048576u    /* the longest block, bytes */
+#define LZS_PLAN_BC_SEG_MAX_BLOCKS  256u        /* total input / longest block */
+enum { LZS_BATCH_COMPRESS_BY_WORKGROUPS = 0, LZS_BATCH_COMPRESS_BY_SEGMENTS = 1 };
+
+static inline int lzs_plan_batch_compress_route(uint64_t nblocks, uint64_t total_in, uint64_t longest, uint64_t out_cap,
+                                                uint64_t out_stride, uint64_t out_align, int forced)
+{
+    if (nblocks == 0u || nblocks > 0x7FFFFFFFull || out_cap > out_stride || (out_stride & 3u) || (out_align & 3u) || forced == 1)
+        return LZS_BATCH_COMPRESS_BY_WORKGROUPS;
+    if (forced == 2) return LZS_BATCH_COMPRESS_BY_SEGMENTS;
+    return longest >= LZS_PLAN_BC_SEG_MIN_LONGEST && total_in <= (uint64_t)LZS_PLAN_BC_SEG_MAX_BLOCKS * longest ? LZS_BATCH_COMPRESS_BY_SEGMENTS
+                                                                                                                 : LZS_BATCH_COMPRESS_BY_WORKGROUPS;
+}
+
+/* The segment route takes consecutive blocks in groups, so that the slots of a group -- about 1.14 times its input -- stay within
+ * what one stream of `bound` bytes takes: the blocks b0, b0 + 1, ... whose lengths sum to `bound` at the most, and never fewer
+ * than one (a block longer than the bound is a group of its own), nor more than LZS_PLAN_BC_GROUP_MAX_BLOCKS: blocks without a
+ * byte add nothing to the sum but a segment each to the tables.  len_each NULL: every block has len_all bytes.  Returns how
+ * many blocks the group at b0 has (0 only if b0 >= nblocks). */
+#define LZS_PLAN_BC_GROUP_MAX_BLOCKS 1048576u
+static inline uint64_t lzs_plan_batch_compress_group(const uint32_t *len_each, uint32_t len_all, uint64_t nblocks, uint64_t b0, uint64_t bound)
+{
+    uint64_t sum = 0, b = b0;
+    for (; b < nblocks && b - b0 < LZS_PLAN_BC_GROUP_MAX_BLOCKS; b++) {
+        const uint64_t len = len_each ? len_each[b] : len_all;
+        if (b > b0 && sum + len > bound) break;
+        sum += len;
+    }
+    return b - b0;
+}
+
+/* A block of len bytes in segments of seg: one for every seg bytes begun, and one for a block without a byte (it carries the
+ * block's end marker). */
+static inline uint64_t lzs_plan_batch_compress_nseg(uint32_t len, uint32_t seg) { return len ? ((uint64_t)len + seg - 1u) / seg : 1u; }
+
+/* The segment table of the blocks b0 .. b0 + nb - 1: for every segment the block it belongs to, counted from b0, and where in
+ * the block it starts.  seg_block, seg_start NULL: only counted.  Returns the number of segments. */
+static inline uint64_t lzs_plan_batch_compress_segments(uint32_t *seg_block, uint32_t *seg_start, const uint32_t *len_each, uint32_t len_all,
+                                                        uint64_t b0, uint64_t nb, uint32_t seg)
+{
+    uint64_t k = 0;
+    for (uint64_t b = 0; b < nb; b++) {
+        const uint32_t len = len_each ? len_each[b0 + b] : len_all;
+        const uint64_t ns = lzs_plan_batch_compress_nseg(len, seg);
+        for (uint64_t j = 0; j < ns; j++, k++)
+            if (seg_block) { seg_block[k] = (uint32_t)b; seg_start[k] = (uint32_t)(j * seg); }
+    }
+    return k;
+}
+
 #endif

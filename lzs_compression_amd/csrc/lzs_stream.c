@@ -79,7 +79,7 @@ LZS_HIDDEN size_t stream_call_ends(size_t result, int rc, int dev, const char *w
  *    16 MiB                          4.032   3.854   3.785   3.961    5.132
  * (round 2 used 4 KiB up to 2 MiB: 64 KiB in 0.29 ms).  A short piece of the incremental interface, whose block collects
  * ~10 KiB, is all latency too: at 512-byte calls 41 MB/s in 4 KiB segments, 62 in 1 KiB, 67 in 512 B. */
-static uint32_t stream_seg(size_t n)
+LZS_HIDDEN uint32_t stream_seg(size_t n)
 {
     const uint32_t v = lzs_env()->stream_seg;
     size_t seg = v ? v
